@@ -6,7 +6,11 @@
 A "step" is one env.step() of every environment of the rank (controller + forward dynamics + soft contact + sensors +
 reward + termination + auto-reset), actions drawn in-kernel from the counter-based stream of BASELINE.md section 4,
 transitions written into rollout blocks in HBM; with N > 1 each finished block is all-gathered over RCCL on a side
-stream.  Prints ONE JSON line on rank 0."""
+stream.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, time --steps steps, print the line.  --full adds what takes runs
+of its own (the CPU baseline: the oracle on the host's cores).  --dump-outputs DIR writes what the last timed step returned to its caller
+(the rows of that step in the rollout block: obs, act, rew, done) as DIR/<name>.npy, so that two builds can be compared output for output."""
 import argparse
 import importlib
 import json
@@ -59,6 +63,28 @@ def cpu_baseline(workload, n_envs, budget_s=float(os.environ.get("USIM_CPU_BUDGE
                       f"{'-O3 -march=native' if native else '-O3'}"}
 
 
+DUMP_CAP_BYTES = 64 << 20          # --dump-outputs writes at most this much in all (N > 1: each rank its share)
+
+
+def dump_outputs(dirname, blk, row, suffix="", cap_bytes=DUMP_CAP_BYTES):
+    """Row `row` of every tensor of the rollout block `blk` (what the step that wrote it returned to its caller) as <dirname>/<name><suffix>.npy,
+    float32 (done flags as 0.0 / 1.0).  If that exceeds cap_bytes, a fixed seeded sample of the environments is written instead, with their
+    indices in env_index<suffix>.npy."""
+    import numpy as np
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {key: t[row].detach().to("cpu").numpy().astype(np.float32) for key, t in sorted(blk.items())}
+    n = next(iter(arrays.values())).shape[0]
+    per_env = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    keep = max(1, cap_bytes // max(per_env, 1))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {key: a[idx] for key, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    for key, a in arrays.items():
+        np.save(out / f"{key}{suffix}.npy", a)
+
+
 def _self_launch(gpus, argv):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves, as CHILD processes of a parent that has
     not touched a GPU (nothing above this line imports torch), exactly the way the driver would -- torch.distributed.run, one rank per GPU,
@@ -88,7 +114,11 @@ def main():
     ap.add_argument("--workload", choices=["soft", "rigid", "full"], default="soft")
     ap.add_argument("--block", type=int, default=256, help="rollout block length T (steps per all-gather)")
     ap.add_argument("--randomize", action="store_true", help="BASELINE configs[4]: per-env randomised stiffness/damping + probe friction")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need and takes runs of its own: "
+                    "the CPU baseline (cpu_baseline: the fp64 oracle on the host's cores, up to USIM_CPU_BUDGET_S seconds)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "(its rows of the rollout block: obs, act, rew, done) as DIR/<name>.npy in float32; N > 1: DIR/<name>_rank<r>.npy per rank")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--gather", choices=["rccl", "p2p"], default="rccl", help="N > 1: RCCL all-gather (resident workgroups on the CUs) or peer-to-peer copies "
                     "of the packed block (copy engines, no CUs; distributed.P2PRolloutGather)")
@@ -212,8 +242,10 @@ def main():
     # kernel-duration leg of the roofline: HIP events around every block of step launches, recorded on the launch stream (the
     # simulator is launched on torch's current stream, so torch events are events of that stream); read after the timed region,
     # the host never blocks inside it
+    last = None                                            # (block, row) that the last timed step wrote
     while done_s < args.steps:                             # EXACTLY args.steps timed steps
         k = min(T, args.steps - done_s)
+        last = (b, k - 1)
         e0, e1 = evs[ib]
         e0.record()
         rollout(step, k, io=io_of(b, 0, k))               # with the gather: simulate block b while block b^1 is in flight
@@ -233,6 +265,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, blocks[last[0]], last[1], "" if world == 1 else f"_rank{rank}", DUMP_CAP_BYTES // world)
     dev_ms = sum(a.elapsed_time(b_) for a, b_ in evs) if on_gpu else elapsed * 1e3
     # the event brackets contain the step launches and, every 256 steps, one reset-bank refill launch: take its device time out, so that
     # avg_kernel_us is the step kernel's (what a rocprofv3 kernel trace reports for it)
@@ -332,7 +366,7 @@ def main():
                                   "SIMD would take four such waves (profiles/r05/micro_two_wave.txt), and at 4096 envs the 512 registers per SIMD lane hold two; the state of a multi-step "
                                   "launch lives in registers and L2; see DESIGN.md section 5")},
         }
-        if world == 1 and on_gpu and not args.no_cpu_baseline:
+        if args.full and world == 1 and on_gpu and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, n)
         result = json.dumps(out)
     else:

@@ -8,6 +8,7 @@ import sys
 from pathlib import Path
 
 import pytest
+import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -50,6 +51,44 @@ def test_single_rank_needs_no_launcher_and_a_mismatched_launcher_is_an_error():
     # --gpus 2 under a launcher that started one rank: refuse (a 1-GPU number must never be labelled as the answer to N = 2)
     r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1"], extra_env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stdout + r.stderr)
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: after exactly --steps timed steps (after --presteps and --warmup untimed ones) the rows that the last timed step wrote
+    into the rollout block, one float32 .npy per output; the stand-in stepper stamps the global step, so the file says which step that was"""
+    import numpy as np
+    d = tmp_path / "out"
+    r = _run(["--steps", "7", "--warmup", "3", "--presteps", "2", "--block", "3", "--envs-per-gpu", "5", "--dump-outputs", str(d)])
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == 7 and out["ms_per_step"] > 0 and "cpu_baseline" not in out
+    files = {p.stem: np.load(p) for p in d.iterdir()}
+    assert set(files) == {"obs", "act", "rew", "done"} and all(p.suffix == ".npy" for p in d.iterdir())
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert files["obs"].shape == (5, 19) and files["act"].shape == (5, 6) and files["rew"].shape == (5,) and files["done"].shape == (5,)
+    last = 2 + 3 + 7 - 1
+    assert (files["obs"][:, 0] == np.arange(5)).all() and (files["obs"][:, 1] == last).all()
+    assert (files["rew"] == np.arange(5) * 1000.0 + last).all() and (files["done"] == float(last % 5 == 4)).all()
+    # same arguments, same outputs
+    d2 = tmp_path / "again"
+    r = _run(["--steps", "7", "--warmup", "3", "--presteps", "2", "--block", "3", "--envs-per-gpu", "5", "--dump-outputs", str(d2)])
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert all(np.array_equal(a, np.load(d2 / f"{name}.npy")) for name, a in files.items())
+
+
+def test_dump_outputs_samples_beyond_the_cap(tmp_path):
+    """more than the cap: a fixed seeded sample of the environments, with their indices"""
+    import numpy as np
+    import bench
+    blk = {"obs": torch.arange(2 * 100 * 19, dtype=torch.float32).view(2, 100, 19), "done": torch.ones((2, 100), dtype=torch.uint8)}
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, blk, 1, cap_bytes=40 * 80)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(a) == {"obs.npy", "done.npy", "env_index.npy"} and a["obs.npy"].shape == (40, 19)
+    idx = a["env_index.npy"].astype(int)
+    assert len(set(idx)) == 40 and (np.diff(idx) > 0).all()
+    assert np.array_equal(a["obs.npy"], blk["obs"][1].numpy()[idx]) and (a["done.npy"] == 1.0).all()
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / k)) for k, v in a.items())
 
 
 def test_gathered_block_holds_every_shard(tmp_path):

@@ -23,7 +23,7 @@ def _run(args, env=None):
 
 
 def test_bench_json_contract_default_workload():
-    out = _run(["--gpus", "1", "--steps", "256", "--warmup", "32"], env={"USIM_CPU_BUDGET_S": "2"})
+    out = _run(["--gpus", "1", "--steps", "256", "--warmup", "32", "--full"], env={"USIM_CPU_BUDGET_S": "2"})
     assert REQUIRED <= set(out)
     assert out["metric"].startswith("env-steps/sec") and out["unit"] == "env-steps/s" and out["higher_is_better"] is True
     assert out["n_gpus"] == 1 and out["steps"] == 256 and out["warmup"] == 32 and out["scaling"] == "weak" and out["vs_baseline"] is None
@@ -44,6 +44,24 @@ def test_bench_json_contract_default_workload():
     assert "valu_frac" not in rf
     cb = out["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "env-steps/s" and cb["value"] > 0 and cb["cores"] >= 1 and "sample" in cb
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """without --full: the headline line and nothing that takes runs of its own; --dump-outputs writes the last timed step's rows of the rollout
+    block, and the same arguments give the same outputs"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = _run(["--gpus", "1", "--steps", "64", "--warmup", "16", "--dump-outputs", str(d)])
+        assert REQUIRED - {"cpu_baseline"} <= set(out) and "cpu_baseline" not in out
+        assert out["steps"] == 64 and out["ms_per_step"] > 0 and abs(out["value"] - 4096 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-6
+        dumps.append({p.stem: np.load(p) for p in d.iterdir()})
+    a, b = dumps
+    assert set(a) == {"obs", "act", "rew", "done"} and all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["obs"].shape == (4096, 19) and a["act"].shape[0] == 4096 and a["rew"].shape == (4096,) and a["done"].shape == (4096,)
+    assert set(np.unique(a["done"])) <= {0.0, 1.0} and np.abs(a["obs"]).max() > 0
+    assert all(np.array_equal(a[k], b[k]) for k in a)
 
 
 def test_bench_gather_path_over_rccl_with_one_rank():

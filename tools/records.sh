@@ -13,7 +13,7 @@ mkdir -p profiles/$TAG
 python3 tools/make_traffic.py $G/prof_${TAG}_soft $G/prof_${TAG}_rigid 256 profiles/$TAG/issue.json > profiles/$TAG/traffic.json
 cp profiles/$TAG/traffic.json "$G/${TAG}_traffic.json"; cp profiles/$TAG/issue.json "$G/${TAG}_issue.json"
 tools/bench_matrix.sh > /dev/null
-python3 bench.py > "$G/${TAG}_bench_soft.json" 2> /dev/null
+python3 bench.py --full > "$G/${TAG}_bench_soft.json" 2> /dev/null
 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$G/${TAG}_bench_driver.json" 2> /dev/null
 python3 bench.py --workload rigid --no-cpu-baseline > "$G/${TAG}_bench_rigid.json" 2> /dev/null
 python3 bench.py --envs-per-gpu 8192 --randomize --steps 1024 --warmup 256 --no-cpu-baseline > "$G/${TAG}_bench_config5.json" 2> /dev/null
@@ -31,7 +31,7 @@ tools/prof_collector.sh 4096 > "$G/${TAG}_prof_collector.txt" 2>&1
 python3 tools/ppo_demo.py 60 4096 128 tracking fused 2>&1 | grep -v amdgpu.ids > "$G/${TAG}_ppo_fused.txt"
 for m in tracking fixed variable_z wrench; do python3 tools/gpu_soak.py 4096 5000 $m 2>&1 | grep -v amdgpu.ids; done > "$G/${TAG}_soak.txt"
 # the full torso (csrc/usim_full.h): bench lines, rocprofv3, replays of the reference checkpoints, full-size parity
-python3 bench.py --workload full --steps 40 --warmup 10 > "$G/${TAG}_bench_full.json" 2> /dev/null
+python3 bench.py --full --workload full --steps 40 --warmup 10 > "$G/${TAG}_bench_full.json" 2> /dev/null
 python3 bench.py --workload full --steps 20 --warmup 5 --no-cpu-baseline > "$G/${TAG}_bench_full_driver.json" 2> /dev/null
 python3 bench.py --workload full --steps 40 --warmup 10 --pgs-iters 12 --no-cpu-baseline > "$G/${TAG}_bench_full_12.json" 2> /dev/null
 python3 bench.py --workload full --steps 40 --warmup 10 --envs-per-gpu 8192 --no-cpu-baseline > "$G/${TAG}_bench_full_8192.json" 2> /dev/null

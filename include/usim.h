@@ -82,8 +82,8 @@ typedef struct usim_config {
     int32_t env_offset;                        /* global index of env 0 of this handle (multi-GPU shard) */
     int32_t lanes_per_env;                     /* kernel mapping: 0 automatic; 16 lanes per environment (arm mathematics distributed over the group); 64 (soft torso: the split
                                                 * kernel with 8-lane groups, 32 environments per workgroup; automatic beyond 4096 envs); 32 (soft torso: the
-                                                * same, arm side and lattice / contact side in two waves that share a SIMD; the automatic choice for the soft torso);
-                                                * 8 (soft torso; arm mathematics replicated per lane) or 1 (rigid torso: one environment per lane) */
+                                                * same, arm side and lattice / contact side in two waves that share a SIMD; the automatic choice for the soft torso).
+                                                * Rigid torso: 0 or 16; anything else is USIM_ERR_INVALID */
     int32_t torso_shape;                       /* use_box_torso (rl_config.yaml:57): 0 box (soft_box.xml), 1 cylinder (soft_human_torso.xml) */
     int32_t waves_per_simd;                    /* 16-lane step kernel: register budget for 1 or 2 waves per SIMD; 0 auto (1 up to 4096 envs, 2 beyond) */
     int32_t robot;                             /* USIM_ROBOT_*: robots of ultrasound.py:137 */
@@ -99,8 +99,8 @@ typedef struct usim_config {
     double probe_radius2, probe_height;        /* ... upper capsule: radius, height of its axis above the tip capsule's (probe_height > |probe_radius2 - probe_radius|) */
     int32_t substeps;                          /* physics steps per env.step(): int(control_timestep / model_timestep) of robosuite MujocoEnv.step, model timestep 2 ms
                                                 * (1 with the shipped control_freq 500, rl_config.yaml:26; 25 with the env default 20, ultrasound.py:119).  control_dt above is
-                                                * the CONTROL timestep (ultrasound.py:542); the physics step is control_dt / substeps.  substeps > 1: 16-lane kernels only
-                                                * (USIM_ERR_UNSUPPORTED otherwise) */
+                                                * the CONTROL timestep (ultrasound.py:542); the physics step is control_dt / substeps.  substeps > 1: not with
+                                                * USIM_TORSO_FULL (USIM_ERR_UNSUPPORTED) */
     int32_t probe_geoms;                       /* colliding geoms of the probe body.  2 (default): ultrasound_probe_gripper.xml:8-9 declares `probe_collision` AND `probe_visual`
                                                 * on the same mesh, and the visual one carries no contype = conaffinity = 0 -- with MuJoCo's defaults it collides too, with the
                                                 * default friction (1, 0.005, 0.0001): every probe-element pair has two coincident contacts.  With pair_model = 0 restated as one contact whose normal

@@ -306,8 +306,8 @@ template <int MODE>
 static int launch(usim_handle* h, DevIO io, int flags, long long rstep, hipStream_t s) {
     io.bank_row0 = h->bank_row0;
     hipError_t e;
-    // 16 lanes per environment: the kernels with the distributed arm mathematics (usim_step16.h); the 8-lane / one-lane mappings run the
-    // kernels of usim_kernels.hip
+    // the full torso runs usim_step_kernel (one wave per environment); the rigid and soft torsos the kernels with the arm mathematics distributed over
+    // 16 lanes (usim_step16.h)
     if (h->cfg.torso == USIM_TORSO_FULL) {
         e = launch_step<2, 64, MODE>(h, io, flags, rstep, s);           // one wave per environment (usim_full.h)
     } else if (h->lpe == 64 && MODE == 0) {
@@ -323,14 +323,12 @@ static int launch(usim_handle* h, DevIO io, int flags, long long rstep, hipStrea
         if (io.nsub > 1 || h->C.substeps > 1) hipLaunchKernelGGL((usim_step32_kernel<true, 16>), grid, block, h->lds32_bytes, s, h->d_M, h->d_C, h->state, h->n, h->npad, io, flags, rstep);
         else hipLaunchKernelGGL((usim_step32_kernel<false, 16>), grid, block, h->lds32_bytes, s, h->d_M, h->d_C, h->state, h->n, h->npad, io, flags, rstep);
         e = hipGetLastError();
-    } else if (h->lpe == 16 || h->lpe == 32 || h->lpe == 64) {
+    } else {
         // (reset computations are not register-critical: always the two-waves-per-SIMD build)
         if (!h->n_el) e = launch_step16<0, 2, MODE>(h, io, flags, rstep, s);
         else if constexpr (MODE == 0) e = (h->occ == 1) ? launch_step16<1, 1, 0>(h, io, flags, rstep, s) : launch_step16<1, 2, 0>(h, io, flags, rstep, s);
         else e = launch_step16<1, 2, MODE>(h, io, flags, rstep, s);
     }
-    else if (!h->n_el) e = launch_step<0, 1, MODE>(h, io, flags, rstep, s);
-    else e = launch_step<1, 8, MODE>(h, io, flags, rstep, s);
     if (e != hipSuccess) { h->hip_err = std::string("usim_step_kernel launch: ") + hipGetErrorString(e); return USIM_ERR_HIP; }
     return USIM_OK;
 }
@@ -418,22 +416,13 @@ int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** ou
     HIPCHK(h, hipEventCreate(&h->ev1));
     for (int i = 0; i < usim_handle::RF_RING; ++i) { HIPCHK(h, hipEventCreate(&h->rf0[i])); HIPCHK(h, hipEventCreate(&h->rf1[i])); }
     // kernel mapping
-    // Rigid torso: 16 lanes per environment (arm mathematics distributed over the group) or, with lanes_per_env = 1, one lane each.
+    // Rigid torso: 16 lanes per environment (arm mathematics distributed over the group).
     // Soft torso, automatic choice (unless a register budget was asked for): the split kernel -- up to 4096 envs/GPU with 16-lane groups (32: two
     // waves per quad of environments, 16 environments per workgroup = one workgroup per CU), beyond with 8-lane groups (64: two environments per
     // DPP row, 32 environments per workgroup: 8192 envs still one workgroup per CU, 23.8 vs 29.3 us/step; profiles/r03/bench_matrix.txt).
     h->lpe = h->n_el ? (cfg->lanes_per_env == 0 ? (cfg->waves_per_simd == 0 ? (n_envs <= 4096 ? 32 : 64) : 16) : cfg->lanes_per_env)
                      : (cfg->lanes_per_env == 0 ? 16 : cfg->lanes_per_env);
-    if (h->n_el ? (h->lpe != 8 && h->lpe != 16 && h->lpe != 32 && h->lpe != 64) : (h->lpe != 1 && h->lpe != 16)) return USIM_ERR_INVALID;
-    if (cfg->robot != USIM_ROBOT_PANDA && h->lpe != 16 && h->lpe != 32 && h->lpe != 64) {
-        h->hip_err = "the UR5e runs on the table-driven 16-lane kernels only (lanes_per_env 0 or 16)";
-        return USIM_ERR_UNSUPPORTED;
-    }
-    if (C.substeps > 1 && h->lpe != 16 && h->lpe != 32 && h->lpe != 64) {
-        // several physics substeps per control step run inside the multi-step kernels (the `fixed` mode's goal, anchored at the policy step, is held in LDS)
-        h->hip_err = "substeps > 1 (control_freq below 500) needs the 16-lane kernels (lanes_per_env 0, 16, 32, 64)";
-        return USIM_ERR_UNSUPPORTED;
-    }
+    if (h->n_el ? (h->lpe != 16 && h->lpe != 32 && h->lpe != 64) : h->lpe != 16) return USIM_ERR_INVALID;
     if (cfg->torso == USIM_TORSO_FULL) {
         // the full torso runs one mapping: a wave per environment, the Panda's constants, one physics step per control step, one step per launch
         if (cfg->robot != USIM_ROBOT_PANDA || C.substeps > 1) { h->hip_err = "torso = USIM_TORSO_FULL: Panda, substeps = 1"; return USIM_ERR_UNSUPPORTED; }
@@ -459,12 +448,6 @@ int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** ou
         HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step16_kernel<1, 2, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds16_bytes));
         HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step16_kernel<1, 2, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds16_bytes));
     }
-    h->lds_bytes = 0;
-    if (h->n_el && h->lpe == 8) {
-        h->lds_bytes = (size_t)GroupGeom<8>::LDS_WORDS * sizeof(float);
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step_kernel<1, 8, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step_kernel<1, 8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    }
     return USIM_OK;
 }
 
@@ -485,7 +468,7 @@ void usim_destroy(usim_handle* h) {
 }
 
 int usim_set_mapping(usim_handle* h, int lanes_per_env, int waves_per_simd) {
-    if (!h || !h->n_el || h->lpe == 8 || h->cfg.torso == USIM_TORSO_FULL || (lanes_per_env != 16 && lanes_per_env != 32 && lanes_per_env != 64) || waves_per_simd < 0 || waves_per_simd > 2) return USIM_ERR_INVALID;
+    if (!h || !h->n_el || h->cfg.torso == USIM_TORSO_FULL || (lanes_per_env != 16 && lanes_per_env != 32 && lanes_per_env != 64) || waves_per_simd < 0 || waves_per_simd > 2) return USIM_ERR_INVALID;
     h->lpe = lanes_per_env;
     h->occ = waves_per_simd ? waves_per_simd : (h->n <= 4096 ? 1 : 2);
     return USIM_OK;

@@ -58,7 +58,7 @@ struct DevModel {
     float base[3];                  // robot base in world coordinates
     float ikb[3];                   // systematic offset of the reference's initial-pose IK
     float invw, wfix, wten;         // contact regulariser scale, lattice soft-equality weights
-    float armature[NJ];             // rotor inertia per joint (usim_config.armature_scale * 5 / (i + 1)): the one-lane / 8-lane / full-torso kernels; the 16-lane kernels read the arm table
+    float armature[NJ];             // rotor inertia per joint (usim_config.armature_scale * 5 / (i + 1)): the full-torso kernel; the 16-lane kernels read the arm table
     const float* tables;            // this handle's lattice table block in HBM (TB_WORDS words, 16-byte aligned; soft torso only)
 };
 

@@ -156,10 +156,8 @@ DI void sincos_(float x, float& s, float& c) {
     c = __int_as_float(__float_as_int(cc) ^ (((ki + 1) & 2) << 30));       // cos < 0 in quadrants 1, 2
 }
 
-// INLINE_TRIG: the branch-free sincos_ above (one environment per lane, where registers are plentiful); otherwise the library
-// sincosf, whose internal branches keep the scheduling regions -- and with them the register pressure -- of the grouped kernels small
-// (docs/DESIGN_rounds_1-3.md section 7, negative result v)
-template <bool INLINE_TRIG>
+// (the library sincosf, not sincos_ above: its internal branches keep the scheduling regions -- and with them the register pressure -- of
+// the step kernel small; docs/DESIGN_rounds_1-3.md section 7, negative result v)
 DI void fk(const DevModel& M, const float* q, Kin& K) {
     f3 px = mk(1.f, 0.f, 0.f), py = mk(0.f, 1.f, 0.f), pz = mk(0.f, 0.f, 1.f), po = mk(0.f, 0.f, 0.f);
 #pragma unroll
@@ -170,7 +168,7 @@ DI void fk(const DevModel& M, const float* q, Kin& K) {
         else if (ROTX[i] > 0) { ay = pz; az = mk(-py.x, -py.y, -py.z); }
         else { ay = mk(-pz.x, -pz.y, -pz.z); az = py; }
         float s, c;
-        if constexpr (INLINE_TRIG) sincos_(q[i], s, c); else sincosf(q[i], &s, &c);
+        sincosf(q[i], &s, &c);
         f3 nx = ax * c + ay * s, ny = ay * c - ax * s;
         K.o[i] = o; K.z[i] = az;
         if (i < NJ - 1) K.c[i] = o + nx * LCOM[i][0] + ny * LCOM[i][1] + az * LCOM[i][2];

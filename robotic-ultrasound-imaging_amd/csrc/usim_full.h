@@ -6,7 +6,7 @@
 // order of visits on dense matrices; this file is written independently of it.  The solve starts from the forces of the previous physics step (LATF_WTAB / LATF_WPROBE in the
 // environment's lattice block): cold, 24 sweeps over ~54 coupled sticking contacts are nowhere near converged (profiles/r05/full_torso_convergence.txt).
 //
-// Mapping: ONE WAVE PER ENVIRONMENT (usim_step_kernel<2, 64, MODE>: the arm mathematics is replicated in the 64 lanes as in the 8-lane kernel; the torso is what the
+// Mapping: ONE WAVE PER ENVIRONMENT (usim_step_kernel<2, 64, MODE>: the arm mathematics is replicated in the 64 lanes; the torso is what the
 // lanes share).  Lane l owns elements 5 l .. 5 l + 4 (s, sdot in registers).
 //   * Torso Hessian H = [M I, 0, m N; 0, I_b, 0; m N', 0, m L] (body frame: linear 3, angular 3, sliders 270; N = slide axes, L = (1 + w_fix) I + w_ten Laplacian of the
 //     shell graph, degree <= 4).  K = H^-1 is never formed: with S = M I - m N L^-1 N' (3 x 3) and P = L^-1 N' (270 x 3, host, float64)

@@ -10,19 +10,19 @@
 // Model and algorithm are specified in DESIGN.md; this file is written independently of oracle/.
 //
 // Mapping.  G lanes of a wave64 form the group of one environment.
-//   rigid torso  G = 1 : one environment per lane, 64 per workgroup, everything in VGPRs, no LDS.
-//   soft torso   G = 8 / 16 : 16 environments per workgroup (4096 envs -> 256 workgroups, one per CU, G/4 waves
-//                each).  All lanes of a group carry the same 7-DoF arm state (the arm mathematics is replicated, those
-//                lanes would otherwise idle) and split the 99-element lattice, the collision tests and the contacts:
+//   rigid / soft torso  G = 16 (the split kernel of the soft torso also G = 8): the kernels of usim_step16.h, which distribute the arm mathematics over
+//                the group.  This file holds the lattice and contact phases of the soft torso they share; the lanes of a group split the 99-element
+//                lattice, the collision tests and the contacts:
 //                  - the lattice inverse (99 x 100 fp32) and the element tables are workgroup-resident in LDS; per-environment
 //                    scratch is a 548-word LDS block (548 mod 64 = 36 puts the 16-byte windows of the 16 environments on
 //                    disjoint bank groups);
 //                  - the lattice right-hand side is a 5-point stencil on a zero-bordered grid, the lattice solve
 //                    A~ = Linv X (X = the right-hand sides of the wave's environments) runs on the matrix cores
-//                    (v_mfma_f32_4x4x1, step kernel) -- the one dense contraction of the path;
+//                    (v_mfma_f32_4x4x1) -- the one dense contraction of the path;
 //                  - contacts keep ascending shell-id order through a wave ballot;
 //                  - contact k lives in the registers of lane k; the dual problem is solved on 3 x 3 Delassus blocks held
 //                    per lane, a Gauss-Seidel visit broadcasts three force increments with DPP row_newbcast.
+//   full torso   G = 64: usim_step_kernel<2, 64, MODE> below, one wave per environment (usim_full.h).
 // Per-environment state is read and written once per step as rows of the SoA state block in HBM.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,8 +65,6 @@ template <int G> struct GroupGeom {
     static constexpr int NT = 64 * WAVES;
     static constexpr int LDS_WORDS = TB_WORDS + EPB * GE_STRIDE;
 };
-// two workgroups of the 8-lane mapping share a CU at 8192 envs/GPU (2 waves each): both must fit the 160 KB of LDS
-static_assert(2 * GroupGeom<8>::LDS_WORDS * 4 <= 160 * 1024, "LDS block too large for two workgroups per CU");
 
 DI void group_sync() {
     // the lanes of a group exchange data through LDS inside one wave: order the LDS traffic, no s_barrier needed
@@ -298,7 +296,7 @@ DI void contact_overflow(float* lds, const int eb, const int gl, const int gbase
 // leave the contact records (ascending shell id; the MAXC deepest when more were found) in LDS.  Returns the number found (may exceed MAXC).
 // PART 0: everything; 1: staging + right-hand side only (needs no arm quantity); 2: solve + collision only (after a PART 1 call); 3: solve only
 // (needs no arm quantity either: the split kernel's lattice side runs it while it would otherwise wait for the site pose); 4: collision only (after PART 3).
-template <int G, int NE, bool MM, int PART = 0, bool QM = false>
+template <int G, int NE, int PART = 0, bool QM = false>
 DI int lattice_front(float* lds, const int eb, const int gl, const int gbase, const DevModel& M, const DevCfg& C, const int tsim,
                      const float kst, const float kdmp, const bool live, const float* s_pre, const float* sd_pre,
                      const f3 Kx, const f3 Ksy, const f3 Ksz, unsigned long long* dbg, const float* queue = nullptr, const int q0 = 0, const int q1 = 0) {
@@ -387,7 +385,7 @@ DI int lattice_front(float* lds, const int eb, const int gl, const int gbase, co
                                     // ---- a~ = Linv * rhs ----
                     if constexpr (PART == 4) {
                         collide_round(0);
-                    } else if constexpr (MM) {
+                    } else {
                         // Matrix-core form (every lane of the wave is active here): the wave's environments are the columns of one dense
                         // product A~[99 x EPW] = Linv[99 x 100] X[100 x EPW], issued as v_mfma_f32_4x4x1 (16 blocks of 4 rows x 4 columns
                         // per instruction).  Lane l feeds Linv row l (and row 64 + l) as the A operand and the rhs of environment l % 4 as
@@ -435,39 +433,6 @@ DI int lattice_front(float* lds, const int eb, const int gl, const int gbase, co
                                 *reinterpret_cast<float4*>(&dst[64 + 4 * blk]) = make_float4(acc1[u][0], acc1[u][1], acc1[u][2], acc1[u][3]);
                         }
                         group_sync();
-                    } else {
-                        // VALU form for launches whose environments may be masked: lane gl computes rows gl, gl+G, ...; Linv rows and rhs
-                        // are read as 16-byte chunks.  (The collision runs first: its queue overlays the a~ area this product fills.)
-                        collide_round(0);
-                        const float4* xv = reinterpret_cast<const float4*>(&EBF(GE_X));
-                        constexpr int RB = 4;                              // rows per pass share one read of the rhs chunk
-    #pragma unroll
-                        for (int i0 = 0; i0 < NE; i0 += RB) {
-                            const float4* lr[RB];
-                            float acc[RB], bcc[RB];
-    #pragma unroll
-                            for (int j = 0; j < RB; ++j) {
-                                int r = gl + (i0 + j) * G; if (r >= N_TOP) r = N_TOP - 1;
-                                lr[j] = reinterpret_cast<const float4*>(&lds[TB_LINV + r * LROW]);
-                                acc[j] = 0.f; bcc[j] = 0.f;
-                            }
-    #pragma unroll 5
-                            for (int c = 0; c < LROW / 4; ++c) {
-                                const float4 x = xv[c];
-    #pragma unroll
-                                for (int j = 0; j < RB; ++j) {
-                                    const float4 u = lr[j][c];
-                                    acc[j] = fmaf(u.x, x.x, acc[j]); bcc[j] = fmaf(u.y, x.y, bcc[j]);
-                                    acc[j] = fmaf(u.z, x.z, acc[j]); bcc[j] = fmaf(u.w, x.w, bcc[j]);
-                                }
-                            }
-    #pragma unroll
-                            for (int j = 0; j < RB; ++j) {
-                                const int r = gl + (i0 + j) * G;
-                                if (i0 + j < NE && r < N_TOP) EBF(GE_A + r) = acc[j] + bcc[j];
-                            }
-                        }
-                        LSTAMP(6);
                     }
                     if constexpr (!QM && PART != 3) contact_overflow<G>(lds, eb, gl, gbase, nc);
     return nc;
@@ -993,21 +958,20 @@ struct StepOut {               // results of one forward pass that the env logic
     int overflow;
 };
 
+// Step kernel of the full torso (TORSO = 2, G = 64: one wave per environment, usim_full.h); the rigid and soft torsos run the kernels of usim_step16.h.
 // MODE 0: one env.step() per environment; a finished environment takes its next initial state from the reset bank.
 // MODE 1: reset computation (draws, initial-pose IK, zero-torque forward pass) for the environments selected by the mask
 //         (written to the live state) or for the (env, episode) items of the refill work list (written to the reset bank).
 template <int TORSO, int G, int MODE>
-__global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_step_kernel(const DevModel M, const DevCfg C, float* __restrict__ st, int n, int npad,
+__global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const DevModel M, const DevCfg C, float* __restrict__ st, int n, int npad,
                                                                       const DevIO io, int flags, long long rstep) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // step waves outrank the background refill waves that may share their SIMD (priority, then age, arbitrates VALU issue)
     __builtin_amdgcn_s_setprio(MODE == 0 ? 3 : 0);
-    constexpr int EPW = GroupGeom<G>::EPW, EPB = GroupGeom<G>::EPB, NT = GroupGeom<G>::NT;
-    constexpr int NTT = NT;
-    static_assert(!TORSO || G >= MAXC, "the contact solver gives every contact its own lane of the group");
+    static_assert(TORSO == 2 && G == 64, "the full torso's mapping only");
+    constexpr int EPW = GroupGeom<G>::EPW, EPB = GroupGeom<G>::EPB;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gl = lane % G, ge = lane / G;           // lane within the group, group (= environment) within the wave
-    const int gbase = lane - gl;                      // ballot bit of the group's first lane
     const int eb = wave * EPW + ge;                   // environment within the workgroup
     // refill launches walk the work list with a grid-stride loop; every other launch runs the body once
     const bool refill = (MODE == 1) && io.refill != 0;
@@ -1027,8 +991,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
     const bool auto_reset = (flags & LF_AUTO_RESET) != 0;
 #define ST(f) st[scalar_index((f), (size_t)ei)]
 #define STI(f) (reinterpret_cast<int*>(st))[scalar_index((f), (size_t)ei)]
-#define LAT(w) st[(size_t)F_LAT * npad + (size_t)ei * (TORSO == 2 ? LATF_ENV_WORDS : LAT_ENV_WORDS) + (w)]
-#define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
+#define LAT(w) st[(size_t)F_LAT * npad + (size_t)ei * LATF_ENV_WORDS + (w)]
 // phase timeline probe (diagnostics only): wave 0 of workgroup 0 stamps the shader clock when io.dbg is set
 // The stamps exist only in the profiling build (make prof -> libusim_prof.so, -DUSIM_TSTAMP): each one is a branch, and sixteen of them
 // cost the production kernel 2 % (25.6 vs 25.1 us/step).  -DUSIM_TSTAMP_NOWAIT additionally keeps the stamps from draining memory traffic.
@@ -1041,20 +1004,6 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
 #endif
 #define BK(slot, f) st[(size_t)io.bank_row0 * npad + ((size_t)ei * BANK_DEPTH + (slot)) * BANK_STRIDE + (f)]
 #define BKI(slot, f) (reinterpret_cast<int*>(st))[(size_t)io.bank_row0 * npad + ((size_t)ei * BANK_DEPTH + (slot)) * BANK_STRIDE + (f)]
-    if (TORSO == 1 && item0 == (refill ? (int)blockIdx.x * EPB : 0)) {
-        // workgroup-resident copy of the lattice tables (inverse 99 x 100, element positions/axes/neighbours/shell ids):
-        // 16-byte loads, all issued before the first LDS store
-        const float4* src = reinterpret_cast<const float4*>(M.tables);
-        float4* dst = reinterpret_cast<float4*>(lds);
-        constexpr int NV = TB_WORDS / 4, PER = (NV + NTT - 1) / NTT;
-        float4 tmp[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) { int idx = threadIdx.x + i * NTT; tmp[i] = (idx < NV) ? src[idx] : make_float4(0, 0, 0, 0); }
-#pragma unroll
-        for (int i = 0; i < PER; ++i) { int idx = threadIdx.x + i * NTT; if (idx < NV) dst[idx] = tmp[i]; }
-        __syncthreads();
-    }
-
     TSTAMP(0);
     // ---------------- load state ----------------
     float sv[F_NSCALAR];                               // the 40 scalar words of the environment, in Field order: ten 16-byte loads
@@ -1070,20 +1019,18 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
     float u0 = sv[F_U0], vbar = sv[F_VBAR], fzbar = sv[F_FZBAR], fzprev = sv[F_FZPREV], dfz = sv[F_DFZ];
     float kst = sv[F_KST], kdmp = sv[F_KDMP], mu = sv[F_MU], epret = sv[F_EPRET];
     int t = __float_as_int(sv[F_T]), touched = __float_as_int(sv[F_TOUCH]), episode = __float_as_int(sv[F_EPISODE]), status = __float_as_int(sv[F_STATUS]);
-    // lattice rows of this lane (elements gl, gl+G, ...): prefetched now, consumed after the arm phase
-    constexpr int NE = (TORSO == 2) ? FE : (TORSO ? (N_TOP + G - 1) / G : 1);
-    float s_pre[NE], sd_pre[NE];
+    // sliders of this lane (lane l owns elements 5 l .. 5 l + 4): prefetched now, consumed after the arm phase
+    float s_pre[FE], sd_pre[FE];
 #pragma unroll
-    for (int i = 0; i < NE; ++i) {
-        const int e = (TORSO == 2) ? FE * gl + i : gl + i * G;          // (full torso: lane l owns elements 5 l .. 5 l + 4)
+    for (int i = 0; i < FE; ++i) {
+        const int e = FE * gl + i;
         s_pre[i] = 0.f; sd_pre[i] = 0.f;
-        if (TORSO == 1 && MODE == 0 && e < N_TOP) { s_pre[i] = LAT(LAT_S + e); sd_pre[i] = LAT(LAT_SD + e); }
-        if (TORSO == 2 && MODE == 0 && e < NSH) { s_pre[i] = LAT(LATF_S + e); sd_pre[i] = LAT(LATF_SD + e); }
+        if (MODE == 0 && e < NSH) { s_pre[i] = LAT(LATF_S + e); sd_pre[i] = LAT(LATF_SD + e); }
     }
-    // full torso: the free body (spawn pose at a reset: ultrasound.py:426-431)
+    // the free body (spawn pose at a reset: ultrasound.py:426-431)
     FullBody body;
     body.p = mk(M.torso[0], M.torso[1], M.torso[2]); body.q[0] = 1.f; body.q[1] = body.q[2] = body.q[3] = 0.f; body.v = mk(0.f, 0.f, 0.f); body.w = mk(0.f, 0.f, 0.f);
-    if (TORSO == 2 && MODE == 0) {
+    if (MODE == 0) {
         float bw[13];
 #pragma unroll
         for (int a = 0; a < 13; ++a) bw[a] = LAT(LATF_BODY + a);
@@ -1097,21 +1044,9 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
     if (!reset_only) {
         if (flags & LF_RANDOM_ACT) {
             uint32_t gid = (uint32_t)(C.env_offset + ei);
-            uint32_t rr[8];
-            if constexpr (G == 16) {
-                // the two counter blocks are evaluated side by side by the even and odd lanes of the group, then shared
-                // (not for G = 8, where the extra live values push the kernel into scratch)
-                u4 r = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 1u + (uint32_t)(gl & 1), C.key0, C.key1);
-                const float ra = __uint_as_float(r.a), rb = __uint_as_float(r.b), rc = __uint_as_float(r.c), rd = __uint_as_float(r.d);
-                rr[0] = __float_as_uint(group_bcast<G>(ra, 0)); rr[1] = __float_as_uint(group_bcast<G>(rb, 0));
-                rr[2] = __float_as_uint(group_bcast<G>(rc, 0)); rr[3] = __float_as_uint(group_bcast<G>(rd, 0));
-                rr[4] = __float_as_uint(group_bcast<G>(ra, 1)); rr[5] = __float_as_uint(group_bcast<G>(rb, 1));
-                rr[6] = __float_as_uint(group_bcast<G>(rc, 1)); rr[7] = 0u;
-            } else {
-                u4 r1 = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 1u, C.key0, C.key1);
-                u4 r2 = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 2u, C.key0, C.key1);
-                rr[0] = r1.a; rr[1] = r1.b; rr[2] = r1.c; rr[3] = r1.d; rr[4] = r2.a; rr[5] = r2.b; rr[6] = r2.c; rr[7] = r2.d;
-            }
+            u4 r1 = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 1u, C.key0, C.key1);
+            u4 r2 = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 2u, C.key0, C.key1);
+            uint32_t rr[8] = {r1.a, r1.b, r1.c, r1.d, r2.a, r2.b, r2.c, r2.d};
 #pragma unroll
             for (int a = 0; a < 7; ++a) {
                 float u = u01(rr[a]);
@@ -1184,7 +1119,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
 #pragma unroll
                 for (int i = 0; i < NJ; ++i) q[i] = INITQ[i];
                 for (int it = 0; it < C.ik_iters; ++it) {
-                    Kin K; fk<G == 1>(M, q, K);
+                    Kin K; fk(M, q, K);
                     f3 gx = mk(M.grot[0], M.grot[3], M.grot[6]), gy = mk(M.grot[1], M.grot[4], M.grot[7]), gz = mk(M.grot[2], M.grot[5], M.grot[8]);
                     f3 eo = (cross(K.sx, gx) + cross(K.sy, gy) + cross(K.sz, gz)) * 0.5f;
                     f3 ep = target - K.x;
@@ -1233,7 +1168,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
         float obs[OBS_DIM];
         float pos_err_norm = 0.f, ori_err = 0.f;
         if (active) {
-            Kin K; fk<G == 1>(M, q, K);
+            Kin K; fk(M, q, K);
             Dyn D; dynamics(M, K, qd, D);
 #pragma unroll
             for (int i = 0; i < NJ; ++i) D.M[PK(i, i)] += M.armature[i];          // rotor inertias (usim_config.armature_scale)
@@ -1387,152 +1322,85 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
             joint_friction(D.M, Lm, idm, qd, C.frictionloss, qs);
 
             float W[6] = {0, 0, 0, 0, 0, 0};          // site-space wrench of the contact forces
-            float full_chk = 0.f;                     // full torso: |free body| + sum |sliders| after the integration, for the numerical fault guard
-            if constexpr (TORSO == 2) {
-                // ---------------- full torso (usim_full.h): 270 sliders on the free body, probe and table contacts ----------------
-                float alpha[6], vs[6];
+            float full_chk = 0.f;                     // |free body| + sum |sliders| after the integration, for the numerical fault guard
+            // ---------------- torso (usim_full.h): 270 sliders on the free body, probe and table contacts ----------------
+            float alpha[6], vs[6];
 #pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    float s = 0.f, u = 0.f;
+            for (int a = 0; a < 6; ++a) {
+                float s = 0.f, u = 0.f;
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) { s = fmaf(J[a][j], qs[j], s); u = fmaf(J[a][j], qd[j], u); }
-                    alpha[a] = s; vs[a] = u;
-                }
-                float acc_e[FE], ab[6], lat_chk = 0.f;
-                int cel[MAXC], nc = 0, ovf = 0;
-                // (the contact solve starts from the forces of the previous physics step, kept in the environment's lattice block; a reset pass starts cold and leaves none)
-                float* const latp = &LAT(0);
-                full_forward(lds, gl, M, C, kst, kdmp, mu, s_pre, sd_pre, body, K.x, K.sx, K.sy, K.sz, Li, alpha, vs, W, acc_e, ab, nc, cel, ovf,
-                             (pass == 0) ? latp : nullptr, (pass == 0 && valid) ? latp : nullptr);
-                // The arm quantities the rest of the pass needs (kinematics, mass matrix and its factor, bias, site Jacobian: ~250 words) are formed AGAIN here, from joint
-                // state the compiler cannot recognise, instead of living through the contact solve: 2.5 k instructions against the solve's 700 k, and without them the
-                // kernel fits 256 registers with no scratch -- two environments per SIMD.  Same inputs, same instructions: the same bits.
+                for (int j = 0; j < NJ; ++j) { s = fmaf(J[a][j], qs[j], s); u = fmaf(J[a][j], qd[j], u); }
+                alpha[a] = s; vs[a] = u;
+            }
+            float acc_e[FE], ab[6], lat_chk = 0.f;
+            int cel[MAXC], nc = 0, ovf = 0;
+            // (the contact solve starts from the forces of the previous physics step, kept in the environment's lattice block; a reset pass starts cold and leaves none)
+            float* const latp = &LAT(0);
+            full_forward(lds, gl, M, C, kst, kdmp, mu, s_pre, sd_pre, body, K.x, K.sx, K.sy, K.sz, Li, alpha, vs, W, acc_e, ab, nc, cel, ovf,
+                         (pass == 0) ? latp : nullptr, (pass == 0 && valid) ? latp : nullptr);
+            // The arm quantities the rest of the pass needs (kinematics, mass matrix and its factor, bias, site Jacobian: ~250 words) are formed AGAIN here, from joint
+            // state the compiler cannot recognise, instead of living through the contact solve: 2.5 k instructions against the solve's 700 k, and without them the
+            // kernel fits 256 registers with no scratch -- two environments per SIMD.  Same inputs, same instructions: the same bits.
 #pragma unroll
-                for (int i = 0; i < NJ; ++i) asm volatile("" : "+v"(q[i]), "+v"(qd[i]));
-                fk<G == 1>(M, q, K);
-                dynamics(M, K, qd, D);
+            for (int i = 0; i < NJ; ++i) asm volatile("" : "+v"(q[i]), "+v"(qd[i]));
+            fk(M, q, K);
+            dynamics(M, K, qd, D);
 #pragma unroll
-                for (int i = 0; i < NJ; ++i) D.M[PK(i, i)] += M.armature[i];
+            for (int i = 0; i < NJ; ++i) D.M[PK(i, i)] += M.armature[i];
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    f3 jv = cross(K.z[j], K.x - K.o[j]);
-                    J[0][j] = jv.x; J[1][j] = jv.y; J[2][j] = jv.z; J[3][j] = K.z[j].x; J[4][j] = K.z[j].y; J[5][j] = K.z[j].z;
-                }
+            for (int j = 0; j < NJ; ++j) {
+                f3 jv = cross(K.z[j], K.x - K.o[j]);
+                J[0][j] = jv.x; J[1][j] = jv.y; J[2][j] = jv.z; J[3][j] = K.z[j].x; J[4][j] = K.z[j].y; J[5][j] = K.z[j].z;
+            }
 #pragma unroll
-                for (int k = 0; k < 28; ++k) Lm[k] = D.M[k];
-                chol_packed<NJ>(Lm, idm);
-                R.ncon = nc; R.overflow = ovf;
+            for (int k = 0; k < 28; ++k) Lm[k] = D.M[k];
+            chol_packed<NJ>(Lm, idm);
+            R.ncon = nc; R.overflow = ovf;
 #pragma unroll
-                for (int k = 0; k < MAXC; ++k) R.con_shell[k] = cel[k];
-                // semi-implicit Euler: sliders; free body (linear part in world axes, angular velocity in the body frame, quaternion by the exponential of dt w / 2)
+            for (int k = 0; k < MAXC; ++k) R.con_shell[k] = cel[k];
+            // semi-implicit Euler: sliders; free body (linear part in world axes, angular velocity in the body frame, quaternion by the exponential of dt w / 2)
 #pragma unroll
-                for (int i = 0; i < FE; ++i) {
-                    const int e = FE * gl + i;
-                    float sdn = 0.f, sn = 0.f;
-                    if (pass == 0) { sdn = fmaf(dt, acc_e[i], sd_pre[i]); sn = fmaf(dt, sdn, s_pre[i]); }
-                    if (valid && e < NSH && (pass == 0 || !refill)) { LAT(LATF_SD + e) = sdn; LAT(LATF_S + e) = sn; }
-                    if (e < NSH) lat_chk += fabsf(sn) + 1e-3f * fabsf(sdn);
-                }
-                if (pass == 0) {
-                    const float qw = body.q[0], qx = body.q[1], qy = body.q[2], qz = body.q[3];
-                    const f3 abl = mk(ab[0], ab[1], ab[2]);
-                    const f3 aw = mk((1.f - 2.f * (qy * qy + qz * qz)) * abl.x + 2.f * (qx * qy - qw * qz) * abl.y + 2.f * (qx * qz + qw * qy) * abl.z,
-                                     2.f * (qx * qy + qw * qz) * abl.x + (1.f - 2.f * (qx * qx + qz * qz)) * abl.y + 2.f * (qy * qz - qw * qx) * abl.z,
-                                     2.f * (qx * qz - qw * qy) * abl.x + 2.f * (qy * qz + qw * qx) * abl.y + (1.f - 2.f * (qx * qx + qy * qy)) * abl.z);
-                    body.v = madd(body.v, aw, dt); body.p = madd(body.p, body.v, dt);
-                    body.w = madd(body.w, mk(ab[3], ab[4], ab[5]), dt);
-                    const float wn = sqrt_(dot(body.w, body.w)), hh = 0.5f * dt * wn;
-                    float shh, chh; sincosf(hh, &shh, &chh);
-                    const float sh = (wn > 1e-12f) ? shh * rcp_(wn) : 0.5f * dt;
-                    const float dx = body.w.x * sh, dy = body.w.y * sh, dz2 = body.w.z * sh;
-                    const float n0 = qw * chh - qx * dx - qy * dy - qz * dz2, n1 = qw * dx + qx * chh + qy * dz2 - qz * dy;
-                    const float n2 = qw * dy - qx * dz2 + qy * chh + qz * dx, n3 = qw * dz2 + qx * dy - qy * dx + qz * chh;
-                    const float irn = rsq_(n0 * n0 + n1 * n1 + n2 * n2 + n3 * n3);
-                    body.q[0] = n0 * irn; body.q[1] = n1 * irn; body.q[2] = n2 * irn; body.q[3] = n3 * irn;
-                    // what the numerical fault guard below sees of the torso: the free body's 13 words and every slider (a non-finite word makes the sum non-finite; without
-                    // this a torso gone NaN fails every comparison of full_forward, its contacts vanish silently and the arm -- all the guard used to look at -- stays finite)
-                    full_chk = wave_sum(lat_chk) + fabsf(body.p.x) + fabsf(body.p.y) + fabsf(body.p.z) + fabsf(body.q[0]) + fabsf(body.q[1]) + fabsf(body.q[2]) + fabsf(body.q[3])
-                             + 1e-3f * (fabsf(body.v.x) + fabsf(body.v.y) + fabsf(body.v.z) + fabsf(body.w.x) + fabsf(body.w.y) + fabsf(body.w.z));
-                }
-                if (store && (pass == 0 || !refill)) {
-                    const float bw[13] = {body.p.x, body.p.y, body.p.z, body.q[0], body.q[1], body.q[2], body.q[3], body.v.x, body.v.y, body.v.z, body.w.x, body.w.y, body.w.z};
+            for (int i = 0; i < FE; ++i) {
+                const int e = FE * gl + i;
+                float sdn = 0.f, sn = 0.f;
+                if (pass == 0) { sdn = fmaf(dt, acc_e[i], sd_pre[i]); sn = fmaf(dt, sdn, s_pre[i]); }
+                if (valid && e < NSH && (pass == 0 || !refill)) { LAT(LATF_SD + e) = sdn; LAT(LATF_S + e) = sn; }
+                if (e < NSH) lat_chk += fabsf(sn) + 1e-3f * fabsf(sdn);
+            }
+            if (pass == 0) {
+                const float qw = body.q[0], qx = body.q[1], qy = body.q[2], qz = body.q[3];
+                const f3 abl = mk(ab[0], ab[1], ab[2]);
+                const f3 aw = mk((1.f - 2.f * (qy * qy + qz * qz)) * abl.x + 2.f * (qx * qy - qw * qz) * abl.y + 2.f * (qx * qz + qw * qy) * abl.z,
+                                 2.f * (qx * qy + qw * qz) * abl.x + (1.f - 2.f * (qx * qx + qz * qz)) * abl.y + 2.f * (qy * qz - qw * qx) * abl.z,
+                                 2.f * (qx * qz - qw * qy) * abl.x + 2.f * (qy * qz + qw * qx) * abl.y + (1.f - 2.f * (qx * qx + qy * qy)) * abl.z);
+                body.v = madd(body.v, aw, dt); body.p = madd(body.p, body.v, dt);
+                body.w = madd(body.w, mk(ab[3], ab[4], ab[5]), dt);
+                const float wn = sqrt_(dot(body.w, body.w)), hh = 0.5f * dt * wn;
+                float shh, chh; sincosf(hh, &shh, &chh);
+                const float sh = (wn > 1e-12f) ? shh * rcp_(wn) : 0.5f * dt;
+                const float dx = body.w.x * sh, dy = body.w.y * sh, dz2 = body.w.z * sh;
+                const float n0 = qw * chh - qx * dx - qy * dy - qz * dz2, n1 = qw * dx + qx * chh + qy * dz2 - qz * dy;
+                const float n2 = qw * dy - qx * dz2 + qy * chh + qz * dx, n3 = qw * dz2 + qx * dy - qy * dx + qz * chh;
+                const float irn = rsq_(n0 * n0 + n1 * n1 + n2 * n2 + n3 * n3);
+                body.q[0] = n0 * irn; body.q[1] = n1 * irn; body.q[2] = n2 * irn; body.q[3] = n3 * irn;
+                // what the numerical fault guard below sees of the torso: the free body's 13 words and every slider (a non-finite word makes the sum non-finite; without
+                // this a torso gone NaN fails every comparison of full_forward, its contacts vanish silently and the arm -- all the guard used to look at -- stays finite)
+                full_chk = wave_sum(lat_chk) + fabsf(body.p.x) + fabsf(body.p.y) + fabsf(body.p.z) + fabsf(body.q[0]) + fabsf(body.q[1]) + fabsf(body.q[2]) + fabsf(body.q[3])
+                         + 1e-3f * (fabsf(body.v.x) + fabsf(body.v.y) + fabsf(body.v.z) + fabsf(body.w.x) + fabsf(body.w.y) + fabsf(body.w.z));
+            }
+            if (store && (pass == 0 || !refill)) {
+                const float bw[13] = {body.p.x, body.p.y, body.p.z, body.q[0], body.q[1], body.q[2], body.q[3], body.v.x, body.v.y, body.v.z, body.w.x, body.w.y, body.w.z};
 #pragma unroll
-                    for (int a = 0; a < 13; ++a) LAT(LATF_BODY + a) = bw[a];
-                }
-                if (pass == 1 && valid && !refill) {                         // a reset of the live state: the episode starts without a warm start
-                    for (int w = gl; w < LATF_WARM_WORDS; w += G) LAT(LATF_WTAB + w) = (w >= 4 * NSH && w < 4 * NSH + 8) ? __int_as_float(-1) : 0.f;
-                }
-            } else if (TORSO) {
-                const int* tb_shell = reinterpret_cast<const int*>(lds + TB_SHELL);
-                const int tsim = (t > 0) ? t - 1 : 0;
-                float dz, vz, az;
-                torso_motion(C, tsim, dz, vz, az);
-                TSTAMP(4);
-                int nc = lattice_front<G, NE, MODE == 0>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, pass == 0, s_pre, sd_pre, K.x, K.sy, K.sz, io.dbg);
-                TSTAMP(7);
-                if (nc > MAXC) { R.overflow = 1; nc = MAXC; }
-                R.ncon = nc;
-                group_sync();
-                int ncmax = 0;                                       // wave-uniform bound on the contact count
-#pragma unroll
-                for (int k = MAXC; k >= 1; --k) if (ncmax == 0 && __any(nc >= k)) ncmax = k;
-                float gf[MAXC];
-                int cel[MAXC];
-#pragma unroll
-                for (int k = 0; k < MAXC; ++k) { gf[k] = 0.f; cel[k] = (k < nc) ? __float_as_int(EB(GE_CG + k * CG_WORDS + 6)) : 0; }
-                if (ncmax > 0) {
-                    float alpha[6], vs[6];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) {
-                        float s = 0.f, u = 0.f;
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) { s = fmaf(J[a][j], qs[j], s); u = fmaf(J[a][j], qd[j], u); }
-                        alpha[a] = s; vs[a] = u;
-                    }
-                    TSTAMP(8);
-                    contact_solve<G, false>(lds, eb, gl, M, C, nc, ncmax, cel, Li, alpha, vs, mu, vz, ContactRows{}, W, gf, io.dbg);
-                }
-                TSTAMP(11);
-                // ---- element accelerations a = a~ + Linv[:, e_c] gf_c, semi-implicit Euler, write back ----
-                {
-                    float acc_e[NE];
-#pragma unroll
-                    for (int i = 0; i < NE; ++i) { const int e = gl + i * G; acc_e[i] = (pass == 0 && e < N_TOP) ? EB(GE_A + e) : 0.f; }
-                    if (pass == 0) {
-#pragma unroll
-                        for (int k = 0; k < MAXC; ++k) {     // contact outer (one wave-uniform test per slot), elements inner; slots beyond this
-                            if (k < ncmax) {                 // environment's count carry gf = 0 and element 0
-#pragma unroll
-                                for (int i = 0; i < NE; ++i) {
-                                    const int e = (gl + i * G < N_TOP) ? gl + i * G : N_TOP - 1;
-                                    acc_e[i] = fmaf(lds[TB_LINV + e * LROW + cel[k]], gf[k], acc_e[i]);
-                                }
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int i = 0; i < NE; ++i) {
-                        const int e = gl + i * G;
-                        if (e >= N_TOP) continue;
-                        float sdn = 0.f, sn = 0.f;
-                        if (pass == 0) {
-                            sdn = sd_pre[i] + dt * acc_e[i];
-                            sn = s_pre[i] + dt * sdn;
-                        }
-                        if (valid && (pass == 0 || !refill)) { LAT(LAT_SD + e) = sdn; LAT(LAT_S + e) = sn; }
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < MAXC; ++k) R.con_shell[k] = (k < nc) ? tb_shell[cel[k]] : -1;
-            } else {
-#pragma unroll
-                for (int k = 0; k < MAXC; ++k) R.con_shell[k] = -1;
+                for (int a = 0; a < 13; ++a) LAT(LATF_BODY + a) = bw[a];
+            }
+            if (pass == 1 && valid && !refill) {                         // a reset of the live state: the episode starts without a warm start
+                for (int w = gl; w < LATF_WARM_WORDS; w += G) LAT(LATF_WTAB + w) = (w >= 4 * NSH && w < 4 * NSH + 8) ? __int_as_float(-1) : 0.f;
             }
             TSTAMP(12);
             // ---------------- constrained arm acceleration: qacc = qs + M^-1 J^T W ----------------
 #pragma unroll
             for (int i = 0; i < NJ; ++i) qacc[i] = qs[i];
-            if (TORSO) {
+            {
                 float z[NJ];
 #pragma unroll
                 for (int i = 0; i < NJ; ++i) {
@@ -1661,10 +1529,10 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
                         L[40] = (float)(t - 1) * inv_h * 100.f;
                         L[41] = pos_rew; L[42] = ori_rew; L[43] = vel_rew; L[44] = force_rew; L[45] = dforce_rew;
                     }
-                    if (R.overflow) status |= (TORSO == 2) ? (R.overflow & 3) : 1;      // (full torso: bit 1 = more element-table contacts than the kernel keeps)
+                    if (R.overflow) status |= R.overflow & 3;                            // (bit 1: more element-table contacts than the kernel keeps)
                     {
                         // numerical fault guard: a non-finite or run-away state ends the episode and is flagged
-                        float chk = (TORSO == 2) ? full_chk : 0.f;
+                        float chk = full_chk;
 #pragma unroll
                         for (int i = 0; i < NJ; ++i) chk += fabsf(q[i]) + 1e-3f * fabsf(qd[i]);
                         if (!(chk < 1.0e3f)) { status |= 4; done = true; epret -= reward; reward = 0.f; if (!(epret == epret)) epret = 0.f; }
@@ -1699,13 +1567,13 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
                         BK(sl, BU0) = u0; BK(sl, BKST) = kst; BK(sl, BKDMP) = kdmp; BK(sl, BMU) = mu; BK(sl, BFZ) = fzbar;
 #pragma unroll
                         for (int a = 0; a < OBS_DIM; ++a) BK(sl, BOBS + a) = obs[a];
-                        BKI(sl, BSTATUS) = (TORSO == 2) ? (R.overflow & 3) : (R.overflow ? 1 : 0);
+                        BKI(sl, BSTATUS) = R.overflow & 3;
                     }
                 } else if (store && io.obs && (pass == 1 ? need : !need)) {
 #pragma unroll
                     for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = obs[a];
                 }
-                if (pass == 1 && R.overflow) status |= (TORSO == 2) ? (R.overflow & 3) : 1;
+                if (pass == 1 && R.overflow) status |= R.overflow & 3;
             }
         }
     } while (0);
@@ -1724,8 +1592,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
 #pragma unroll
             for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = BK(sl, BOBS + a);
         }
-        if (TORSO == 1 && valid) for (int e = gl; e < N_TOP; e += G) { LAT(LAT_S + e) = 0.f; LAT(LAT_SD + e) = 0.f; }
-        if (TORSO == 2 && valid) {
+        if (valid) {
             // (every word by the lane that wrote it in the step above)
             for (int i = 0; i < FE; ++i) { const int e = FE * gl + i; if (e < NSH) { LAT(LATF_S + e) = 0.f; LAT(LATF_SD + e) = 0.f; } }
             if (gl == 0) {
@@ -1765,7 +1632,6 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, (TORSO == 2) ? 2 : 1) void usim_s
 #undef ST
 #undef STI
 #undef LAT
-#undef EB
     if (refill) group_sync();                         // next item reuses the per-environment LDS block
     }   // item loop
     if (MODE == 1 && refill) {

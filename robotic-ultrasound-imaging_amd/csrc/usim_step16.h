@@ -1,7 +1,7 @@
 // usim_step16.h -- step kernel with the arm mathematics of an environment DISTRIBUTED over the 16 lanes of its group (one DPP row).
 //
-// The first step kernel (usim_kernels.hip) replicates the 7-DoF arm mathematics in all lanes of a group: at 4096 envs/GPU every SIMD holds
-// one wave, the kernel is bound by VALU issue slots, and 4.1 k of its 7 k instructions per wave-step are that replicated stream.  Here a lane
+// The first step kernel (round 1, since removed) replicated the 7-DoF arm mathematics in all lanes of a group: at 4096 envs/GPU every SIMD held
+// one wave, the kernel was bound by VALU issue slots, and 4.1 k of its 7 k instructions per wave-step were that replicated stream.  Here a lane
 // owns one link (joint space, lanes 0 .. nj-1) and / or one task-space row (lanes 0-2 position, 4-6 orientation); lane 7 owns the
 // end-effector site frame.  Lanes exchange data with DPP row operations only (row_newbcast, row_shr / row_shl, quad_perm) plus two 8 x 8
 // transposes through LDS:
@@ -467,13 +467,13 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         const int tsim = tphys;
         float dz, vz, az;
         torso_motion(C, tsim, dz, vz, az);
-        lattice_front<G, NE, true, 1>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, mk(0, 0, 0), mk(0, 0, 0), mk(0, 0, 0), dbg);
+        lattice_front<G, NE, 1>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, mk(0, 0, 0), mk(0, 0, 0), mk(0, 0, 0), dbg);
         // The matrix-core solve a~ = Linv rhs needs nothing from the arm side: it runs here, where this wave used to wait for the site pose (hand-off (1)
         // comes when the arm side has finished its kinematics and the broad phase), and leaves only the narrow phase for after the hand-off: one box,
         // 14.38 -> 13.65 us/step at 4096 envs, 20.8 -> 20.2 at 8192 (8-lane groups).  Splitting the product around the hand-off so that both sides reach
         // hand-offs (1) and (2) together (18 / 14 / 21 of the 25 k chunks before it, accumulators live across the barrier) is slower: 13.9 / 14.1 / 13.85,
         // and with 8-lane groups the accumulators of both column sets spill (44 us).
-        lattice_front<G, NE, true, 3, true>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, mk(0, 0, 0), mk(0, 0, 0), mk(0, 0, 0), dbg);
+        lattice_front<G, NE, 3, true>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, mk(0, 0, 0), mk(0, 0, 0), mk(0, 0, 0), dbg);
         RSTAMP(1);
         USIM_BAR();                                                 // (1) the arm side has published the site pose
         RSTAMP(2);
@@ -494,7 +494,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             group_sync();
         }
         const int na = (__float_as_int(mb[MB_POSE + 10]) * arm_share_num<G>() + ARM_SHARE_DEN - 1) / ARM_SHARE_DEN;
-        const int ncl = lattice_front<G, NE, true, 4, true>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, xs, sy, sz, dbg, mb + MB_Q, na, nq);
+        const int ncl = lattice_front<G, NE, 4, true>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, xs, sy, sz, dbg, mb + MB_Q, na, nq);
         // Without an arm-side share of the narrow phase the contact list is complete here: the slot rule, the contact elements and the arm-independent half
         // of every contact row (frame, lever arms, lattice coupling, regulariser) can be formed before hand-off (2), while the arm side still forms Lambda^-1.
         // One box, kernel us/step: 8-lane groups at 8192 envs 20.19 -> 19.97 (scratch 176 -> 112 bytes per lane); 16-lane groups at 4096 envs 13.67 -> 13.82
@@ -1021,7 +1021,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         const int tsim = tphys;
         float dz, vz, az;
         torso_motion(C, tsim, dz, vz, az);
-        int nc = lattice_front<G, NE, true>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, MODE == 0, s_pre, sd_pre, xs, sy, sz, dbg);
+        int nc = lattice_front<G, NE>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, MODE == 0, s_pre, sd_pre, xs, sy, sz, dbg);
         USIM_STAMP(dbg, 7);
         if (nc > MAXC) { overflow = 1; nc = MAXC; }
         ncon = nc;

@@ -30,10 +30,11 @@ def test_error_conventions_on_device(usim):
     cfg = usim.make_config()
     h = C.c_void_p()
     assert lib.usim_create(C.byref(cfg), 8, 99, C.byref(h)) == -2 and not h            # device index out of range
-    cfg.lanes_per_env = 5
-    assert lib.usim_create(C.byref(cfg), 8, 0, C.byref(h)) == -1                        # invalid mapping
-    if h:
-        lib.usim_destroy(h); h = C.c_void_p()
+    for lanes in (1, 5, 8):
+        cfg.lanes_per_env = lanes
+        assert lib.usim_create(C.byref(cfg), 8, 0, C.byref(h)) == -1, lanes             # invalid mapping
+        if h:
+            lib.usim_destroy(h); h = C.c_void_p()
     cfg.lanes_per_env = 0
     assert lib.usim_create(C.byref(cfg), 8, 0, C.byref(h)) == 0 and h
     assert lib.usim_num_envs(h) == 8 and lib.usim_action_dim(h) == 6 and lib.usim_num_elements(h) == 99

@@ -17,7 +17,6 @@ run "configs[4] 8192 randomised auto" --steps 1024 --warmup 256 --envs-per-gpu 8
 run "configs[4] after 1000 steps"      --steps 1024 --warmup 256 --envs-per-gpu 8192 --randomize --presteps 1024
 run "configs[4] 8192 randomised l32"  --steps 1024 --warmup 256 --envs-per-gpu 8192 --randomize --lanes-per-env 32
 run "configs[4] 8192 randomised l64"  --steps 1024 --warmup 256 --envs-per-gpu 8192 --randomize --lanes-per-env 64
-run "configs[4] 8192 randomised l8"   --steps 1024 --warmup 256 --envs-per-gpu 8192 --randomize --lanes-per-env 8
 run "soft 16384 auto"                 --steps 512 --warmup 256 --envs-per-gpu 16384
 run "soft 16384 l64"                  --steps 512 --warmup 256 --envs-per-gpu 16384 --lanes-per-env 64
 run "configs[2] soft 4096 l64"        --steps 2048 --warmup 256 --lanes-per-env 64

@@ -10,8 +10,7 @@ def bench(n=4096, steps=300, torso="soft", **kw):
     ms = env.time_steps(100, steps, blk)
     print(f"[{torso} {kw}] n={n} {ms / steps * 1e3:.1f} us/step  {n * steps / ms * 1e3:.3e} env-steps/s", flush=True)
     env.close()
-for lpe in (16, 8):
-    for it in (0, 1, 2, 5, 10):
-        bench(pgs_iters=it, lanes_per_env=lpe)
-bench(torso="rigid", lanes_per_env=16); bench(torso="rigid", lanes_per_env=1)
+for it in (0, 1, 2, 5, 10):
+    bench(pgs_iters=it, lanes_per_env=16)
+bench(torso="rigid", lanes_per_env=16)
 bench(n=256, lanes_per_env=16); bench(n=256, torso="rigid", lanes_per_env=16); bench(n=16, lanes_per_env=16)

@@ -9,7 +9,7 @@ def mean_kb(root, sub, counter, steps_per_launch):
         with open(f) as fh:
             for r in csv.DictReader(fh):
                 name = r["Kernel_Name"].replace(" ", "")
-                # step launches: the split kernel, or MODE 0 (template argument before the MULTI flag) of the 16-lane / round-1 kernel templates
+                # step launches: the split kernel, or MODE 0 (template argument before the MULTI flag) of the 16-lane / full-torso kernel templates
                 head = name.split(">(")[0]
                 is_step = "usim_step32_kernel" in name or (("usim_step16_kernel" in name) and (head.endswith(",0,true") or head.endswith(",0,false") or head.endswith(",0"))) \
                     or ("usim_step_kernel" in name and head.endswith(",0"))

@@ -301,11 +301,4 @@ DI float distance_quat_goal(const float* q, const float* ghat, float eps_g) {
     return 4.f * asinf(sqrt_(fminf(0.5f * h, 1.f)));
 }
 
-// closest point of the segment p1 + s d1 (s in [0,1]) to the point c
-DI f3 seg_point(f3 p1, f3 d1, f3 c) {
-    float s = clampf(dot(d1, c - p1) * rcp_(dot(d1, d1)), 0.f, 1.f);
-    return madd(p1, d1, s);
-}
-
-
 }  // namespace usim

@@ -1,6 +1,11 @@
-// usim_kernels.hip -- CDNA4 (gfx950) step/reset kernel of the batched Ultrasound simulator.
+// usim_kernels.hip -- CDNA4 (gfx950) device code of the batched Ultrasound simulator; the translation unit is usim_api.hip, which includes it.
 //
-// The step replaces, per environment:
+// This file holds
+//   - the lattice and contact phases of the soft torso (lattice_front, collide_*, contact_rows / contact_solve), which the 16-lane step kernels
+//     of usim_step16.h (rigid and soft torso, included at the end) call;
+//   - usim_step_kernel<2, 64, MODE>, the step / reset kernel of the full torso (physics in usim_full.h);
+//   - usim_bank_items_kernel (refill work list of the reset / set_state paths) and usim_random_actions_kernel (the synthetic actions).
+// Pieces of the env logic that the step kernels share are in usim_episode.h.  Every step kernel replaces, per environment:
 //   a1 robosuite MujocoEnv.step driver            a2 OSC_POSE controller (rl_config.yaml:33-51)
 //   a3 MuJoCo mj_step (forward dynamics + soft constraints + Euler)
 //   a4 Ultrasound.reward  ultrasound.py:230-269   a5 sensors ultrasound.py:363-401
@@ -11,8 +16,7 @@
 //
 // Mapping.  G lanes of a wave64 form the group of one environment.
 //   rigid / soft torso  G = 16 (the split kernel of the soft torso also G = 8): the kernels of usim_step16.h, which distribute the arm mathematics over
-//                the group.  This file holds the lattice and contact phases of the soft torso they share; the lanes of a group split the 99-element
-//                lattice, the collision tests and the contacts:
+//                the group; in the lattice and contact phases below the lanes of a group split the 99-element lattice, the collision tests and the contacts:
 //                  - the lattice inverse (99 x 100 fp32) and the element tables are workgroup-resident in LDS; per-environment
 //                    scratch is a 548-word LDS block (548 mod 64 = 36 puts the 16-byte windows of the 16 environments on
 //                    disjoint bank groups);
@@ -205,14 +209,6 @@ DI void collide_elem(const float* lds, float* recs, const bool valid, const int 
     nc += __popc(gm);
 }
 
-// round form: element i G + gl of this lane's environment (the single-wave kernels walk all rounds)
-template <int G>
-DI void collide_one(const float* lds, float* recs, const int i, const int gl, const int gbase, const DevModel& M, const DevCfg& C, const float se, const float dz,
-                    const f3 Kx, const f3 Ksx, const f3 Ksy, const f3 Ksz, int& nc) {
-    const int eraw = i * G + gl;
-    collide_elem<G>(lds, recs, eraw < N_TOP, eraw < N_TOP ? eraw : N_TOP - 1, gl, gbase, M, C, se, dz, Kx, Ksx, Ksy, Ksz, nc);
-}
-
 // Broad phase (split kernel).  The probe -- convex hull of two parallel capsules whose axes are probe_h apart -- lies inside the capsule of
 // radius probe_r + probe_h around its UPPER axis; an element's capsule lies inside the ball of radius ELEM_HL + ELEM_R around the midpoint of its
 // axis segment.  An element whose ball misses that capsule cannot touch the probe: 80 % of the 99 elements, for 20 instructions each instead
@@ -351,7 +347,7 @@ DI int lattice_front(float* lds, const int eb, const int gl, const int gbase, co
                     }
                     if constexpr (PART == 1) return 0;
                     LSTAMP(5);
-                                    // ---- collision: seven rounds of one element per lane (collide_one), scheduled between the pieces of the matrix-core
+                                    // ---- collision: seven rounds of one element per lane (collide_elem), scheduled between the pieces of the matrix-core
                     //      solve below -- or, in the split kernel (QM), this wave's share [q0, q1) of the broad phase's queue (collide_cull / collide_queue;
                     //      the arm wave, which has the site pose first, builds the queue and takes the other share; the two hit lists are merged
                     //      after hand-off (2)) ----
@@ -949,6 +945,7 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
 }
 
 #include "usim_full.h"
+#include "usim_episode.h"
 
 struct StepOut {               // results of one forward pass that the env logic needs
     float fc[3];               // net contact force on the probe (cfrc_ext[probe][3:6])
@@ -1002,8 +999,6 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
 #else
 #define TSTAMP(k) do { if (io.dbg && blockIdx.x == 0 && threadIdx.x == 0) { __builtin_amdgcn_s_waitcnt(0); io.dbg[k] = __builtin_readcyclecounter(); } } while (0)
 #endif
-#define BK(slot, f) st[(size_t)io.bank_row0 * npad + ((size_t)ei * BANK_DEPTH + (slot)) * BANK_STRIDE + (f)]
-#define BKI(slot, f) (reinterpret_cast<int*>(st))[(size_t)io.bank_row0 * npad + ((size_t)ei * BANK_DEPTH + (slot)) * BANK_STRIDE + (f)]
     TSTAMP(0);
     // ---------------- load state ----------------
     float sv[F_NSCALAR];                               // the 40 scalar words of the environment, in Field order: ten 16-byte loads
@@ -1015,10 +1010,14 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
     float q[NJ], qd[NJ], q0[NJ], dq[NJ];             // the joint words of the state hold dq = q - q0 (usim_device.h)
 #pragma unroll
     for (int i = 0; i < NJ; ++i) { dq[i] = sv[F_Q + i]; qd[i] = sv[F_QD + i]; q0[i] = sv[F_Q0 + i]; q[i] = q0[i] + dq[i]; }
-    f3 ts = mk(sv[F_TS], sv[F_TS + 1], sv[F_TS + 2]), te = mk(sv[F_TE], sv[F_TE + 1], sv[F_TE + 2]);
-    float u0 = sv[F_U0], vbar = sv[F_VBAR], fzbar = sv[F_FZBAR], fzprev = sv[F_FZPREV], dfz = sv[F_DFZ];
-    float kst = sv[F_KST], kdmp = sv[F_KDMP], mu = sv[F_MU], epret = sv[F_EPRET];
-    int t = __float_as_int(sv[F_T]), touched = __float_as_int(sv[F_TOUCH]), episode = __float_as_int(sv[F_EPISODE]), status = __float_as_int(sv[F_STATUS]);
+    Episode E;
+    f3 &ts = E.ts, &te = E.te;
+    float &u0 = E.u0, &vbar = E.vbar, &fzbar = E.fzbar, &fzprev = E.fzprev, &dfz = E.dfz, &kst = E.kst, &kdmp = E.kdmp, &mu = E.mu, &epret = E.epret;
+    int &t = E.t, &touched = E.touched, &episode = E.episode, &status = E.status;
+    ts = mk(sv[F_TS], sv[F_TS + 1], sv[F_TS + 2]); te = mk(sv[F_TE], sv[F_TE + 1], sv[F_TE + 2]);
+    u0 = sv[F_U0]; vbar = sv[F_VBAR]; fzbar = sv[F_FZBAR]; fzprev = sv[F_FZPREV]; dfz = sv[F_DFZ];
+    kst = sv[F_KST]; kdmp = sv[F_KDMP]; mu = sv[F_MU]; epret = sv[F_EPRET];
+    t = __float_as_int(sv[F_T]); touched = __float_as_int(sv[F_TOUCH]); episode = __float_as_int(sv[F_EPISODE]); status = __float_as_int(sv[F_STATUS]);
     // sliders of this lane (lane l owns elements 5 l .. 5 l + 4): prefetched now, consumed after the arm phase
     float s_pre[FE], sd_pre[FE];
 #pragma unroll
@@ -1049,18 +1048,12 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
             uint32_t rr[8] = {r1.a, r1.b, r1.c, r1.d, r2.a, r2.b, r2.c, r2.d};
 #pragma unroll
             for (int a = 0; a < 7; ++a) {
-                float u = u01(rr[a]);
-                bool sgn = (C.mode == 1) || (C.mode == 3) || (C.mode == 2 && a == 6);
-                act[a] = sgn ? 2.f * u - 1.f : u;
-                if (C.mode == 3) act[a] *= WRENCH_MAX;
+                act[a] = synthetic_action(C, rr[a], a);
                 if (io.act_out && store && a < C.adim) io.act_out[(size_t)ei * C.adim + a] = act[a];
             }
         } else {
 #pragma unroll
-            for (int a = 0; a < 7; ++a) if (a < C.adim) {
-                float v = io.act[(size_t)ei * C.adim + a];
-                act[a] = (v == v && fabsf(v) <= 3.0e38f) ? v : 0.f;      // a non-finite action component is treated as 0
-            }
+            for (int a = 0; a < 7; ++a) if (a < C.adim) act[a] = finite_or_zero(io.act[(size_t)ei * C.adim + a]);
         }
     }
 
@@ -1115,7 +1108,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
                 // ================= initial pose: damped-least-squares IK from init_qpos (ultrasound.py:812-844) ==========
                 float uu = clampf(u0, 0.f, 1.f);
                 f3 tp0 = ts + (te - ts) * uu;
-                f3 target = mk(tp0.x + noise.x + 0.0028f - M.base[0], tp0.y + noise.y + 0.0008f - M.base[1], tp0.z + noise.z + 0.0066f - M.base[2]);
+                f3 target = mk(tp0.x + noise.x + M.ikb[0] - M.base[0], tp0.y + noise.y + M.ikb[1] - M.base[1], tp0.z + noise.z + M.ikb[2] - M.base[2]);
 #pragma unroll
                 for (int i = 0; i < NJ; ++i) q[i] = INITQ[i];
                 for (int it = 0; it < C.ik_iters; ++it) {
@@ -1152,7 +1145,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
                 }
 #pragma unroll
                 for (int i = 0; i < NJ; ++i) { q0[i] = q[i]; qd[i] = 0.f; dq[i] = 0.f; }
-                t = 0; touched = 0; fzprev = 0.f; dfz = 0.f; vbar = 0.f; epret = 0.f; status = 0;
+                episode_begin(E, 0);
             }
         } else {
             t += 1;                                                  // MujocoEnv.step: timestep += 1
@@ -1502,7 +1495,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
                     float hvn = sqrt_(dot(hv, hv));
                     vbar += (hvn - vbar) * rcp_((float)t);
                     float fz = R.fc[2];
-                    dfz = (fz - fzprev) * rcp_(dt);
+                    dfz = (fz - fzprev) * rcp_(C.dt_ctrl);                 // ultrasound.py:542: self.control_timestep
                     fzprev = fz;
                     fzbar = 0.1f * fz + 0.9f * fzbar;
                     if (C.early_term) {                                // ultrasound.py:635-670
@@ -1587,7 +1580,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
         for (int i = 0; i < NJ; ++i) { q[i] = BK(sl, BQ0 + i); q0[i] = q[i]; qd[i] = 0.f; dq[i] = 0.f; }
         ts = mk(BK(sl, BTS), BK(sl, BTS + 1), BK(sl, BTS + 2)); te = mk(BK(sl, BTE), BK(sl, BTE + 1), BK(sl, BTE + 2));
         u0 = BK(sl, BU0); kst = BK(sl, BKST); kdmp = BK(sl, BKDMP); mu = BK(sl, BMU); fzbar = BK(sl, BFZ);
-        t = 0; touched = 0; fzprev = 0.f; dfz = 0.f; vbar = 0.f; epret = 0.f; status = BKI(sl, BSTATUS);
+        episode_begin(E, BKI(sl, BSTATUS));
         if (store && io.obs) {
 #pragma unroll
             for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = BK(sl, BOBS + a);
@@ -1602,9 +1595,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
             group_sync();                                                    // (the step above left its warm start through other lanes)
             for (int w = gl; w < LATF_WARM_WORDS; w += G) LAT(LATF_WTAB + w) = (w >= 4 * NSH && w < 4 * NSH + 8) ? __int_as_float(-1) : 0.f;
         }
-        // the slot just consumed is free again: order the episode that will occupy it (computed by the next bulk refill,
-        // which runs at least every BANK_DEPTH steps, i.e. before this environment can come round to the slot again)
-        if (store) { const int idx = atomicAdd(io.count, 1); io.items[idx] = make_int2(env, episode + BANK_DEPTH); }
+        if (store) order_refill(io, env, episode);
     }
 
     TSTAMP(15);
@@ -1634,17 +1625,8 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
 #undef LAT
     if (refill) group_sync();                         // next item reuses the per-environment LDS block
     }   // item loop
-    if (MODE == 1 && refill) {
-        // the last workgroup to finish empties the work list for the step kernels that follow on the stream
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            // (no device-scope fence: the list is read by the launches that FOLLOW on the stream, and a fence costs an L2 write-back per wave)
-            if (atomicAdd(io.count + 1, 1) == (int)gridDim.x - 1) { io.count[0] = 0; io.count[1] = 0; }
-        }
-    }
+    if (MODE == 1 && refill) work_list_close(io);
     TSTAMP(16);
-#undef BK
-#undef BKI
 #undef TSTAMP
 }
 
@@ -1667,12 +1649,7 @@ __global__ void usim_random_actions_kernel(const DevCfg C, int n, long long rste
     u4 r1 = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 1u, C.key0, C.key1);
     u4 r2 = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 2u, C.key0, C.key1);
     uint32_t rr[8] = {r1.a, r1.b, r1.c, r1.d, r2.a, r2.b, r2.c, r2.d};
-    for (int a = 0; a < C.adim; ++a) {
-        float u = u01(rr[a]);
-        bool sgn = (C.mode == 1) || (C.mode == 3) || (C.mode == 2 && a == 6);
-        float v = sgn ? 2.f * u - 1.f : u;
-        act[(size_t)i * C.adim + a] = (C.mode == 3) ? v * WRENCH_MAX : v;
-    }
+    for (int a = 0; a < C.adim; ++a) act[(size_t)i * C.adim + a] = synthetic_action(C, rr[a], a);
 }
 
 }  // namespace usim

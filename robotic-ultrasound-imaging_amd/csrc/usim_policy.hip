@@ -40,19 +40,6 @@ struct NormStats {                                       // policy.DeviceVecNorm
 DI double ld_agent(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 DI void st_agent(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-DI double block_sum(double v, double* red) {
-    // sum over the workgroup (any size that is a multiple of 64): wave reduction by DPP-free shuffles, then the wave sums through LDS
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += red[i];
-    return s;
-}
-
 // RunningMeanStd.update(obs).  PL_SB workgroups read their slice of the [n][19] batch once, coalesced (thread t takes words t, t + 128, ...: the
 // channel of a word is its index mod 19, and since 128 * 19 words form a block, slot j of a thread always holds channel (first + t + 128 j) mod 19 --
 // nineteen slots, nineteen different channels), and leave per-channel partial sums (sum x, sum x^2 in float64) in `part`.  The workgroup that

@@ -63,7 +63,6 @@ template <int G> DI float prefix_sum(float v) { v += rshr0<G, 1>(v); v += rshr0<
 template <int G> DI float suffix_sum(float v) { v += rshl0<G, 1>(v); v += rshl0<G, 2>(v); v += rshl0<G, 4>(v); return v; }     // inclusive, over lanes l .. l+7
 template <int G> DI f3 prefix_sum(f3 v) { return mk(prefix_sum<G>(v.x), prefix_sum<G>(v.y), prefix_sum<G>(v.z)); }
 template <int G> DI f3 suffix_sum(f3 v) { return mk(suffix_sum<G>(v.x), suffix_sum<G>(v.y), suffix_sum<G>(v.z)); }
-DI f3 symmul6(const float* I, f3 v) { return symmul(I, v); }
 
 constexpr int TASK_LANE[6] = {0, 1, 2, 4, 5, 6};      // lane that owns task-space row a: position rows in quad 0, orientation rows in quad 1
 
@@ -291,9 +290,7 @@ template <int TORSO, int ROLE, int G> constexpr int arm_lds_base();
 template <int NE>
 struct Carry {
     float dqj, qdj, q0j;
-    f3 ts, te;
-    float u0, vbar, fzbar, fzprev, dfz, kst, kdmp, mu, epret;
-    int t, touched, episode, status;
+    Episode ep;
     float s[NE], sd[NE];
 };
 
@@ -341,8 +338,6 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     const int ei = valid ? env : (refill ? 0 : n - 1);              // clamp so that every lane has something to read; stores are guarded
 #define LAT(w) st[(size_t)F_LAT * npad + (size_t)ei * LAT_ENV_WORDS + (w)]
 #define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
-#define BK(slot, f) st[(size_t)io.bank_row0 * npad + ((size_t)ei * BANK_DEPTH + (slot)) * BANK_STRIDE + (f)]
-#define BKI(slot, f) (reinterpret_cast<int*>(st))[(size_t)io.bank_row0 * npad + ((size_t)ei * BANK_DEPTH + (slot)) * BANK_STRIDE + (f)]
     // The mailbox block sits beyond the 64 KB an LDS instruction's immediate offset reaches.  Left to itself the compiler forms one address register per mailbox WORD
     // (block + constant, hoisted out of the step loop) and spills them around the contact solve: 74 registers, two scratch round trips per step in the resident
     // kernel.  The block's offset is therefore made opaque: one address register, the words at immediate offsets from it.
@@ -387,9 +382,10 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     // the joint words of the state hold dq = q - q0 (usim_device.h): the per-step increment dt qd is then rounded at the magnitude of the
     // excursion (~0.05 rad), not of the angle (~3 rad) -- the rounding of q would otherwise accumulate to micrometres at the probe over 200 steps
     float &dqj = cy.dqj, &qdj = cy.qdj, &q0j = cy.q0j;
-    f3 &ts = cy.ts, &te = cy.te;
-    float &u0 = cy.u0, &vbar = cy.vbar, &fzbar = cy.fzbar, &fzprev = cy.fzprev, &dfz = cy.dfz, &kst = cy.kst, &kdmp = cy.kdmp, &mu = cy.mu, &epret = cy.epret;
-    int &t = cy.t, &touched = cy.touched, &episode = cy.episode, &status = cy.status;
+    Episode& E = cy.ep;
+    f3 &ts = E.ts, &te = E.te;
+    float &u0 = E.u0, &vbar = E.vbar, &fzbar = E.fzbar, &fzprev = E.fzprev, &dfz = E.dfz, &kst = E.kst, &kdmp = E.kdmp, &mu = E.mu, &epret = E.epret;
+    int &t = E.t, &touched = E.touched, &episode = E.episode, &status = E.status;
     float (&s_pre)[NE] = cy.s, (&sd_pre)[NE] = cy.sd;
     if (fresh) {
         dqj = sp[F_Q + jl]; qdj = sp[F_QD + jl]; q0j = sp[F_Q0 + jl];
@@ -680,7 +676,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             group_sync();                                                // the scratch is rewritten by the next iteration / the forward pass
         }
         q0j = qj; qdj = 0.f; dqj = 0.f;
-        t = 0; touched = 0; fzprev = 0.f; dfz = 0.f; vbar = 0.f; epret = 0.f; status = 0;
+        episode_begin(E, 0);
     }
 
     // =================================================================================================================
@@ -734,6 +730,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         uint32_t rr[7];
         rr[0] = __float_as_uint(rbc<G, 0>(ra)); rr[1] = __float_as_uint(rbc<G, 0>(rb)); rr[2] = __float_as_uint(rbc<G, 0>(rc)); rr[3] = __float_as_uint(rbc<G, 0>(rd));
         rr[4] = __float_as_uint(rbc<G, 1>(ra)); rr[5] = __float_as_uint(rbc<G, 1>(rb)); rr[6] = __float_as_uint(rbc<G, 1>(rc));
+        // (the decoding of synthetic_action, usim_episode.h, written out: called here it changes the schedule of 7 of the 14 16-lane kernels)
 #pragma unroll
         for (int a = 0; a < 7; ++a) {
             const float u = u01(rr[a]);
@@ -747,10 +744,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         }
     } else {
 #pragma unroll
-        for (int a = 0; a < 7; ++a) if (a < C.adim) {
-            const float v = io.act[(size_t)ei * C.adim + a];
-            act[a] = (v == v && fabsf(v) <= 3.0e38f) ? v : 0.f;          // a non-finite action component is treated as 0
-        }
+        for (int a = 0; a < 7; ++a) if (a < C.adim) act[a] = finite_or_zero(io.act[(size_t)ei * C.adim + a]);
     }
     }
     }
@@ -1222,7 +1216,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         qj = jlane ? BK(sl, BQ0 + jl) : 0.f; q0j = qj; qdj = 0.f; dqj = 0.f;
         ts = mk(BK(sl, BTS), BK(sl, BTS + 1), BK(sl, BTS + 2)); te = mk(BK(sl, BTE), BK(sl, BTE + 1), BK(sl, BTE + 2));
         u0 = BK(sl, BU0); kst = BK(sl, BKST); kdmp = BK(sl, BKDMP); mu = BK(sl, BMU); fzbar = BK(sl, BFZ);
-        t = 0; touched = 0; fzprev = 0.f; dfz = 0.f; vbar = 0.f; epret = 0.f; status = BKI(sl, BSTATUS);
+        episode_begin(E, BKI(sl, BSTATUS));
         if (store && io.obs) {
 #pragma unroll
             for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = BK(sl, BOBS + a);
@@ -1237,7 +1231,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
                 if (ROLE == 1 && gl + i * G < N_TOP) EB(GE_S + gl + i * G) = 0.f;
             }
         }
-        if (store) { const int idx = atomicAdd(io.count, 1); io.items[idx] = make_int2(env, episode + BANK_DEPTH); }
+        if (store) order_refill(io, env, episode);
     }
     if constexpr (RES && ROLE == 1) {
         // (the wrench mailbox is free between hand-off (4) and the lattice side's next contact solve)
@@ -1265,22 +1259,13 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     }
     if (refill) group_sync();                                            // the next item reuses the per-environment LDS block
     }   // item loop
-    if (MODE == 1 && refill) {
-        // the last workgroup to finish empties the work list for the step kernels that follow on the stream
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            // (no device-scope fence: the list is read by the launches that FOLLOW on the stream, and a fence costs an L2 write-back per wave)
-            if (atomicAdd(io.count + 1, 1) == (int)gridDim.x - 1) { io.count[0] = 0; io.count[1] = 0; }
-        }
-    }
+    if (MODE == 1 && refill) work_list_close(io);
     USIM_STAMP(dbg, 16);
     if constexpr (ROLE == 1) RSTAMP(9);
 #undef RSTAMP
 #undef XSTAMP
 #undef LAT
 #undef EB
-#undef BK
-#undef BKI
 }
 
 // One launch = io.nsub consecutive steps (usim_rollout_random: the actions are drawn in-kernel, so step k + 1 needs nothing from the host).

@@ -80,12 +80,14 @@ typedef struct usim_config {
                                                 * previous physics step (94 % of the environments follow a converged solve's decisions at 24) */
     int32_t ik_iters;                          /* reset inverse-kinematics iterations */
     int32_t env_offset;                        /* global index of env 0 of this handle (multi-GPU shard) */
-    int32_t lanes_per_env;                     /* kernel mapping: 0 automatic; 16 lanes per environment (arm mathematics distributed over the group); 64 (soft torso: the split
-                                                * kernel with 8-lane groups, 32 environments per workgroup; automatic beyond 4096 envs); 32 (soft torso: the
-                                                * same, arm side and lattice / contact side in two waves that share a SIMD; the automatic choice for the soft torso).
-                                                * Rigid torso: 0 or 16; anything else is USIM_ERR_INVALID */
+    int32_t lanes_per_env;                     /* kernel mapping: 0 automatic; 16 lanes per environment (arm mathematics distributed over the group); 32 (soft torso: the split
+                                                * kernel, arm side and lattice / contact side in two waves that share a SIMD; automatic up to 4096 envs); 64 (soft torso: the
+                                                * same with 8-lane groups, 32 environments per workgroup; automatic beyond 4096 envs).  Rigid torso: 0 or 16; soft torso: 0, 16,
+                                                * 32 or 64; full torso: 0, 16, 32 or 64, ignored (one wave per environment); anything else is USIM_ERR_INVALID.  The table of
+                                                * mappings and of the kernels they run: resolve_mapping in csrc/usim_api.hip */
     int32_t torso_shape;                       /* use_box_torso (rl_config.yaml:57): 0 box (soft_box.xml), 1 cylinder (soft_human_torso.xml) */
-    int32_t waves_per_simd;                    /* 16-lane step kernel: register budget for 1 or 2 waves per SIMD; 0 auto (1 up to 4096 envs, 2 beyond) */
+    int32_t waves_per_simd;                    /* soft torso, 16-lane step kernel: register budget for 1 or 2 waves per SIMD; 0 auto (1 up to 4096 envs, 2 beyond).  Nonzero with
+                                                * lanes_per_env 0: lanes_per_env 16.  Rigid and full torso: 0, 1 or 2, ignored */
     int32_t robot;                             /* USIM_ROBOT_*: robots of ultrasound.py:137 */
     uint64_t seed;                             /* rl_config.yaml:1 */
     double control_dt;                         /* 1 / control_freq (rl_config.yaml:26) */
@@ -157,8 +159,8 @@ int usim_default_config(usim_config* c);
 int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** out);
 void usim_destroy(usim_handle* h);
 
-/* Switch the kernel mapping of a live soft-torso handle between lanes_per_env 32 (split kernel) and 16 (waves_per_simd 0 / 1 / 2 as in
- * usim_config).  The mappings compute the same bits, so a rollout may change between them at any step -- e.g. the two-waves-per-SIMD
+/* Switch the kernel mapping of a live soft-torso handle between lanes_per_env 32 or 64 (split kernel) and 16 (waves_per_simd 0 / 1 / 2 as in
+ * usim_config); lanes_per_env 0 and rigid or full-torso handles are USIM_ERR_INVALID.  The mappings compute the same bits, so a rollout may change between them at any step -- e.g. the two-waves-per-SIMD
  * 16-lane build while a collective's workgroups are resident, the split kernel otherwise (bench.py, N > 1).  Takes effect with the next
  * call that enqueues work. */
 int usim_set_mapping(usim_handle* h, int lanes_per_env, int waves_per_simd);

@@ -21,9 +21,55 @@
 
 using namespace usim;
 
+// Kernel mapping of a handle: the kernels of its step launches (MODE 0) and of its reset / refill launches (MODE 1);
+// M = io.nsub > 1 || C.substeps > 1 (several physics steps per launch: every mapping but FULL).
+//   mapping     handle                                                step launch                      reset / refill launch
+//   FULL        full torso (lanes_per_env 0, 16, 32 or 64: ignored)   usim_step_kernel<2, 64, 0>       usim_step_kernel<2, 64, 1>
+//   RIGID16     rigid torso, lanes 0 or 16 (waves_per_simd ignored)   usim_step16_kernel<0, 2, 0, M>   usim_step16_kernel<0, 2, 1, false>
+//   SOFT16_W1   soft torso, lanes 16, 1 wave per SIMD                 usim_step16_kernel<1, 1, 0, M>   usim_step16_kernel<1, 2, 1, false> (not register-critical)
+//   SOFT16_W2   soft torso, lanes 16, 2 waves per SIMD                usim_step16_kernel<1, 2, 0, M>   same
+//   SPLIT16     soft torso, lanes 32 (split kernel, 16-lane groups)   usim_step32_kernel<M, 16>        same
+//   SPLIT8      soft torso, lanes 64 (split kernel, 8-lane groups)    usim_step32_kernel<M, 8>         same
+// Soft torso, lanes 0: waves_per_simd 0 the split kernel -- up to 4096 envs/GPU lanes 32 (two waves per quad of environments, 16 environments per workgroup
+// = one workgroup per CU), beyond lanes 64 (two environments per DPP row, 32 per workgroup: 8192 envs still one workgroup per CU, 23.8 vs 29.3 us/step;
+// profiles/r03/bench_matrix.txt) --, a nonzero waves_per_simd (a register budget) lanes 16.  Waves per SIMD: the value given, else 1 up to 4096 envs, 2 beyond.
+// Refused: waves_per_simd outside 0 .. 2, any other lanes_per_env; usim_set_mapping also refuses lanes 0 and rigid / full-torso handles.
+enum class Mapping : int { FULL, RIGID16, SOFT16_W1, SOFT16_W2, SPLIT16, SPLIT8 };
+static bool resolve_mapping(int torso, int lanes_per_env, int waves_per_simd, int n_envs, Mapping* m) {
+    if (waves_per_simd < 0 || waves_per_simd > 2) return false;
+    if (torso == USIM_TORSO_NONE) { *m = Mapping::RIGID16; return lanes_per_env == 0 || lanes_per_env == 16; }
+    if (lanes_per_env != 0 && lanes_per_env != 16 && lanes_per_env != 32 && lanes_per_env != 64) return false;
+    const int lanes = lanes_per_env ? lanes_per_env : (waves_per_simd ? 16 : (n_envs <= 4096 ? 32 : 64));
+    const int waves = waves_per_simd ? waves_per_simd : (n_envs <= 4096 ? 1 : 2);
+    *m = torso == USIM_TORSO_FULL ? Mapping::FULL : lanes == 32 ? Mapping::SPLIT16 : lanes == 64 ? Mapping::SPLIT8 : (waves == 1 ? Mapping::SOFT16_W1 : Mapping::SOFT16_W2);
+    return true;
+}
+static bool soft_torso(Mapping m) { return m != Mapping::FULL && m != Mapping::RIGID16; }
+static bool multi_step(Mapping m) { return m != Mapping::FULL; }           // several control steps per launch (usim_rollout_random)
+
+// one kernel of the table with its launch geometry (environments and threads per workgroup, dynamic LDS words; the 16-lane kernels: + the arm table behind
+// everything else); model and configuration by value, or through pointers for the split kernels
+struct Kernel { void (*step)(const DevModel, const DevCfg, float*, int, int, const DevIO, int, long long); void (*split)(const DevModel*, const DevCfg*, float*, int, int, const DevIO, int, long long);
+                int epb, nt, lds_words; };
+static Kernel kernel_of(Mapping m, int mode, bool multi) {
+    if (mode != 0 && soft_torso(m)) m = Mapping::SOFT16_W2;
+    const bool r = mode != 0, mu = !r && multi;
+    constexpr int L16 = arm_lds_base<1, 0, 16>() + ARM_LDS_WORDS;
+    switch (m) {
+        case Mapping::FULL: return {r ? usim_step_kernel<2, 64, 1> : usim_step_kernel<2, 64, 0>, nullptr, GroupGeom<64>::EPB, GroupGeom<64>::NT, GroupGeom<64>::LDS_WORDS};
+        case Mapping::RIGID16: return {r ? usim_step16_kernel<0, 2, 1, false> : mu ? usim_step16_kernel<0, 2, 0, true> : usim_step16_kernel<0, 2, 0, false>, nullptr, 16, 256, arm_lds_base<0, 0, 16>() + ARM_LDS_WORDS};
+        case Mapping::SOFT16_W1: return {mu ? usim_step16_kernel<1, 1, 0, true> : usim_step16_kernel<1, 1, 0, false>, nullptr, 16, 256, L16};
+        case Mapping::SOFT16_W2: return {r ? usim_step16_kernel<1, 2, 1, false> : mu ? usim_step16_kernel<1, 2, 0, true> : usim_step16_kernel<1, 2, 0, false>, nullptr, 16, 256, L16};
+        case Mapping::SPLIT16: return {nullptr, mu ? usim_step32_kernel<true, 16> : usim_step32_kernel<false, 16>, 4 * wpr<16>(), 128 * wpr<16>(), arm_lds_base<1, 1, 16>() + ARM_LDS_WORDS};
+        case Mapping::SPLIT8: return {nullptr, mu ? usim_step32_kernel<true, 8> : usim_step32_kernel<false, 8>, 8 * wpr<8>(), 128 * wpr<8>(), arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS};
+    }
+    return {};
+}
+
 struct usim_handle {
     usim_config cfg;
-    int n = 0, npad = 0, device = 0, adim = 6, n_el = 0, nfields = 0, lpe = 1, occ = 1;
+    Mapping map = Mapping::RIGID16;   // resolved by usim_create (resolve_mapping)
+    int n = 0, npad = 0, device = 0, adim = 6, n_el = 0, nfields = 0;
     DevModel M;
     DevCfg C;
     float* state = nullptr;
@@ -44,7 +90,6 @@ struct usim_handle {
     long long steps_since_refill = 0;
     int steps_per_launch = 256;      // usim_rollout_random: consecutive steps per launch of the 16-lane kernels (USIM_STEPS_PER_LAUNCH overrides, 1 .. MAX_STEPS_PER_LAUNCH)
     int bank_row0 = 0;
-    size_t lds_bytes = 0, lds16_bytes = 0, lds32_bytes = 0, lds64_bytes = 0;
     std::string hip_err;
 };
 
@@ -84,6 +129,41 @@ void pack_sym(const double I[3][3], float* o) { o[0] = (float)I[0][0]; o[1] = (f
 bool on_shell(int a, int b, int c) {
     if (a < 0 || a >= 9 || b < 0 || b >= 4 || c < 0 || c >= 11) return false;
     return a == 0 || a == 8 || b == 0 || b == 3 || c == 0 || c == 10;
+}
+
+// soft equality constraints of the lattice (composite solrefsmooth, d_max 0.95): weight of the pin to the rest position and of a tendon to a neighbour
+const double kDMax = 0.95, kWFix = kDMax / (1 - kDMax), kWTen = 0.5 * kDMax / (1 - kDMax);
+double lattice_diag(int nn) { return 1.0 + kWFix + kWTen * nn; }      // diagonal of the lattice Laplacian: an element with nn tendons
+
+// one element of the 9 x 4 x 11 torso shell (soft_box.xml:9): lattice cell, world-axes position and slide axis (float, as uploaded), the shell ids
+// of its 6-neighbourhood (x-, x+, y-, y+, z-, z+; -1 off the shell) and their number
+struct ShellElement { int a, b, c; float pos[3], axis[3]; int nbr[6], nn; };
+
+// the 270 shell elements in creation order (ix outer, iy, iz inner: the index is the shell id)
+std::vector<ShellElement> torso_shell(int shape) {
+    int id[9][4][11], n = 0;
+    for (int a = 0; a < 9; ++a) for (int b = 0; b < 4; ++b) for (int c = 0; c < 11; ++c) id[a][b][c] = on_shell(a, b, c) ? n++ : -1;
+    std::vector<ShellElement> sh;
+    for (int a = 0; a < 9; ++a) for (int b = 0; b < 4; ++b) for (int c = 0; c < 11; ++c) {
+        if (id[a][b][c] < 0) continue;
+        ShellElement el{a, b, c, {}, {}, {}, 0};
+        double loc[3] = {(a - 4) * 0.035, (b - 1.5) * 0.035, (c - 5) * 0.035};
+        // composite type "cylinder" (soft_human_torso.xml:9): direction in the local x-y cross-section projected on the unit circle, max-norm radius kept ->
+        // the box section becomes an ellipse 0.14 x 0.0525
+        const double xn = loc[0] / 0.14, yn = loc[1] / 0.0525, l0 = std::fmax(std::fabs(xn), std::fabs(yn)), nn = std::sqrt(xn * xn + yn * yn);
+        if (shape == 1 && nn > 0) { loc[0] = 0.14 * l0 * xn / nn; loc[1] = 0.0525 * l0 * yn / nn; }
+        const double len = std::sqrt(loc[0] * loc[0] + loc[1] * loc[1] + loc[2] * loc[2]);
+        const double w[3] = {-loc[2], -loc[0], loc[1]};                  // parent quat (0.5, 0.5, -0.5, -0.5): world x = -local z, y = -local x, z = local y
+        for (int k = 0; k < 3; ++k) { el.pos[k] = (float)w[k]; el.axis[k] = (float)(w[k] / len); }
+        const int d3[6][3] = {{-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
+        for (int d = 0; d < 6; ++d) {
+            const int a2 = a + d3[d][0], b2 = b + d3[d][1], c2 = c + d3[d][2];
+            el.nbr[d] = on_shell(a2, b2, c2) ? id[a2][b2][c2] : -1;
+            el.nn += el.nbr[d] >= 0;
+        }
+        sh.push_back(el);
+    }
+    return sh;
 }
 
 // dense symmetric positive definite inverse by Gauss-Jordan in double precision
@@ -145,45 +225,34 @@ static void build_arm_table(const usim_host::Chain& c, float* tb, const double a
 // Full torso (usim_full.h): all 270 shell elements in creation order (ix outer, iy, iz inner: the shell id), their 6-neighbourhood restricted to the shell, and the
 // constants of the torso's Hessian H = [M I, 0, m N; 0, I_b, 0; m N', 0, m L] in float64: L^-1, P = L^-1 N', S^-1 = (M I - m N P)^-1, I_b^-1.
 static int build_full_tables(usim_handle* h, int shape) {
-    const double dmax = 0.95, wfix = dmax / (1 - dmax), wten = 0.5 * dmax / (1 - dmax), m = 0.01;
+    const double m = 0.01;
     std::vector<float> tb(FT_WORDS, 0.f);
     int* tbi = reinterpret_cast<int*>(tb.data());
-    int id[9][4][11], n = 0;
-    for (int a = 0; a < 9; ++a) for (int b = 0; b < 4; ++b) for (int c = 0; c < 11; ++c) id[a][b][c] = on_shell(a, b, c) ? n++ : -1;
-    if (n != NSH) return USIM_ERR_INVALID;
+    const std::vector<ShellElement> sh = torso_shell(shape);
+    if ((int)sh.size() != NSH) return USIM_ERR_INVALID;
     std::vector<double> ax((size_t)NSH * 3), L((size_t)NSH * NSH, 0.0);
     for (int e = 0; e < FNE; ++e) { tb[FT_DIAG + e] = 1.f; for (int d = 0; d < 4; ++d) tbi[FT_NBR + 4 * e + d] = FNE - 1; }
     double mt = m, Ib[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};                 // 270 elements + the composite's centre geom, 0.01 kg each
-    for (int a = 0; a < 9; ++a) for (int b = 0; b < 4; ++b) for (int c = 0; c < 11; ++c) {
-        const int e = id[a][b][c];
-        if (e < 0) continue;
-        double loc[3] = {(a - 4) * 0.035, (b - 1.5) * 0.035, (c - 5) * 0.035};
-        if (shape == 1) {
-            const double xn = loc[0] / 0.14, yn = loc[1] / 0.0525, l0 = std::fmax(std::fabs(xn), std::fabs(yn)), nn = std::sqrt(xn * xn + yn * yn);
-            if (nn > 0) { loc[0] = 0.14 * l0 * xn / nn; loc[1] = 0.0525 * l0 * yn / nn; }
-        }
-        const double len = std::sqrt(loc[0] * loc[0] + loc[1] * loc[1] + loc[2] * loc[2]);
-        const double w[3] = {-loc[2], -loc[0], loc[1]};                  // parent quat (0.5, 0.5, -0.5, -0.5): world x = -local z, y = -local x, z = local y
+    for (int e = 0; e < NSH; ++e) {
+        const ShellElement& el = sh[e];
         double cpos[3];
         for (int k = 0; k < 3; ++k) {
-            tb[FT_POS + 3 * e + k] = (float)w[k]; tb[FT_AXIS + 3 * e + k] = (float)(w[k] / len);
-            ax[(size_t)e * 3 + k] = (double)tb[FT_AXIS + 3 * e + k];
-            cpos[k] = (double)tb[FT_POS + 3 * e + k] - (0.0075 + 0.025) * ax[(size_t)e * 3 + k];          // capsule centre
+            tb[FT_POS + 3 * e + k] = el.pos[k]; tb[FT_AXIS + 3 * e + k] = el.axis[k];
+            ax[(size_t)e * 3 + k] = (double)el.axis[k];
+            cpos[k] = (double)el.pos[k] - (0.0075 + 0.025) * ax[(size_t)e * 3 + k];          // capsule centre
         }
         mt += m;
         const double dd = cpos[0] * cpos[0] + cpos[1] * cpos[1] + cpos[2] * cpos[2];
         for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Ib[3 * i + j] += m * ((i == j ? dd : 0.0) - cpos[i] * cpos[j]);
         int nn = 0;
-        const int d3[6][3] = {{-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
         for (int d = 0; d < 6; ++d) {
-            const int a2 = a + d3[d][0], b2 = b + d3[d][1], c2 = c + d3[d][2];
-            if (a2 < 0 || a2 > 8 || b2 < 0 || b2 > 3 || c2 < 0 || c2 > 10 || id[a2][b2][c2] < 0) continue;
+            if (el.nbr[d] < 0) continue;
             if (nn >= 4) return USIM_ERR_INVALID;
-            tbi[FT_NBR + 4 * e + nn++] = id[a2][b2][c2];
-            L[(size_t)e * NSH + id[a2][b2][c2]] = -wten;
+            tbi[FT_NBR + 4 * e + nn++] = el.nbr[d];
+            L[(size_t)e * NSH + el.nbr[d]] = -kWTen;
         }
-        L[(size_t)e * NSH + e] = 1.0 + wfix + wten * nn;
-        tb[FT_DIAG + e] = (float)(1.0 + wfix + wten * nn);
+        L[(size_t)e * NSH + e] = lattice_diag(nn);
+        tb[FT_DIAG + e] = (float)lattice_diag(nn);
     }
     const std::vector<double> Li = invert(L, NSH);
     std::vector<double> P((size_t)NSH * 3, 0.0);
@@ -233,9 +302,8 @@ static int build_model(usim_handle* h) {
         M.ghat[0] = (float)w; M.ghat[1] = (float)x; M.ghat[2] = (float)y; M.ghat[3] = (float)z;
         M.geps = (float)(1.0 - nn);
     }
-    const double dmax = 0.95;
-    M.wfix = (float)(dmax / (1 - dmax));
-    M.wten = (float)(0.5 * dmax / (1 - dmax));
+    M.wfix = (float)kWFix;
+    M.wten = (float)kWTen;
 
     // one table block per handle: [lattice tables (soft torso) | arm table], laid out as the kernels read it
     std::vector<float> tb(TB_TOTAL, 0.f);
@@ -247,88 +315,44 @@ static int build_model(usim_handle* h) {
     h->n_el = (h->cfg.torso == USIM_TORSO_TOP) ? N_TOP : (h->cfg.torso == USIM_TORSO_FULL ? NSH : 0);
     if (h->n_el == 0) return upload_tables(h, tb);
     if (h->cfg.torso == USIM_TORSO_FULL) return build_full_tables(h, shape);
-    std::vector<float> elpos(N_TOP * 3), elaxis(N_TOP * 3);
-    std::vector<int> nbr(N_TOP * 4, -2), shell(N_TOP);
-    int sid = 0, top_index[9][11];
-    for (int a = 0; a < 9; ++a) for (int b = 0; b < 4; ++b) for (int c = 0; c < 11; ++c) {
-        if (!on_shell(a, b, c)) continue;
-        if (b == 3) { top_index[a][c] = a * 11 + c; shell[a * 11 + c] = sid; }
-        ++sid;
-    }
+    // top face (iy = 3): element e = 11 ix + iz; its side-face neighbour below the rim, if any, is pinned (a tendon, no lattice unknown)
     std::vector<double> L((size_t)N_TOP * N_TOP, 0.0);
-    for (int a = 0; a < 9; ++a) for (int c = 0; c < 11; ++c) {
-        const int e = top_index[a][c];
-        double loc[3] = {(a - 4) * 0.035, 1.5 * 0.035, (c - 5) * 0.035};
-        if (shape == 1) {
-            // composite type "cylinder" (soft_human_torso.xml:9): direction in the local x-y cross-section projected on the unit
-            // circle, max-norm radius kept -> the top row of the box becomes the upper arc of an ellipse 0.14 x 0.0525
-            const double xn = loc[0] / 0.14, yn = loc[1] / 0.0525, l0 = std::fmax(std::fabs(xn), std::fabs(yn)), nn = std::sqrt(xn * xn + yn * yn);
-            loc[0] = 0.14 * l0 * xn / nn; loc[1] = 0.0525 * l0 * yn / nn;
-        }
-        const double len = std::sqrt(loc[0] * loc[0] + loc[1] * loc[1] + loc[2] * loc[2]);
-        // parent quat (0.5, 0.5, -0.5, -0.5): world x = -local z, world y = -local x, world z = local y
-        const double w[3] = {-loc[2], -loc[0], loc[1]};
-        for (int k = 0; k < 3; ++k) { elpos[e * 3 + k] = (float)w[k]; elaxis[e * 3 + k] = (float)(w[k] / len); }
-        int nn = 0;
-        const int da[4] = {-1, 1, 0, 0}, dc[4] = {0, 0, -1, 1};
-        for (int d = 0; d < 4; ++d) {
-            int a2 = a + da[d], c2 = c + dc[d];
-            if (a2 >= 0 && a2 < 9 && c2 >= 0 && c2 < 11) nbr[e * 4 + nn++] = top_index[a2][c2];
-        }
-        if (on_shell(a, 2, c)) nbr[e * 4 + nn++] = -1;     // side-face neighbour below the rim: pinned
-        L[(size_t)e * N_TOP + e] = 1.0 + dmax / (1 - dmax) + 0.5 * dmax / (1 - dmax) * nn;
-        for (int d = 0; d < nn; ++d) if (nbr[e * 4 + d] >= 0) L[(size_t)e * N_TOP + nbr[e * 4 + d]] = -0.5 * dmax / (1 - dmax);
+    const std::vector<ShellElement> sh = torso_shell(shape);
+    for (int id = 0; id < NSH; ++id) {
+        const ShellElement& el = sh[id];
+        if (el.b != 3) continue;
+        const int e = el.a * 11 + el.c;
+        std::memcpy(&tb[TB_SHELL + e], &id, sizeof(int));
+        for (int k = 0; k < 3; ++k) { tb[TB_POS + e * 3 + k] = el.pos[k]; tb[TB_AXIS + e * 3 + k] = el.axis[k]; }
+        for (int d : {0, 1, 4, 5}) if (el.nbr[d] >= 0) L[(size_t)e * N_TOP + sh[el.nbr[d]].a * 11 + sh[el.nbr[d]].c] = -kWTen;
+        L[(size_t)e * N_TOP + e] = lattice_diag(el.nn);
     }
     std::vector<double> Li = invert(L, N_TOP);
     // lattice part: laid out exactly as the kernels' workgroup-resident LDS copy
     for (int i = 0; i < N_TOP; ++i) for (int j = 0; j < N_TOP; ++j) tb[TB_LINV + (size_t)i * LROW + j] = (float)Li[(size_t)i * N_TOP + j];
-    for (int i = 0; i < N_TOP * 3; ++i) { tb[TB_POS + i] = elpos[i]; tb[TB_AXIS + i] = elaxis[i]; }
-    std::memcpy(&tb[TB_SHELL], shell.data(), shell.size() * sizeof(int));
     return upload_tables(h, tb);
 }
 
-template <int TORSO, int G, int MODE>
-static hipError_t launch_step(usim_handle* h, const DevIO& io, int flags, long long rstep, hipStream_t s) {
-    dim3 grid((h->n + GroupGeom<G>::EPB - 1) / GroupGeom<G>::EPB), block(GroupGeom<G>::NT);
-    hipLaunchKernelGGL((usim_step_kernel<TORSO, G, MODE>), grid, block, h->lds_bytes, s, h->M, h->C, h->state, h->n, h->npad, io, flags, rstep);
-    return hipGetLastError();
-}
-
-template <int TORSO, int OCC, int MODE>
-static hipError_t launch_step16(usim_handle* h, const DevIO& io, int flags, long long rstep, hipStream_t s) {
-    dim3 grid((h->n + 15) / 16), block(256);
-    if (MODE == 0 && (io.nsub > 1 || h->C.substeps > 1)) hipLaunchKernelGGL((usim_step16_kernel<TORSO, OCC, MODE, MODE == 0>), grid, block, h->lds16_bytes, s, h->M, h->C, h->state, h->n, h->npad, io, flags, rstep);
-    else hipLaunchKernelGGL((usim_step16_kernel<TORSO, OCC, MODE, false>), grid, block, h->lds16_bytes, s, h->M, h->C, h->state, h->n, h->npad, io, flags, rstep);
-    return hipGetLastError();
+// dynamic LDS limit of every kernel the handle can launch: those of its mapping, for a soft-torso handle those of every soft-torso mapping (usim_set_mapping)
+static int set_lds_limits(usim_handle* h) {
+    for (int m = 0; m <= (int)Mapping::SPLIT8; ++m)
+        if ((Mapping)m == h->map || (soft_torso((Mapping)m) && soft_torso(h->map)))
+            for (int i = 0; i < 4; ++i) {
+                const Kernel k = kernel_of((Mapping)m, i & 1, i >> 1);
+                HIPCHK(h, hipFuncSetAttribute(k.step ? (const void*)k.step : (const void*)k.split, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_words * (int)sizeof(float)));
+            }
+    return USIM_OK;
 }
 
 template <int MODE>
 static int launch(usim_handle* h, DevIO io, int flags, long long rstep, hipStream_t s) {
     io.bank_row0 = h->bank_row0;
-    hipError_t e;
-    // the full torso runs usim_step_kernel (one wave per environment); the rigid and soft torsos the kernels with the arm mathematics distributed over
-    // 16 lanes (usim_step16.h)
-    if (h->cfg.torso == USIM_TORSO_FULL) {
-        e = launch_step<2, 64, MODE>(h, io, flags, rstep, s);           // one wave per environment (usim_full.h)
-    } else if (h->lpe == 64 && MODE == 0) {
-        // split kernel with 8-lane groups: 32 environments per workgroup (8 per wave pair)
-        constexpr int EPB8 = 8 * wpr<8>();
-        dim3 grid((h->n + EPB8 - 1) / EPB8), block(128 * wpr<8>());
-        if (io.nsub > 1 || h->C.substeps > 1) hipLaunchKernelGGL((usim_step32_kernel<true, 8>), grid, block, h->lds64_bytes, s, h->d_M, h->d_C, h->state, h->n, h->npad, io, flags, rstep);
-        else hipLaunchKernelGGL((usim_step32_kernel<false, 8>), grid, block, h->lds64_bytes, s, h->d_M, h->d_C, h->state, h->n, h->npad, io, flags, rstep);
-        e = hipGetLastError();
-    } else if (h->lpe == 32 && MODE == 0) {
-        constexpr int EPB16 = 4 * wpr<16>();                            // environments per workgroup
-        dim3 grid((h->n + EPB16 - 1) / EPB16), block(128 * wpr<16>());
-        if (io.nsub > 1 || h->C.substeps > 1) hipLaunchKernelGGL((usim_step32_kernel<true, 16>), grid, block, h->lds32_bytes, s, h->d_M, h->d_C, h->state, h->n, h->npad, io, flags, rstep);
-        else hipLaunchKernelGGL((usim_step32_kernel<false, 16>), grid, block, h->lds32_bytes, s, h->d_M, h->d_C, h->state, h->n, h->npad, io, flags, rstep);
-        e = hipGetLastError();
-    } else {
-        // (reset computations are not register-critical: always the two-waves-per-SIMD build)
-        if (!h->n_el) e = launch_step16<0, 2, MODE>(h, io, flags, rstep, s);
-        else if constexpr (MODE == 0) e = (h->occ == 1) ? launch_step16<1, 1, 0>(h, io, flags, rstep, s) : launch_step16<1, 2, 0>(h, io, flags, rstep, s);
-        else e = launch_step16<1, 2, MODE>(h, io, flags, rstep, s);
-    }
+    const Kernel k = kernel_of(h->map, MODE, io.nsub > 1 || h->C.substeps > 1);
+    const dim3 grid((h->n + k.epb - 1) / k.epb), block(k.nt);
+    const size_t lds = (size_t)k.lds_words * sizeof(float);
+    if (k.step) hipLaunchKernelGGL(k.step, grid, block, lds, s, h->M, h->C, h->state, h->n, h->npad, io, flags, rstep);
+    else hipLaunchKernelGGL(k.split, grid, block, lds, s, h->d_M, h->d_C, h->state, h->n, h->npad, io, flags, rstep);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->hip_err = std::string("usim_step_kernel launch: ") + hipGetErrorString(e); return USIM_ERR_HIP; }
     return USIM_OK;
 }
@@ -415,40 +439,10 @@ int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** ou
     HIPCHK(h, hipEventCreate(&h->ev0));
     HIPCHK(h, hipEventCreate(&h->ev1));
     for (int i = 0; i < usim_handle::RF_RING; ++i) { HIPCHK(h, hipEventCreate(&h->rf0[i])); HIPCHK(h, hipEventCreate(&h->rf1[i])); }
-    // kernel mapping
-    // Rigid torso: 16 lanes per environment (arm mathematics distributed over the group).
-    // Soft torso, automatic choice (unless a register budget was asked for): the split kernel -- up to 4096 envs/GPU with 16-lane groups (32: two
-    // waves per quad of environments, 16 environments per workgroup = one workgroup per CU), beyond with 8-lane groups (64: two environments per
-    // DPP row, 32 environments per workgroup: 8192 envs still one workgroup per CU, 23.8 vs 29.3 us/step; profiles/r03/bench_matrix.txt).
-    h->lpe = h->n_el ? (cfg->lanes_per_env == 0 ? (cfg->waves_per_simd == 0 ? (n_envs <= 4096 ? 32 : 64) : 16) : cfg->lanes_per_env)
-                     : (cfg->lanes_per_env == 0 ? 16 : cfg->lanes_per_env);
-    if (h->n_el ? (h->lpe != 16 && h->lpe != 32 && h->lpe != 64) : h->lpe != 16) return USIM_ERR_INVALID;
-    if (cfg->torso == USIM_TORSO_FULL) {
-        // the full torso runs one mapping: a wave per environment, the Panda's constants, one physics step per control step, one step per launch
-        if (cfg->robot != USIM_ROBOT_PANDA || C.substeps > 1) { h->hip_err = "torso = USIM_TORSO_FULL: Panda, substeps = 1"; return USIM_ERR_UNSUPPORTED; }
-        h->lpe = 1; h->occ = 1;
-        h->lds_bytes = (size_t)GroupGeom<64>::LDS_WORDS * sizeof(float);
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step_kernel<2, 64, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step_kernel<2, 64, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-        return USIM_OK;
-    }
-    h->occ = cfg->waves_per_simd ? cfg->waves_per_simd : (n_envs <= 4096 ? 1 : 2);
-    // (every 16-lane kernel: + the arm table, parked behind everything else by multi-step launches)
-    h->lds16_bytes = (size_t)((h->n_el ? arm_lds_base<1, 0, 16>() : arm_lds_base<0, 0, 16>()) + ARM_LDS_WORDS) * sizeof(float);
-    h->lds32_bytes = (size_t)(arm_lds_base<1, 1, 16>() + ARM_LDS_WORDS) * sizeof(float);
-    h->lds64_bytes = (size_t)(arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS) * sizeof(float);
-    if (h->n_el) {
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step32_kernel<false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds32_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step32_kernel<true, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds32_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step32_kernel<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds64_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step32_kernel<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds64_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step16_kernel<1, 1, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds16_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step16_kernel<1, 1, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds16_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step16_kernel<1, 2, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds16_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step16_kernel<1, 2, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds16_bytes));
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&usim_step16_kernel<1, 2, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds16_bytes));
-    }
-    return USIM_OK;
+    if (!resolve_mapping(cfg->torso, cfg->lanes_per_env, cfg->waves_per_simd, n_envs, &h->map)) return USIM_ERR_INVALID;
+    // the full torso runs one mapping: a wave per environment, the Panda's constants, one physics step per control step, one step per launch
+    if (h->map == Mapping::FULL && (cfg->robot != USIM_ROBOT_PANDA || C.substeps > 1)) { h->hip_err = "torso = USIM_TORSO_FULL: Panda, substeps = 1"; return USIM_ERR_UNSUPPORTED; }
+    return set_lds_limits(h);
 }
 
 void usim_destroy(usim_handle* h) {
@@ -468,10 +462,8 @@ void usim_destroy(usim_handle* h) {
 }
 
 int usim_set_mapping(usim_handle* h, int lanes_per_env, int waves_per_simd) {
-    if (!h || !h->n_el || h->cfg.torso == USIM_TORSO_FULL || (lanes_per_env != 16 && lanes_per_env != 32 && lanes_per_env != 64) || waves_per_simd < 0 || waves_per_simd > 2) return USIM_ERR_INVALID;
-    h->lpe = lanes_per_env;
-    h->occ = waves_per_simd ? waves_per_simd : (h->n <= 4096 ? 1 : 2);
-    return USIM_OK;
+    if (!h || !soft_torso(h->map) || lanes_per_env == 0) return USIM_ERR_INVALID;
+    return resolve_mapping(h->cfg.torso, lanes_per_env, waves_per_simd, h->n, &h->map) ? USIM_OK : USIM_ERR_INVALID;
 }
 
 int usim_set_steps_per_launch(usim_handle* h, int steps) {
@@ -598,10 +590,9 @@ int usim_rollout_random(usim_handle* h, int64_t first_step, int nsteps, const us
     DevIO io; int rc = fill_io(s, io, false);
     if (rc) return rc;
     io.act = nullptr;
-    const size_t n = (size_t)h->n;
     // the 16-lane kernels run up to h->steps_per_launch consecutive steps per launch (usim_step16.h step16_body); a launch never crosses the
     // refill period of the reset bank (an environment consumes at most one ring slot per step)
-    const int kmax = (h->lpe == 16 || h->lpe == 32 || h->lpe == 64) ? h->steps_per_launch : 1;
+    const int kmax = multi_step(h->map) ? h->steps_per_launch : 1;
     for (int k = 0; k < nsteps;) {
         int kk = nsteps - k < kmax ? nsteps - k : kmax;
         if (kk > BANK_DEPTH - (int)h->steps_since_refill) kk = BANK_DEPTH - (int)h->steps_since_refill;
@@ -610,15 +601,7 @@ int usim_rollout_random(usim_handle* h, int64_t first_step, int nsteps, const us
         rc = step_common(h, io, LF_AUTO_RESET | LF_RANDOM_ACT, (long long)(first_step + k), stream);
         if (rc) return rc;
         k += kk;
-        if (block_advance) {
-            const size_t adv = n * (size_t)kk;
-            io.obs += adv * OBS_DIM; io.rew += adv; io.done += adv;
-            if (io.term_obs) io.term_obs += adv * OBS_DIM;
-            if (io.contacts) io.contacts += adv * (1 + MAXC);
-            if (io.ep_ret) io.ep_ret += adv;
-            if (io.ep_len) io.ep_len += adv;
-            if (io.act_out) io.act_out += adv * h->adim;
-        }
+        if (block_advance) advance_rollout_block(io, (size_t)h->n * kk, h->adim);
     }
     return USIM_OK;
 }

@@ -101,6 +101,16 @@ struct DevIO {
     int block;
 };
 
+// rollout blocks [steps][n][...] (DevIO::block): move the block pointers on by `rows` = steps * n rows; adim: words per action
+__host__ __device__ inline void advance_rollout_block(DevIO& io, size_t rows, int adim) {
+    io.obs += rows * OBS_DIM; io.rew += rows; io.done += rows;
+    if (io.term_obs) io.term_obs += rows * OBS_DIM;
+    if (io.contacts) io.contacts += rows * (1 + MAXC);
+    if (io.ep_ret) io.ep_ret += rows;
+    if (io.ep_len) io.ep_len += rows;
+    if (io.act_out) io.act_out += rows * adim;
+}
+
 enum LaunchFlags : int { LF_AUTO_RESET = 1, LF_RANDOM_ACT = 4 };
 
 // reset bank: BANK_DEPTH ring slots per environment (slot = episode mod depth), each holding a ready-made initial state and

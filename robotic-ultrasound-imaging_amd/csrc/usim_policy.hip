@@ -551,6 +551,13 @@ __global__ void usim_policy_gae_kernel(const float* __restrict__ rewards, const 
     }
 }
 
+// the C ABI's structs as kernel arguments, and the arguments usim_policy_step and usim_policy_step_fused both require
+static PolicyNet policy_net(const usim_policy_net& n) { return {n.pi_w1, n.pi_b1, n.pi_w2, n.pi_b2, n.act_w, n.act_b, n.vf_w1, n.vf_b1, n.vf_w2, n.vf_b2, n.val_w, n.val_b, n.log_std, reinterpret_cast<const float4*>(n.w2_packed)}; }
+static NormStats norm_stats(const usim_norm_stats& s) { return {s.obs_mean, s.obs_var, s.obs_count, s.ret_mean, s.ret_var, s.ret_count, s.returns, s.clip_obs, s.clip_reward, s.gamma, s.epsilon}; }
+static bool step_args_ok(const usim_policy_net* net, const usim_norm_stats* st, const float* obs_dev, int n, int act_dim, const float* lo, const float* hi, const usim_policy_out* out) {
+    return net && st && obs_dev && out && out->act_env_dev && n > 0 && act_dim >= 1 && act_dim <= 7 && lo && hi && net->w2_packed;
+}
+
 }  // namespace usim
 
 extern "C" {
@@ -565,10 +572,10 @@ int usim_policy_step(const usim_policy_net* net, const usim_norm_stats* st, cons
                      const float* act_low_dev, const float* act_high_dev, uint64_t seed, uint32_t counter, const uint32_t* counter_base_dev, int env_offset,
                      int training, int deterministic, const usim_policy_out* out, void* stream) {
     using namespace usim;
-    if (!net || !st || !obs_dev || !out || !out->act_env_dev || n <= 0 || act_dim < 1 || act_dim > 7 || !act_low_dev || !act_high_dev || !net->w2_packed) return USIM_ERR_INVALID;
+    if (!step_args_ok(net, st, obs_dev, n, act_dim, act_low_dev, act_high_dev, out)) return USIM_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    PolicyNet P{net->pi_w1, net->pi_b1, net->pi_w2, net->pi_b2, net->act_w, net->act_b, net->vf_w1, net->vf_b1, net->vf_w2, net->vf_b2, net->val_w, net->val_b, net->log_std, reinterpret_cast<const float4*>(net->w2_packed)};
-    NormStats S{st->obs_mean, st->obs_var, st->obs_count, st->ret_mean, st->ret_var, st->ret_count, st->returns, st->clip_obs, st->clip_reward, st->gamma, st->epsilon};
+    const PolicyNet P = policy_net(*net);
+    const NormStats S = norm_stats(*st);
     if (training == 1) {
         if (!st->scratch) return USIM_ERR_INVALID;
         // scratch: PL_SB x 19 x 2 partial sums, then the arrival counter (zero on entry, left zero)
@@ -584,7 +591,7 @@ int usim_policy_step_fused(const usim_policy_net* net, const usim_norm_stats* st
                            int act_dim, const float* act_low_dev, const float* act_high_dev, uint64_t seed, uint32_t counter, const uint32_t* counter_base_dev,
                            int env_offset, int deterministic, const usim_policy_out* out, void* stream) {
     using namespace usim;
-    if (!net || !st || !f || !obs_dev || !out || !out->act_env_dev || n <= 0 || act_dim < 1 || act_dim > 7 || !act_low_dev || !act_high_dev || !net->w2_packed) return USIM_ERR_INVALID;
+    if (!f || !step_args_ok(net, st, obs_dev, n, act_dim, act_low_dev, act_high_dev, out)) return USIM_ERR_INVALID;
     if (!f->work_dev || (f->have_prev && (!f->rew_prev_dev || !f->done_prev_dev || !f->nrew_prev_dev))) return USIM_ERR_INVALID;
     if (n > USIM_POLICY_FUSED_MAX_ENVS) return USIM_ERR_UNSUPPORTED;          // every workgroup must be resident (see the kernel)
     {
@@ -603,8 +610,8 @@ int usim_policy_step_fused(const usim_policy_net* net, const usim_norm_stats* st
         }
         if (2 * ((n + PL_TM - 1) / PL_TM) > cap) return USIM_ERR_UNSUPPORTED;
     }
-    PolicyNet P{net->pi_w1, net->pi_b1, net->pi_w2, net->pi_b2, net->act_w, net->act_b, net->vf_w1, net->vf_b1, net->vf_w2, net->vf_b2, net->val_w, net->val_b, net->log_std, reinterpret_cast<const float4*>(net->w2_packed)};
-    NormStats S{st->obs_mean, st->obs_var, st->obs_count, st->ret_mean, st->ret_var, st->ret_count, st->returns, st->clip_obs, st->clip_reward, st->gamma, st->epsilon};
+    const PolicyNet P = policy_net(*net);
+    const NormStats S = norm_stats(*st);
     FusedArgs F{f->rew_prev_dev, f->done_prev_dev, f->nrew_prev_dev, f->raw_sum_dev, f->work_dev, f->update_obs, f->have_prev, f->norm_reward};
     hipLaunchKernelGGL(usim_policy_act_kernel<true>, dim3((n + PL_TM - 1) / PL_TM, 2), dim3(256), 0, (hipStream_t)stream, P, S, obs_dev, prev_done_dev, n,
                        act_dim, act_low_dev, act_high_dev, (uint32_t)seed, (uint32_t)(seed >> 32), counter, counter_base_dev, env_offset, deterministic, out->nobs_dev, out->act_dev,
@@ -616,7 +623,7 @@ int usim_policy_reward(const usim_norm_stats* st, const float* rew_dev, const ui
                        double* raw_sum_dev, const float* next_obs_dev, void* stream) {
     using namespace usim;
     if (!st || !rew_dev || !done_dev || !nrew_dev || n <= 0) return USIM_ERR_INVALID;
-    NormStats S{st->obs_mean, st->obs_var, st->obs_count, st->ret_mean, st->ret_var, st->ret_count, st->returns, st->clip_obs, st->clip_reward, st->gamma, st->epsilon};
+    const NormStats S = norm_stats(*st);
     if (next_obs_dev && training) {
         if (!st->scratch) return USIM_ERR_INVALID;
         hipLaunchKernelGGL(usim_policy_post_kernel, dim3(PL_SB + 1), dim3(1024), 0, (hipStream_t)stream, rew_dev, done_dev, n, S, training, norm_reward, nrew_dev, raw_sum_dev,

@@ -1297,15 +1297,7 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
             // against 14.8 with the barriers, whatever the sleep length (8192 envs, 8-lane groups: 23.4 against 22.7).
             __threadfence_block();
             if constexpr (ROLE != 0) USIM_BAR();
-            if (io0.block && ctrl_done) {
-                const size_t nn = (size_t)n;
-                io.obs += nn * OBS_DIM; io.rew += nn; io.done += nn;
-                if (io.term_obs) io.term_obs += nn * OBS_DIM;
-                if (io.contacts) io.contacts += nn * (1 + MAXC);
-                if (io.ep_ret) io.ep_ret += nn;
-                if (io.ep_len) io.ep_len += nn;
-                if (io.act_out) io.act_out += nn * C.adim;
-            }
+            if (io0.block && ctrl_done) advance_rollout_block(io, (size_t)n, C.adim);
         }
     }
 #if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)

@@ -53,6 +53,44 @@ def test_error_conventions_on_device(usim):
     lib.usim_destroy(h)
 
 
+def test_mapping_refusal_matrix(usim):
+    """which kernel mappings usim_create and usim_set_mapping accept (include/usim.h lanes_per_env, waves_per_simd): the rigid torso takes
+    lanes_per_env 0 or 16, the soft and full torsos 0, 16, 32 or 64 (the full torso ignores it), every torso waves_per_simd 0 .. 2;
+    usim_set_mapping switches soft-torso handles only, between lanes_per_env 16, 32 and 64"""
+    lib = usim._lib.load()
+    lanes_ok = {0: (0, 16), 1: (0, 16, 32, 64), 2: (0, 16, 32, 64)}
+    got, want = {}, {}
+    for torso in (0, 1, 2):
+        for lanes in (0, 1, 5, 8, 16, 32, 64):
+            for waves in (0, 1, 2, 3):
+                cfg = usim._lib.UsimConfig()
+                cfg.struct_size = C.sizeof(cfg)
+                assert lib.usim_default_config(C.byref(cfg)) == 0
+                cfg.torso, cfg.lanes_per_env, cfg.waves_per_simd = torso, lanes, waves
+                h = C.c_void_p()
+                got[torso, lanes, waves] = lib.usim_create(C.byref(cfg), 8, 0, C.byref(h))
+                want[torso, lanes, waves] = 0 if lanes in lanes_ok[torso] and waves <= 2 else -1
+                if h:
+                    lib.usim_destroy(h)
+    assert got == want
+    assert lib.usim_set_mapping(None, 32, 0) == -1
+    for torso in (0, 1, 2):
+        cfg = usim._lib.UsimConfig()
+        cfg.struct_size = C.sizeof(cfg)
+        assert lib.usim_default_config(C.byref(cfg)) == 0
+        cfg.torso = torso
+        h = C.c_void_p()
+        assert lib.usim_create(C.byref(cfg), 8, 0, C.byref(h)) == 0
+        got, want = {}, {}
+        for lanes in (0, 1, 5, 8, 16, 32, 64):
+            for waves in (-1, 0, 1, 2, 3):
+                got[lanes, waves] = lib.usim_set_mapping(h, lanes, waves)
+                want[lanes, waves] = 0 if torso == 1 and lanes in (16, 32, 64) and 0 <= waves <= 2 else -1
+        assert got == want, torso
+        assert lib.usim_set_mapping(h, 32, 0) == (0 if torso == 1 else -1)
+        lib.usim_destroy(h)
+
+
 def test_profile_step_needs_the_profiling_build(usim):
     """the phase stamps are compiled into libusim_prof.so only (make -C csrc prof); the production library says so instead of
     returning zeros"""

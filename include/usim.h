@@ -76,6 +76,8 @@ typedef struct usim_config {
                                                 * convex contact problem -- every contact solves its own 3 x 3 cone block at the same time (ray update, then the friction QCQP with
                                                 * the normal fixed), the step along the joint direction is the minimiser of the quadratic with the slope taken block by block, capped at 1.  24 iterations rest
                                                 * 2e-3 N (99th percentile) from the optimum, which is what MuJoCo's Newton solver converges to.
+                                                * With warm_start = 1 the iterations start from the previous physics step's forces instead of zero, so a given count ends
+                                                * closer to the optimum (18 warm iterations follow a converged solve's decisions as 24 cold ones do).
                                                 * USIM_TORSO_FULL: sweeps of a block Gauss-Seidel over the probe and the element-table contacts, started from the forces of the
                                                 * previous physics step (94 % of the environments follow a converged solve's decisions at 24) */
     int32_t ik_iters;                          /* reset inverse-kinematics iterations */
@@ -116,7 +118,15 @@ typedef struct usim_config {
                                                 * convex problem, as in MuJoCo -- the same three rows twice, each with a single contact's regulariser, cones
                                                 * mu_A = max(probe_friction, elem_friction) (the per-environment friction word) and mu_B = max(probe_friction2, elem_friction).
                                                 * 0: the merged contact of rounds 3-4 (half the normal regulariser, cone (mu_A + mu_B) / 2) */
-    int32_t reserved0;                         /* (keeps the struct a multiple of 8 bytes) */
+    int32_t warm_start;                        /* USIM_TORSO_TOP: 1 = every contact solve starts from the forces of the previous physics step, as MuJoCo's solver does
+                                                * (mj_step warm-starts from qacc_warmstart): an environment keeps the element of each contact slot with the force and friction
+                                                * multiplier of its two virtual contacts; the next solve matches its contacts against that list by element, a matched contact
+                                                * starts from the kept values (the shared residual from b + A s0), an unmatched one from zero.  Carried from substep to substep;
+                                                * an episode starts cold (auto-reset, usim_reset, usim_reset_explicit, fault-guard restart), and so does a state set with
+                                                * usim_set_state.  0 (default): cold start, the behaviour of earlier versions bit for bit.  Rigid and full torso: 0 or 1, no
+                                                * effect (the full torso is always warm).  Anything else: USIM_ERR_INVALID.  The USIM_WARM_START environment variable (0 / 1),
+                                                * read by usim_create, replaces the field's value for every handle the process creates afterwards -- a switch for timing a fixed
+                                                * command line, in either direction; usim_has_warm_start says what a handle runs.  (Was reserved0: same offset, same sizeof) */
     double armature_scale;                     /* rotor inertia armature_i = armature_scale * 5 / (i + 1) kg m^2 on arm joint i (MuJoCo joint armature: added to the diagonal of the
                                                 * mass matrix -- the plant's and, through sim.data.qM, the OSC controller's).  [RECALLED: robosuite >= 1.2 RobotModel.__init__ sets armature
                                                 * 5 / (i + 1), frictionloss 0.1 and damping 0.1 on robot joints that do not specify them; the reference imports robosuite.utils.observables
@@ -168,6 +178,8 @@ int usim_set_mapping(usim_handle* h, int lanes_per_env, int waves_per_simd);
 int usim_num_envs(const usim_handle* h);
 int usim_action_dim(const usim_handle* h);     /* GymWrapper.action_space.shape[0] */
 int usim_num_elements(const usim_handle* h);   /* dynamic torso elements per env (0, 99 or 270) */
+int usim_has_warm_start(const usim_handle* h); /* 1: the handle keeps a contact list for usim_get_warm_start / usim_set_warm_start (USIM_TORSO_TOP with warm_start = 1, after
+                                                * USIM_WARM_START); 0: it does not; < 0: error code */
 
 /* Replaces env.reset() (ultrasound.py:416-478) for the envs where mask_dev[i] != 0 (NULL = all).
  * obs_dev [n][19] (may be NULL) receives the reset observation of the selected envs. */
@@ -232,6 +244,13 @@ int usim_set_state(usim_handle* h, const float* scalars, const float* lattice);
 #define USIM_FULL_BODY_WORDS (13 + 4 * 270 + 8 + 64)
 int usim_get_body_state(usim_handle* h, double* body);
 int usim_set_body_state(usim_handle* h, const double* body);
+/* USIM_TORSO_TOP with warm_start = 1 (any other handle: USIM_ERR_INVALID): host buffers [n][USIM_WARM_WORDS] of float32 -- the kept contact list of the solver, the part of
+ * the state that usim_get_state does not carry: [8] the element (0 .. 98) of each contact slot of the previous physics step, -1 for an empty slot; then [16][4] force
+ * (normal, two tangents) and friction multiplier of the virtual contacts, contact A of slot c at c, contact B at 8 + c.  Synchronises the device.  usim_set_state empties the
+ * list (a state set from outside starts cold); usim_set_warm_start after it restores a checkpoint exactly. */
+#define USIM_WARM_WORDS (8 + 16 * 4)
+int usim_get_warm_start(usim_handle* h, float* w);
+int usim_set_warm_start(usim_handle* h, const float* w);
 
 /* Diagnostics: runs one step (in-kernel synthetic actions of `step`, auto-reset on) on the default stream, blocks, and returns
  * shader-clock stamps taken in workgroup 0: ticks[0..16] by wave 0 at the phase boundaries of the single-wave step

@@ -16,6 +16,7 @@ NSCALAR = 40
 POLICY_PACKED = 2 * 128 * 256      # USIM_POLICY_PACKED
 RESET_PARAMS = 13
 LOG_WIDTH = 53
+WARM_WORDS = 8 + 16 * 4            # USIM_WARM_WORDS
 
 MODE = {"tracking": 0, "fixed": 1, "variable_z": 2, "wrench": 3}
 TORSO = {"none": 0, "rigid": 0, "top": 1, "soft": 1, "full": 2}
@@ -31,7 +32,7 @@ class UsimConfig(C.Structure):
         [("seed", C.c_uint64)] + [(n, C.c_double) for n in (
             "control_dt", "kp_fixed", "damping_ratio", "kp_min", "kp_max", "out_max_pos", "out_max_ori", "stiffness", "damping",
             "elem_friction", "probe_friction", "probe_radius", "probe_halflen", "probe_radius2", "probe_height")] + \
-        [("substeps", C.c_int32), ("probe_geoms", C.c_int32), ("probe_friction2", C.c_double), ("probe_halfwidth", C.c_double), ("probe_tip", C.c_double), ("pair_model", C.c_int32), ("reserved0", C.c_int32), ("armature_scale", C.c_double), ("joint_frictionloss", C.c_double)]
+        [("substeps", C.c_int32), ("probe_geoms", C.c_int32), ("probe_friction2", C.c_double), ("probe_halfwidth", C.c_double), ("probe_tip", C.c_double), ("pair_model", C.c_int32), ("warm_start", C.c_int32), ("armature_scale", C.c_double), ("joint_frictionloss", C.c_double)]
 
 
 class UsimStepIO(C.Structure):
@@ -84,6 +85,7 @@ SYMBOLS = {
     "usim_num_envs": (C.c_int, [C.c_void_p]),
     "usim_action_dim": (C.c_int, [C.c_void_p]),
     "usim_num_elements": (C.c_int, [C.c_void_p]),
+    "usim_has_warm_start": (C.c_int, [C.c_void_p]),
     "usim_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_reset_explicit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_step": (C.c_int, [C.c_void_p, C.POINTER(UsimStepIO), C.c_int, C.c_void_p]),
@@ -94,6 +96,8 @@ SYMBOLS = {
     "usim_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_get_body_state": (C.c_int, [C.c_void_p, C.c_void_p]),
     "usim_set_body_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "usim_get_warm_start": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "usim_set_warm_start": (C.c_int, [C.c_void_p, C.c_void_p]),
     "usim_profile_step": (C.c_int, [C.c_void_p, C.POINTER(UsimStepIO), C.c_int64, C.POINTER(C.c_uint64), C.c_int]),
     "usim_strerror": (C.c_char_p, [C.c_int]),
     "usim_last_hip_error": (C.c_char_p, [C.c_void_p]),

@@ -25,7 +25,7 @@ _DEFAULT_ONLY = {
 }
 # extensions of this build (not kwargs of the reference env)
 _NATIVE = {"torso", "friction_randomization", "torso_drop", "pgs_iters", "ik_iters", "lanes_per_env", "waves_per_simd", "stiffness", "damping",
-           "elem_friction", "probe_friction", "probe_friction2", "probe_geoms", "pair_model", "probe_radius", "probe_halflen", "probe_radius2", "probe_height", "probe_halfwidth", "probe_tip", "armature_scale", "joint_frictionloss"}
+           "elem_friction", "probe_friction", "probe_friction2", "probe_geoms", "pair_model", "probe_radius", "probe_halflen", "probe_radius2", "probe_height", "probe_halfwidth", "probe_tip", "armature_scale", "joint_frictionloss", "warm_start"}
 
 
 def default_robosuite_kwargs():
@@ -110,7 +110,7 @@ def make_config(seed=3, env_offset=0, **kw):
     if torso not in _lib.TORSO:
         raise ValueError(f"torso must be one of {sorted(_lib.TORSO)}")
     c.torso = _lib.TORSO[torso]
-    for k in ("friction_randomization", "torso_drop", "pgs_iters", "ik_iters", "lanes_per_env", "waves_per_simd", "probe_geoms", "pair_model"):
+    for k in ("friction_randomization", "torso_drop", "pgs_iters", "ik_iters", "lanes_per_env", "waves_per_simd", "probe_geoms", "pair_model", "warm_start"):
         if k in kw:
             setattr(c, k, int(kw.pop(k)))
     for k in ("stiffness", "damping", "elem_friction", "probe_friction", "probe_friction2", "probe_radius", "probe_halflen", "probe_radius2", "probe_height", "probe_halfwidth", "probe_tip", "armature_scale", "joint_frictionloss"):

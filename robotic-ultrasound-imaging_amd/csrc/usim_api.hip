@@ -34,6 +34,8 @@ using namespace usim;
 // = one workgroup per CU), beyond lanes 64 (two environments per DPP row, 32 per workgroup: 8192 envs still one workgroup per CU, 23.8 vs 29.3 us/step;
 // profiles/r03/bench_matrix.txt) --, a nonzero waves_per_simd (a register budget) lanes 16.  Waves per SIMD: the value given, else 1 up to 4096 envs, 2 beyond.
 // Refused: waves_per_simd outside 0 .. 2, any other lanes_per_env; usim_set_mapping also refuses lanes 0 and rigid / full-torso handles.
+// usim_config.warm_start on a soft-torso handle: the step launch of its mapping is the instantiation with the warm start (last template argument true); the
+// reset / refill launch likewise (it empties the warm rows of the environments it resets).  Rigid and full torso: no effect.
 enum class Mapping : int { FULL, RIGID16, SOFT16_W1, SOFT16_W2, SPLIT16, SPLIT8 };
 static bool resolve_mapping(int torso, int lanes_per_env, int waves_per_simd, int n_envs, Mapping* m) {
     if (waves_per_simd < 0 || waves_per_simd > 2) return false;
@@ -51,9 +53,19 @@ static bool multi_step(Mapping m) { return m != Mapping::FULL; }           // se
 // everything else); model and configuration by value, or through pointers for the split kernels
 struct Kernel { void (*step)(const DevModel, const DevCfg, float*, int, int, const DevIO, int, long long); void (*split)(const DevModel*, const DevCfg*, float*, int, int, const DevIO, int, long long);
                 int epb, nt, lds_words; };
-static Kernel kernel_of(Mapping m, int mode, bool multi) {
+static Kernel kernel_of(Mapping m, int mode, bool multi, bool warm) {
     if (mode != 0 && soft_torso(m)) m = Mapping::SOFT16_W2;
     const bool r = mode != 0, mu = !r && multi;
+    if (warm && soft_torso(m)) {
+        constexpr int L16 = arm_lds_base<1, 0, 16>() + ARM_LDS_WORDS;
+        if (r) return {usim_step16_kernel<1, 2, 1, false, true>, nullptr, 16, 256, L16};
+        switch (m) {
+            case Mapping::SOFT16_W1: return {mu ? usim_step16_kernel<1, 1, 0, true, true> : usim_step16_kernel<1, 1, 0, false, true>, nullptr, 16, 256, L16};
+            case Mapping::SOFT16_W2: return {mu ? usim_step16_kernel<1, 2, 0, true, true> : usim_step16_kernel<1, 2, 0, false, true>, nullptr, 16, 256, L16};
+            case Mapping::SPLIT16: return {nullptr, mu ? usim_step32_kernel<true, 16, true> : usim_step32_kernel<false, 16, true>, 4 * wpr<16>(), 128 * wpr<16>(), arm_lds_base<1, 1, 16>() + ARM_LDS_WORDS};
+            default: return {nullptr, mu ? usim_step32_kernel<true, 8, true> : usim_step32_kernel<false, 8, true>, 8 * wpr<8>(), 128 * wpr<8>(), arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS};
+        }
+    }
     constexpr int L16 = arm_lds_base<1, 0, 16>() + ARM_LDS_WORDS;
     switch (m) {
         case Mapping::FULL: return {r ? usim_step_kernel<2, 64, 1> : usim_step_kernel<2, 64, 0>, nullptr, GroupGeom<64>::EPB, GroupGeom<64>::NT, GroupGeom<64>::LDS_WORDS};
@@ -90,6 +102,7 @@ struct usim_handle {
     long long steps_since_refill = 0;
     int steps_per_launch = 256;      // usim_rollout_random: consecutive steps per launch of the 16-lane kernels (USIM_STEPS_PER_LAUNCH overrides, 1 .. MAX_STEPS_PER_LAUNCH)
     int bank_row0 = 0;
+    bool warm = false;                // warm start of the top-face contact solve: warm rows behind the reset bank, the step / reset kernels that use them (kernel_of)
     std::string hip_err;
 };
 
@@ -338,16 +351,25 @@ static int set_lds_limits(usim_handle* h) {
     for (int m = 0; m <= (int)Mapping::SPLIT8; ++m)
         if ((Mapping)m == h->map || (soft_torso((Mapping)m) && soft_torso(h->map)))
             for (int i = 0; i < 4; ++i) {
-                const Kernel k = kernel_of((Mapping)m, i & 1, i >> 1);
+                const Kernel k = kernel_of((Mapping)m, i & 1, i >> 1, h->warm);
                 HIPCHK(h, hipFuncSetAttribute(k.step ? (const void*)k.step : (const void*)k.split, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_words * (int)sizeof(float)));
             }
+    return USIM_OK;
+}
+
+// every environment's warm rows to "nothing kept" (synchronous)
+static int warm_rows_reset(usim_handle* h) {
+    std::vector<float> w((size_t)WARM_WORDS * h->npad, 0.f);
+    const int none = -1;
+    for (int i = 0; i < h->npad; ++i) for (int k = 0; k < MAXC; ++k) std::memcpy(&w[(size_t)i * WARM_WORDS + WARM_EL + k], &none, 4);
+    HIPCHK(h, hipMemcpy(h->state + warm_index(h->bank_row0, h->npad, 0), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
     return USIM_OK;
 }
 
 template <int MODE>
 static int launch(usim_handle* h, DevIO io, int flags, long long rstep, hipStream_t s) {
     io.bank_row0 = h->bank_row0;
-    const Kernel k = kernel_of(h->map, MODE, io.nsub > 1 || h->C.substeps > 1);
+    const Kernel k = kernel_of(h->map, MODE, io.nsub > 1 || h->C.substeps > 1, h->warm);
     const dim3 grid((h->n + k.epb - 1) / k.epb), block(k.nt);
     const size_t lds = (size_t)k.lds_words * sizeof(float);
     if (k.step) hipLaunchKernelGGL(k.step, grid, block, lds, s, h->M, h->C, h->state, h->n, h->npad, io, flags, rstep);
@@ -380,7 +402,7 @@ int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** ou
     if (!(cfg->probe_halfwidth >= 0) || !(std::fabs(cfg->probe_tip) <= 0.02) || cfg->torso_drop < 0 || cfg->torso_drop > 2) return USIM_ERR_INVALID;
     if (cfg->mode < 0 || cfg->mode > 3 || cfg->torso < 0 || cfg->torso > 2 || !(cfg->armature_scale >= 0) || !(cfg->joint_frictionloss >= 0) || cfg->horizon <= 0 || cfg->control_dt <= 0 ||
         cfg->probe_halflen < 1e-4 || cfg->probe_radius <= 0 || cfg->pgs_iters < 0 || cfg->ik_iters < 0 || cfg->torso_shape < 0 ||
-        cfg->torso_shape > 1 || cfg->waves_per_simd < 0 || cfg->waves_per_simd > 2 || cfg->robot < 0 || cfg->robot > 1) return USIM_ERR_INVALID;
+        cfg->torso_shape > 1 || cfg->waves_per_simd < 0 || cfg->waves_per_simd > 2 || cfg->robot < 0 || cfg->robot > 1 || cfg->warm_start < 0 || cfg->warm_start > 1) return USIM_ERR_INVALID;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return USIM_ERR_NO_DEVICE;
     usim_handle* h = new (std::nothrow) usim_handle();
@@ -398,6 +420,10 @@ int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** ou
     C.key0 = (uint32_t)cfg->seed; C.key1 = (uint32_t)(cfg->seed >> 32);
     C.substeps = cfg->substeps > 1 ? cfg->substeps : 1;
     C.frictionloss = (float)cfg->joint_frictionloss;
+    // warm start of the top-face contact solve (the rigid torso has no contact solve, the full torso is always warm: accepted, no effect).  USIM_WARM_START = 0 / 1
+    // replaces the field, so that a fixed command line (bench.py) can time both; the handle's recorded configuration follows it
+    if (const char* ws = std::getenv("USIM_WARM_START")) { if ((ws[0] == '0' || ws[0] == '1') && ws[1] == 0) h->cfg.warm_start = ws[0] - '0'; }
+    h->warm = h->cfg.warm_start != 0 && cfg->torso == USIM_TORSO_TOP;
     C.dt_ctrl = (float)cfg->control_dt; C.dt = (float)(cfg->control_dt / C.substeps); C.kp_fixed = (float)cfg->kp_fixed; C.damping_ratio = (float)cfg->damping_ratio; C.kp_min = (float)cfg->kp_min;
     C.kp_max = (float)cfg->kp_max; C.out_pos = (float)cfg->out_max_pos; C.out_ori = (float)cfg->out_max_ori; C.stiffness = (float)cfg->stiffness;
     C.damping = (float)cfg->damping; C.elem_fric = (float)cfg->elem_friction; C.probe_fric = (float)cfg->probe_friction;
@@ -431,8 +457,10 @@ int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** ou
     h->nfields = (cfg->torso == USIM_TORSO_FULL) ? F_TOTAL_FULL : (h->n_el ? F_TOTAL_TOP : F_NSCALAR);
     h->bank_row0 = h->nfields;                                  // two reset-bank slots follow the live state rows
     size_t bytes = (size_t)(h->nfields + BANK_ROWS) * h->npad * sizeof(float);
-    HIPCHK(h, hipMalloc(&h->state, bytes));
-    HIPCHK(h, hipMemset(h->state, 0, bytes));
+    const size_t warm_bytes = h->warm ? (size_t)WARM_WORDS * h->npad * sizeof(float) : 0;      // warm rows behind the bank (usim_device.h warm_index)
+    HIPCHK(h, hipMalloc(&h->state, bytes + warm_bytes));
+    HIPCHK(h, hipMemset(h->state, 0, bytes + warm_bytes));
+    if (h->warm) { int rc2 = warm_rows_reset(h); if (rc2) return rc2; }
     HIPCHK(h, hipMalloc(&h->d_items, 2 * (size_t)h->n * BANK_DEPTH * sizeof(int2)));
     HIPCHK(h, hipMalloc(&h->d_count, 2 * sizeof(int)));
     HIPCHK(h, hipMemset(h->d_count, 0, 2 * sizeof(int)));
@@ -487,6 +515,7 @@ int usim_refill_time(usim_handle* h, double* total_ms, long long* launches) {
 int usim_num_envs(const usim_handle* h) { return h ? h->n : USIM_ERR_INVALID; }
 int usim_action_dim(const usim_handle* h) { return h ? h->adim : USIM_ERR_INVALID; }
 int usim_num_elements(const usim_handle* h) { return h ? h->n_el : USIM_ERR_INVALID; }
+int usim_has_warm_start(const usim_handle* h) { return h ? (h->warm ? 1 : 0) : USIM_ERR_INVALID; }
 
 // compute every episode on the refill work list into the reset bank (grid-stride over the list, one launch)
 static void refill_collect(usim_handle* h, int slot) {
@@ -664,6 +693,33 @@ int usim_set_body_state(usim_handle* h, const double* body) {
     return USIM_OK;
 }
 
+// soft top-face torso with usim_config.warm_start: the kept contact list of the solver, [n][USIM_WARM_WORDS] float32 (the device's warm rows with the elements as numbers)
+static_assert(WARM_WORDS == USIM_WARM_WORDS, "include/usim.h");
+int usim_get_warm_start(usim_handle* h, float* w) {
+    if (!h || !w || !h->warm) return USIM_ERR_INVALID;
+    DeviceGuard guard(h->device);
+    HIPCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipMemcpy(w, h->state + warm_index(h->bank_row0, h->npad, 0), (size_t)WARM_WORDS * h->n * sizeof(float), hipMemcpyDeviceToHost));
+    for (int i = 0; i < h->n; ++i) for (int k = 0; k < MAXC; ++k) {
+        float* p = &w[(size_t)i * WARM_WORDS + WARM_EL + k];
+        int v; std::memcpy(&v, p, 4); *p = (float)v;
+    }
+    return USIM_OK;
+}
+int usim_set_warm_start(usim_handle* h, const float* w) {
+    if (!h || !w || !h->warm) return USIM_ERR_INVALID;
+    DeviceGuard guard(h->device);
+    HIPCHK(h, hipDeviceSynchronize());
+    std::vector<float> buf(w, w + (size_t)WARM_WORDS * h->n);
+    for (int i = 0; i < h->n; ++i) for (int k = 0; k < MAXC; ++k) {
+        float* p = &buf[(size_t)i * WARM_WORDS + WARM_EL + k];
+        const int v = (*p >= 0.f && *p < (float)N_TOP) ? (int)*p : -1;       // (an element number the kernels can compare; anything else: empty slot)
+        std::memcpy(p, &v, 4);
+    }
+    HIPCHK(h, hipMemcpy(h->state + warm_index(h->bank_row0, h->npad, 0), buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
+    return USIM_OK;
+}
+
 int usim_get_state(usim_handle* h, float* scalars, float* lattice) {
     if (!h || !scalars) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
@@ -708,6 +764,7 @@ int usim_set_state(usim_handle* h, const float* scalars, const float* lattice) {
             }
     }
     HIPCHK(h, hipMemcpy(h->state, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (h->warm) { int rc = warm_rows_reset(h); if (rc) return rc; }          // a state set from outside starts cold (usim_set_warm_start after this call restores the list)
     // the bank is a pure function of (seed, env, episode): rebuild every ring for the restored episode counters
     HIPCHK(h, hipMemset(h->d_count, 0, 2 * sizeof(int)));
     {

@@ -123,4 +123,10 @@ constexpr int MAX_STEPS_PER_LAUNCH = 256;
 constexpr int BANK_STRIDE = 40;                       // words per slot (BANK_WORDS rounded up to 16 bytes)
 constexpr int BANK_ROWS = BANK_DEPTH * BANK_STRIDE;   // the bank is environment-major too: env i owns BANK_ROWS words, slot s at s * BANK_STRIDE
 
+// warm rows (usim_config.warm_start, soft top-face torso; allocated only then): WARM_WORDS words per environment behind the reset bank, environment-major -- the
+// kept contact list of the previous physics step in one layout for every mapping: the element of each of the MAXC contact slots (-1: empty), then force (3) and
+// friction multiplier of the 2 MAXC virtual contacts, contact A of slot c at c, contact B at MAXC + c (= usim_get_warm_start's block, the elements as ints)
+constexpr int WARM_EL = 0, WARM_F = MAXC, WARM_WORDS = MAXC + 2 * MAXC * 4;
+__host__ __device__ inline size_t warm_index(int bank_row0, int npad, size_t i) { return (size_t)(bank_row0 + BANK_ROWS) * npad + i * WARM_WORDS; }
+
 }  // namespace usim

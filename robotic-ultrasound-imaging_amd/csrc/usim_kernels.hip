@@ -545,6 +545,38 @@ DI typename LaneVec<T>::mask cone_local(const T b00, const T b01, const T b02, c
 struct ContactRows {
     float w[3][6], g[3], Rd[3], Km[MAXC], vrel0[3], ae0, kdist;
 };
+// Kept contact list of an environment (usim_config.warm_start; oracle: uso_env.warm_el / warm_fv / warm_lamv): the element of every contact slot of the previous
+// physics step with the force and the friction multiplier of its two virtual contacts.  The lane that runs a slot's visits keeps its record -- T = float: 16-lane
+// groups, contact A of slot k in lane k, contact B in lane 8 + k; T = v2f: 8-lane groups, both in lane k -- in registers from step to step of a multi-step launch and
+// in the environment's warm rows in HBM (usim_device.h WARM_*: one layout for every mapping) across launches.  NoWarm: handles without a warm start carry nothing.
+struct NoWarm {};
+template <class T> struct WarmRec { int el; T f[3], lam; };
+template <int G> struct WarmOf { typedef WarmRec<typename std::conditional<G == 16, float, v2f>::type> type; };
+template <class T> DI void warm_clear(WarmRec<T>& r) { r.el = -1; r.f[0] = r.f[1] = r.f[2] = r.lam = LaneVec<T>::splat(0.f); }
+DI void warm_clear(NoWarm&) {}
+// an environment's warm rows <-> the records of its group's lanes (every lane of the group calls; 16-byte accesses)
+DI void warm_load(const float* wp, const int gl, WarmRec<float>& r) {
+    const float4 x = *reinterpret_cast<const float4*>(wp + WARM_F + 4 * gl);
+    r.el = __float_as_int(wp[WARM_EL + (gl & 7)]); r.f[0] = x.x; r.f[1] = x.y; r.f[2] = x.z; r.lam = x.w;
+}
+DI void warm_load(const float* wp, const int gl, WarmRec<v2f>& r) {
+    const float4 a = *reinterpret_cast<const float4*>(wp + WARM_F + 4 * gl), b = *reinterpret_cast<const float4*>(wp + WARM_F + 4 * (MAXC + gl));
+    r.el = __float_as_int(wp[WARM_EL + gl]);
+    r.f[0].x = a.x; r.f[1].x = a.y; r.f[2].x = a.z; r.lam.x = a.w; r.f[0].y = b.x; r.f[1].y = b.y; r.f[2].y = b.z; r.lam.y = b.w;
+}
+DI void warm_store(float* wp, const int gl, const WarmRec<float>& r) {
+    *reinterpret_cast<float4*>(wp + WARM_F + 4 * gl) = make_float4(r.f[0], r.f[1], r.f[2], r.lam);
+    if (gl < MAXC) wp[WARM_EL + gl] = __int_as_float(r.el);
+}
+DI void warm_store(float* wp, const int gl, const WarmRec<v2f>& r) {
+    *reinterpret_cast<float4*>(wp + WARM_F + 4 * gl) = make_float4(r.f[0].x, r.f[1].x, r.f[2].x, r.lam.x);
+    *reinterpret_cast<float4*>(wp + WARM_F + 4 * (MAXC + gl)) = make_float4(r.f[0].y, r.f[1].y, r.f[2].y, r.lam.y);
+    wp[WARM_EL + gl] = __int_as_float(r.el);
+}
+// the rows of an environment whose episode begins: no kept contact (G lanes of a group; every word of the rows)
+template <int G> DI void warm_rows_clear(float* wp, const int gl) {
+    for (int v = gl; v < WARM_WORDS / 4; v += G) reinterpret_cast<float4*>(wp)[v] = (v < MAXC / 4) ? make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), __int_as_float(-1)) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
 template <int G>
 DI void contact_rows(float* lds, const int eb, const int gl, const DevModel& M, const DevCfg& C, const int nc, const int* cel, const float vz, ContactRows& P) {
 #define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
@@ -595,10 +627,12 @@ DI void contact_rows(float* lds, const int eb, const int gl, const DevModel& M, 
 
 // PRE: the arm-independent half of the rows comes from contact_rows (P); otherwise the whole set-up is formed here (vz and the records; P is not read) -- one
 // statement sequence for the kernels that do not split it: handing the rows through the struct cost the 16-lane split kernel 0.5 us per step.
-template <int G, bool PRE>
+// WR = WarmRec: the solve starts from the kept record `wr` of the lane (matched by element against this pass's contact list) and leaves the new one in it.
+template <int G, bool PRE, class WR>
 DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M, const DevCfg& C, const int nc, const int ncmax, const int* cel,
                       const float* Li, const float* alpha, const float* vs, const float mu, const float vz, const ContactRows& P, float* W, float* gf,
-                      unsigned long long* dbg) {
+                      unsigned long long* dbg, WR& wr) {
+    constexpr bool WARM = !std::is_same<WR, NoWarm>::value;
 #define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
     // ---- contact k lives in the registers of lane k of its group.  Set-up: row directions w, Lambda^-1 w, element
     //      coupling g, reference acceleration, regulariser; Km[c] = Linv[e_own][e_c] / m ----
@@ -810,6 +844,36 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
     if constexpr (CLONE) { ownv = own && (gl < 8 || pairB); muv = (gl < 8) ? mu : muB; }
     else { ownv = b2{own, own && pairB}; muv.x = mu; muv.y = muB; }
     fv[0] = fv[1] = fv[2] = V::splat(0.f);
+    int myel = -1;
+    if constexpr (WARM) {
+        // ---- warm start: the kept list goes through the environment's LDS block (words 0 .. 71, laid out as the warm rows; the Delassus records above have been
+        //      read by every lane), a lane finds its contact's element among the eight kept ones and takes that slot's force and multiplier.  No match, no contact:
+        //      zero, as in a cold start.
+        static_assert(std::is_same<WR, WarmRec<VT>>::value, "warm record of the mapping");
+        static_assert(WARM_WORDS <= GE_SD, "kept list overlays the rhs / staging area");
+        myel = own ? __float_as_int(EB(GE_CG + cl * CG_WORDS + 6)) : -1;
+        group_sync();
+        warm_store(&EB(0), gl, wr);
+        group_sync();
+        const float4 k0 = *reinterpret_cast<const float4*>(&EB(WARM_EL)), k1 = *reinterpret_cast<const float4*>(&EB(WARM_EL + 4));
+        const int kel[MAXC] = {__float_as_int(k0.x), __float_as_int(k0.y), __float_as_int(k0.z), __float_as_int(k0.w),
+                               __float_as_int(k1.x), __float_as_int(k1.y), __float_as_int(k1.z), __float_as_int(k1.w)};
+        int m = -1;
+#pragma unroll
+        for (int k = 0; k < MAXC; ++k) m = (own && kel[k] == myel) ? k : m;
+        const bool hit = m >= 0;
+        const int ms = hit ? m : 0;
+        if constexpr (CLONE) {
+            const float4 x = *reinterpret_cast<const float4*>(&EB(WARM_F + 4 * ((gl & 8) + ms)));
+            const bool take = hit && ownv;
+            fv[0] = take ? x.x : 0.f; fv[1] = take ? x.y : 0.f; fv[2] = take ? x.z : 0.f; lamv = take ? x.w : 0.f;
+        } else {
+            const float4 xa = *reinterpret_cast<const float4*>(&EB(WARM_F + 4 * ms)), xb = *reinterpret_cast<const float4*>(&EB(WARM_F + 4 * (MAXC + ms)));
+            const bool ta = hit && ownv.x, tb = hit && ownv.y;
+            fv[0].x = ta ? xa.x : 0.f; fv[1].x = ta ? xa.y : 0.f; fv[2].x = ta ? xa.z : 0.f; lamv.x = ta ? xa.w : 0.f;
+            fv[0].y = tb ? xb.x : 0.f; fv[1].y = tb ? xb.y : 0.f; fv[2].y = tb ? xb.z : 0.f; lamv.y = tb ? xb.w : 0.f;
+        }
+    }
     // the lane's own diagonal block, regulariser included
     if constexpr (!CLONE) {
 #pragma unroll
@@ -822,10 +886,60 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
         }
     }
     b00 += Rd[0]; b11 += Rd[1]; b22 += Rd[2];
+    // q = A D for the pairs' summed directions D (one per lane, D_k in lane k).  Up to four contacts: one running sum over them.  More: the sum over contacts 0-3 plus the
+    // sum over contacts 4-7 -- in that association in EVERY mapping (an environment's bits must not depend on its wave's neighbours: for one with at most four contacts
+    // the second sum is exact zeros) -- which a 16-lane group evaluates in its two halves at once: lanes 0-7 take D_j, lanes 8-15 D_(4+j) from the same row (two bank-masked
+    // broadcasts per word), each half multiplies with the four blocks it formed, one rotation by eight lanes adds the halves.  Eight contacts: 63 instructions instead of
+    // 96 (round 5), six: 63 / 72.  Used by every iteration and, with a warm start, once before them (A s0): one statement of the association for both
+    // (a macro, not a lambda: through a lambda the 8-lane split kernel of a cold handle spills one more register).
+#define USIM_DELASSUS_PRODUCT(D0, D1, D2, q0, q1, q2) \
+            if constexpr (NCM <= 4) { \
+_Pragma("unroll") \
+                for (int k = 0; k < NCM; ++k) { \
+                    const float e0 = group_bcast<G>(D0, k), e1 = group_bcast<G>(D1, k), e2 = group_bcast<G>(D2, k); \
+                    q0 = fmaf(B[k][0][2], e2, fmaf(B[k][0][1], e1, fmaf(B[k][0][0], e0, q0))); \
+                    q1 = fmaf(B[k][1][2], e2, fmaf(B[k][1][1], e1, fmaf(B[k][1][0], e0, q1))); \
+                    q2 = fmaf(B[k][2][2], e2, fmaf(B[k][2][1], e1, fmaf(B[k][2][0], e0, q2))); \
+                } \
+            } else if constexpr (CLONE) { \
+_Pragma("unroll") \
+                for (int j = 0; j < 4; ++j) { \
+                    const float e0 = half_bcast(D0, j), e1 = half_bcast(D1, j), e2 = half_bcast(D2, j); \
+                    q0 = fmaf(B[j][0][2], e2, fmaf(B[j][0][1], e1, fmaf(B[j][0][0], e0, q0))); \
+                    q1 = fmaf(B[j][1][2], e2, fmaf(B[j][1][1], e1, fmaf(B[j][1][0], e0, q1))); \
+                    q2 = fmaf(B[j][2][2], e2, fmaf(B[j][2][1], e1, fmaf(B[j][2][0], e0, q2))); \
+                } \
+                q0 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q0), 0x128, 0xf, 0xf, true)); \
+                q1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q1), 0x128, 0xf, 0xf, true)); \
+                q2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q2), 0x128, 0xf, 0xf, true)); \
+            } else { \
+                float h0 = 0.f, h1 = 0.f, h2 = 0.f; \
+_Pragma("unroll") \
+                for (int k = 0; k < NCM; ++k) { \
+                    const float e0 = group_bcast<G>(D0, k), e1 = group_bcast<G>(D1, k), e2 = group_bcast<G>(D2, k); \
+                    float& a0 = (k < 4) ? q0 : h0; float& a1 = (k < 4) ? q1 : h1; float& a2 = (k < 4) ? q2 : h2; \
+                    a0 = fmaf(B[k][0][2], e2, fmaf(B[k][0][1], e1, fmaf(B[k][0][0], e0, a0))); \
+                    a1 = fmaf(B[k][1][2], e2, fmaf(B[k][1][1], e1, fmaf(B[k][1][0], e0, a1))); \
+                    a2 = fmaf(B[k][2][2], e2, fmaf(B[k][2][1], e1, fmaf(B[k][2][0], e0, a2))); \
+                } \
+                q0 += h0; q1 += h1; q2 += h2; \
+            }
     auto iterations = [&](auto NCM_) {
         constexpr int NCM = decltype(NCM_)::value;
         const VT vb00 = V::splat(b00), vb01 = V::splat(b01), vb02 = V::splat(b02), vb11 = V::splat(b11), vb12 = V::splat(b12), vb22 = V::splat(b22);
         const VT vR0 = V::splat(Rd[0]), vR1 = V::splat(Rd[1]), vR2 = V::splat(Rd[2]);
+        if constexpr (WARM) {
+            // the shared residual at the kept forces: b + A s0, s0 = f_A + f_B per pair -- one product
+            float D0 = V::hsum(fv[0]), D1 = V::hsum(fv[1]), D2 = V::hsum(fv[2]);
+            if constexpr (CLONE) {
+                D0 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D0), 0x128, 0xf, 0xf, true));
+                D1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D1), 0x128, 0xf, 0xf, true));
+                D2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D2), 0x128, 0xf, 0xf, true));
+            }
+            float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+            USIM_DELASSUS_PRODUCT(D0, D1, D2, q0, q1, q2)
+            cres[0] += q0; cres[1] += q1; cres[2] += q2;
+        }
         for (int it = 0; it < C.pgs_iters; ++it) {
             VT dv[3];
             float num, D0, D1, D2;
@@ -847,42 +961,8 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
                 D1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D1), 0x128, 0xf, 0xf, true));
                 D2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D2), 0x128, 0xf, 0xf, true));
             }
-            // q = A D.  Up to four contacts: one running sum over them.  More: the sum over contacts 0-3 plus the sum over contacts 4-7 -- in that association in EVERY mapping
-            // (an environment's bits must not depend on its wave's neighbours: for one with at most four contacts the second sum is exact zeros) -- which a 16-lane group
-            // evaluates in its two halves at once: lanes 0-7 take D_j, lanes 8-15 D_(4+j) from the same row (two bank-masked broadcasts per word), each half multiplies with
-            // the four blocks it formed, one rotation by eight lanes adds the halves.  Eight contacts: 63 instructions instead of 96 (round 5), six: 63 / 72.
             float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-            if constexpr (NCM <= 4) {
-#pragma unroll
-                for (int k = 0; k < NCM; ++k) {
-                    const float e0 = group_bcast<G>(D0, k), e1 = group_bcast<G>(D1, k), e2 = group_bcast<G>(D2, k);
-                    q0 = fmaf(B[k][0][2], e2, fmaf(B[k][0][1], e1, fmaf(B[k][0][0], e0, q0)));
-                    q1 = fmaf(B[k][1][2], e2, fmaf(B[k][1][1], e1, fmaf(B[k][1][0], e0, q1)));
-                    q2 = fmaf(B[k][2][2], e2, fmaf(B[k][2][1], e1, fmaf(B[k][2][0], e0, q2)));
-                }
-            } else if constexpr (CLONE) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float e0 = half_bcast(D0, j), e1 = half_bcast(D1, j), e2 = half_bcast(D2, j);
-                    q0 = fmaf(B[j][0][2], e2, fmaf(B[j][0][1], e1, fmaf(B[j][0][0], e0, q0)));
-                    q1 = fmaf(B[j][1][2], e2, fmaf(B[j][1][1], e1, fmaf(B[j][1][0], e0, q1)));
-                    q2 = fmaf(B[j][2][2], e2, fmaf(B[j][2][1], e1, fmaf(B[j][2][0], e0, q2)));
-                }
-                q0 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q0), 0x128, 0xf, 0xf, true));
-                q1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q1), 0x128, 0xf, 0xf, true));
-                q2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q2), 0x128, 0xf, 0xf, true));
-            } else {
-                float h0 = 0.f, h1 = 0.f, h2 = 0.f;
-#pragma unroll
-                for (int k = 0; k < NCM; ++k) {
-                    const float e0 = group_bcast<G>(D0, k), e1 = group_bcast<G>(D1, k), e2 = group_bcast<G>(D2, k);
-                    float& a0 = (k < 4) ? q0 : h0; float& a1 = (k < 4) ? q1 : h1; float& a2 = (k < 4) ? q2 : h2;
-                    a0 = fmaf(B[k][0][2], e2, fmaf(B[k][0][1], e1, fmaf(B[k][0][0], e0, a0)));
-                    a1 = fmaf(B[k][1][2], e2, fmaf(B[k][1][1], e1, fmaf(B[k][1][0], e0, a1)));
-                    a2 = fmaf(B[k][2][2], e2, fmaf(B[k][2][1], e1, fmaf(B[k][2][0], e0, a2)));
-                }
-                q0 += h0; q1 += h1; q2 += h2;
-            }
+            USIM_DELASSUS_PRODUCT(D0, D1, D2, q0, q1, q2)
             float den = V::hsum(V::fma(dv[2], V::fma(vR2, dv[2], V::splat(q2)), V::fma(dv[1], V::fma(vR1, dv[1], V::splat(q1)), dv[0] * V::fma(vR0, dv[0], V::splat(q0)))));
             num = group_allsum<G>(num); den = group_allsum<G>(den);
             const float t = (den > 0.f) ? fminf(-num * rcp_(den), 1.f) : 0.f;
@@ -901,6 +981,8 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
         case 7: iterations(std::integral_constant<int, 7>{}); break;
         default: iterations(std::integral_constant<int, 8>{}); break;
     }
+#undef USIM_DELASSUS_PRODUCT
+    if constexpr (WARM) { wr.el = myel; wr.f[0] = fv[0]; wr.f[1] = fv[1]; wr.f[2] = fv[2]; wr.lam = lamv; }     // (a virtual contact that does not exist holds zeros)
     // the pair's total force (lanes 0-7 of a 16-lane group: contact A's own force plus contact B's from lane 8 + k)
     if constexpr (CLONE) {
 #pragma unroll

@@ -287,11 +287,12 @@ template <int G> constexpr int arm_share_num() { return 0; }     // quarters of 
 // registers it would be live across the whole step (the split kernel spills at 256 registers).
 constexpr int ARM_LDS_WORDS = A16_LANES * AT_STRIDE;
 template <int TORSO, int ROLE, int G> constexpr int arm_lds_base();
-template <int NE>
+template <int NE, class WR = NoWarm>
 struct Carry {
     float dqj, qdj, q0j;
     Episode ep;
     float s[NE], sd[NE];
+    WR wr;                                                               // kept contact list of the lane (warm start; NoWarm: nothing)
 };
 
 template <int TORSO, int ROLE, int G> constexpr int arm_lds_base() {
@@ -300,9 +301,14 @@ template <int TORSO, int ROLE, int G> constexpr int arm_lds_base() {
 static_assert((arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS) * 4 <= 160 * 1024 && arm_lds_base<1, 1, 8>() % 4 == 0 && arm_lds_base<1, 1, 16>() % 4 == 0 && arm_lds_base<1, 0, 16>() % 4 == 0
               && arm_lds_base<0, 0, 16>() % 4 == 0, "arm table behind the LDS blocks of every 16-lane kernel");
 
-template <int TORSO, int MODE, int ROLE, int NT, int G = 16, bool RES = false>
+template <int TORSO, int MODE, int ROLE, int NT, int G = 16, bool RES = false, class WR = NoWarm>
 DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __restrict__ st, const int n, const int npad, const DevIO& io, const int flags, const long long rstep,
-                   const bool first_pass, const int sub, int& nbar, Carry<TORSO ? (N_TOP + G - 1) / G : 1>& cy) {
+                   const bool first_pass, const int sub, int& nbar, Carry<TORSO ? (N_TOP + G - 1) / G : 1, WR>& cy) {
+    // warm start of the contact solve (WR = WarmRec): the side that solves the contacts loads the lane's record of the kept list with the state, hands it to
+    // contact_solve and stores the new one with the lattice; the side that restarts an episode clears the environment's warm rows
+    constexpr bool WARM = !std::is_same<WR, NoWarm>::value;
+    // (MODE 1, the reset launch of such a handle: its zero-torque forward pass solves cold and keeps nothing; it clears the rows of the environments it resets)
+    static_assert(!WARM || (TORSO == 1 && ROLE == 0) || (TORSO == 1 && MODE == 0), "warm start: the soft-torso kernels");
     constexpr int WPR = (ROLE != 0) ? wpr<G>() : 4;
     constexpr int EPW = 64 / G, EPB = WPR * EPW;                        // environments per wave / per workgroup (WPR waves per role)
     static_assert(!RES || MODE == 0, "resident state: step launches only");
@@ -338,6 +344,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     const int ei = valid ? env : (refill ? 0 : n - 1);              // clamp so that every lane has something to read; stores are guarded
 #define LAT(w) st[(size_t)F_LAT * npad + (size_t)ei * LAT_ENV_WORDS + (w)]
 #define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
+    float* const warm_rows = st + warm_index(io.bank_row0, npad, (size_t)ei);      // (dereferenced by handles with warm rows only)
     // The mailbox block sits beyond the 64 KB an LDS instruction's immediate offset reaches.  Left to itself the compiler forms one address register per mailbox WORD
     // (block + constant, hoisted out of the step loop) and spills them around the contact solve: 74 registers, two scratch round trips per step in the resident
     // kernel.  The block's offset is therefore made opaque: one address register, the words at immediate offsets from it.
@@ -408,6 +415,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             if (TORSO && MODE == 0 && ROLE != 1 && e < N_TOP) { s_pre[i] = LAT(LAT_S + e); sd_pre[i] = LAT(LAT_SD + e); }
             if (TORSO && MODE == 0 && ROLE == 1 && e < N_TOP) s_pre[i] = LAT(LAT_S + e);      // the arm side runs the broad phase of the collision
         }
+        if constexpr (WARM && MODE == 0 && ROLE != 1) warm_load(warm_rows, gl, cy.wr);
     } else if constexpr (RES && ROLE == 1) {
         // resident launch, arm side: the element positions the lattice side integrated (or the zeros this side left for a new episode) are in
         // the environment's LDS block
@@ -420,6 +428,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             kst = nx.x; kdmp = nx.y; mu = nx.z; t = 0;
 #pragma unroll
             for (int i = 0; i < NE; ++i) { s_pre[i] = 0.f; sd_pre[i] = 0.f; }
+            warm_clear(cy.wr);                                           // an episode starts cold
         }
     }
     if (!jlane) { dqj = 0.f; qdj = 0.f; q0j = 0.f; }
@@ -556,9 +565,9 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
                 for (int b = 0; b <= a; ++b) Lp[PK(a, b)] = mb[MB_OP + a * 8 + b];
             }
             XSTAMP(2);
-            contact_solve<G, EARLY>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, P, W, gf, dbg);
+            contact_solve<G, EARLY>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, P, W, gf, dbg, cy.wr);
             XSTAMP(3);
-        }
+        } else warm_clear(cy.wr);                                        // (no contact in the wave: nothing kept)
         if (gl == 0) {
             *reinterpret_cast<float4*>(&mb[MB_W]) = make_float4(W[0], W[1], W[2], W[3]);
             *reinterpret_cast<float4*>(&mb[MB_W + 4]) = make_float4(W[4], W[5], __int_as_float(nc), __int_as_float(overflow));
@@ -590,6 +599,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
                 if (valid) { LAT(LAT_SD + e) = sdn; LAT(LAT_S + e) = sn; }
                 if constexpr (RES) { sd_pre[i] = sdn; s_pre[i] = sn; EB(GE_S + e) = sn; }     // resident launch: the next step's state; positions for the arm side's broad phase
             }
+            if constexpr (WARM) { if (valid) warm_store(warm_rows, gl, cy.wr); }
         }
         RSTAMP(7);
         USIM_BAR();                                                 // (4) lattice stored: the arm side may now zero it for an episode that ended
@@ -1037,12 +1047,16 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
                 for (int b = 0; b <= a; ++b) Lp[PK(a, b)] = rbc<G, TASK_LANE[a]>(Li[b]);
             });
             USIM_STAMP(dbg, 8);
-            contact_solve<G, false>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, ContactRows{}, W, gf, dbg);
-        }
+            if constexpr (MODE == 0) contact_solve<G, false>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, ContactRows{}, W, gf, dbg, cy.wr);
+            else { NoWarm cold; contact_solve<G, false>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, ContactRows{}, W, gf, dbg, cold); }
+        } else warm_clear(cy.wr);                                        // (no contact in the wave: nothing kept)
         USIM_STAMP(dbg, 11);
         // ---- element accelerations a = a~ + Linv[:, e_c] gf_c, semi-implicit Euler, write back (a reset leaves the lattice at rest) ----
         if constexpr (MODE == 1) {
-            if (valid && need && !refill) for (int e = gl; e < N_TOP; e += G) { LAT(LAT_S + e) = 0.f; LAT(LAT_SD + e) = 0.f; }
+            if (valid && need && !refill) {
+                for (int e = gl; e < N_TOP; e += G) { LAT(LAT_S + e) = 0.f; LAT(LAT_SD + e) = 0.f; }
+                if constexpr (WARM) warm_rows_clear<G>(warm_rows, gl);    // an episode starts cold
+            }
         } else {
             float acc_e[NE];
 #pragma unroll
@@ -1066,6 +1080,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
                 if (valid) { LAT(LAT_SD + e) = sdn; LAT(LAT_S + e) = sn; }
                 if constexpr (RES) { sd_pre[i] = sdn; s_pre[i] = sn; }
             }
+            if constexpr (WARM) { if (valid) warm_store(warm_rows, gl, cy.wr); }
         }
 #pragma unroll
         for (int k = 0; k < MAXC; ++k) con_shell[k] = (k < nc) ? tb_shell[cel[k]] : -1;
@@ -1222,6 +1237,12 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = BK(sl, BOBS + a);
         }
         if (TORSO && valid) for (int e = gl; e < N_TOP; e += G) { LAT(LAT_S + e) = 0.f; LAT(LAT_SD + e) = 0.f; }
+        if constexpr (WARM) {
+            // an episode starts cold: the warm rows (after hand-off (4) in the split kernel: the lattice side has stored this step's list) and, where this wave
+            // solves the contacts itself, its record (the lattice side of a resident launch learns of the new episode through the mailbox)
+            if (valid) warm_rows_clear<G>(warm_rows, gl);
+            warm_clear(cy.wr);
+        }
         if constexpr (RES && TORSO != 0) {
             // resident launch: the lattice of the new episode is at rest in the registers too (single wave) / in the LDS copy of the element
             // positions this side reads back at the next step (split kernel; the lattice side learns of it through the mailbox below)
@@ -1271,7 +1292,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 // One launch = io.nsub consecutive steps (usim_rollout_random: the actions are drawn in-kernel, so step k + 1 needs nothing from the host).
 // The lattice tables stay in LDS, launch latency and the kernel-argument / first-load round trip are paid once; every step still reads its
 // state from HBM and writes it back together with its slice of the transition block, so the algorithmic traffic per step is unchanged.
-template <int TORSO, int MODE, int ROLE, int NT, bool MULTI = false, int G = 16>
+template <int TORSO, int MODE, int ROLE, int NT, bool MULTI = false, int G = 16, class WR = NoWarm>
 DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __restrict__ st, const int n, const int npad, const DevIO& io0, const int flags, const long long rstep) {
     // (MULTI is a template parameter: the single-step instantiation -- usim_step, a policy in the loop -- keeps the register allocation of a
     // straight-line kernel; the loop costs it 2 us per step)
@@ -1280,11 +1301,11 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
     const int nsub = (MULTI && MODE == 0) ? (io0.nsub > 1 ? io0.nsub : 1) * S : 1;
     DevIO io = io0;
     int nbar = 0;                                                        // barriers executed by this wave (read by the profiling build only)
-    Carry<TORSO ? (N_TOP + G - 1) / G : 1> cy;                           // multi-step launches: the state stays in registers between the steps
+    Carry<TORSO ? (N_TOP + G - 1) / G : 1, WR> cy;                        // multi-step launches: the state stays in registers between the steps
     int sub = 0;
     long long cstep = rstep;                                             // control step: keys the in-kernel action draw
     for (int ks = 0; ks < nsub; ++ks) {
-        step16_one<TORSO, MODE, ROLE, NT, G, MULTI && MODE == 0>(lds, M, C, st, n, npad, io, flags, cstep, ks == 0, sub, nbar, cy);
+        step16_one<TORSO, MODE, ROLE, NT, G, MULTI && MODE == 0, WR>(lds, M, C, st, n, npad, io, flags, cstep, ks == 0, sub, nbar, cy);
         const bool ctrl_done = sub == S - 1;                             // this pass completed a control step
         if (ctrl_done) { sub = 0; ++cstep; } else ++sub;
         if (ks + 1 < nsub) {
@@ -1305,11 +1326,11 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
 #endif
 }
 
-template <int TORSO, int OCC, int MODE, bool MULTI = false>
+template <int TORSO, int OCC, int MODE, bool MULTI = false, bool WARM = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void usim_step16_kernel(const DevModel M, const DevCfg C, float* __restrict__ st, int n, int npad,
                                                                                                           const DevIO io, int flags, long long rstep) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    step16_body<TORSO, MODE, 0, 256, MULTI>(lds, M, C, st, n, npad, io, flags, rstep);
+    step16_body<TORSO, MODE, 0, 256, MULTI, 16, typename std::conditional<WARM, WarmOf<16>::type, NoWarm>::type>(lds, M, C, st, n, npad, io, flags, rstep);
 }
 
 // soft-torso step with two waves per quad of environments: waves 0-3 of the workgroup run the arm side, waves 4-7 the lattice / contact side
@@ -1322,7 +1343,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // tests/test_gpu_properties.py compares them; the split-vs-single-wave bit-exactness tests cover ragged workgroups and slot overflow.
 // G = 16: 16 environments per workgroup (a quad per wave pair).  G = 8: 32 environments per workgroup (eight per wave pair; two per DPP row) -- the
 // mapping for more than 4096 envs/GPU, where 16-lane groups would need a second round of workgroups.
-template <bool MULTI, int G = 16>
+template <bool MULTI, int G = 16, bool WARM = false>
 __global__ __launch_bounds__(128 * wpr<G>()) __attribute__((amdgpu_waves_per_eu(2, 2))) void usim_step32_kernel(const DevModel* __restrict__ Mp, const DevCfg* __restrict__ Cp, float* __restrict__ st, int n, int npad,
                                                                                                                   const DevIO io, int flags, long long rstep) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1333,8 +1354,9 @@ __global__ __launch_bounds__(128 * wpr<G>()) __attribute__((amdgpu_waves_per_eu(
     constexpr int NT = 128 * wpr<G>();
     // (two workgroups per CU: the role order alternates with a bit of the workgroup index, so that a SIMD holds an arm wave of one and a lattice wave of the other)
     const bool flip = USIM_ROLE_FLIP_BIT >= 0 && ((blockIdx.x >> (USIM_ROLE_FLIP_BIT >= 0 ? USIM_ROLE_FLIP_BIT : 0)) & 1);
-    if ((threadIdx.x < NT / 2) != flip) step16_body<1, 0, 1, NT, MULTI, G>(lds, M, C, st, n, npad, io, flags, rstep);
-    else step16_body<1, 0, 2, NT, MULTI, G>(lds, M, C, st, n, npad, io, flags, rstep);
+    typedef typename std::conditional<WARM, typename WarmOf<G>::type, NoWarm>::type WR;
+    if ((threadIdx.x < NT / 2) != flip) step16_body<1, 0, 1, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
+    else step16_body<1, 0, 2, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
 }
 
 }  // namespace usim

@@ -368,9 +368,20 @@ class UltrasoundVecEnv:
             self._check(self.lib.usim_get_body_state(self._handle, body.ctypes.data))
             st["body"] = body[:, :13].copy()
             st["solver_warm_start"] = body[:, 13:].copy()                                          # the contact forces of the previous physics step (the solve's initial guess)
+        elif self.lib.usim_has_warm_start(self._handle) == 1:         # top-face torso with warm_start on: the solver's kept contact list
+            warm = np.zeros((self.num_envs, _lib.WARM_WORDS), dtype=np.float32)
+            self._check(self.lib.usim_get_warm_start(self._handle, warm.ctypes.data))
+            st["solver_warm_start"] = warm
         return st
 
     def set_state(self, st):
+        # the kept contact list of a top-face handle with warm_start on: checked before anything is written.  A handle without a warm start does not use the list
+        # (every solve starts from zero): a checkpoint of a warm run loads into it without the key's content
+        warm = None
+        if self.num_elements != 270 and "solver_warm_start" in st and self.lib.usim_has_warm_start(self._handle) == 1:
+            warm = np.ascontiguousarray(st["solver_warm_start"], dtype=np.float32)
+            if warm.shape != (self.num_envs, _lib.WARM_WORDS):
+                raise ValueError(f"solver_warm_start must have shape {(self.num_envs, _lib.WARM_WORDS)}, got {warm.shape}")
         sc = np.zeros((self.num_envs, _lib.NSCALAR), dtype=np.float32)
         lat = np.zeros((self.num_envs, max(self.num_elements, 1), 2), dtype=np.float32)
         for k, v in self._FIELDS.items():
@@ -382,6 +393,8 @@ class UltrasoundVecEnv:
             body = np.ascontiguousarray(np.concatenate([np.asarray(st["body"], dtype=np.float64), np.asarray(st["solver_warm_start"], dtype=np.float64)], axis=1))
             self._check(self.lib.usim_set_body_state(self._handle, body.ctypes.data))
         self._check(self.lib.usim_set_state(self._handle, sc.ctypes.data, lat.ctypes.data))
+        if warm is not None:                                          # (usim_set_state has emptied the kept list: without the key the next solve starts cold)
+            self._check(self.lib.usim_set_warm_start(self._handle, warm.ctypes.data))
 
 
 class UltrasoundEnv:

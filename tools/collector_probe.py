@@ -1,6 +1,6 @@
 """Policy in the loop: env-steps/s of policy.collect_rollouts (eager, ~40 launches per step from Python) against policy.GraphedCollector (the same
-rollout recorded once as a HIP graph), and that the two produce the same buffer.   usage: python tools/collector_probe.py [n_envs] [T] [repeats]"""
-import importlib, sys, time
+rollout recorded once as a HIP graph), and that the two produce the same buffer.   usage: [USIM_ENV_KWARGS='{"warm_start": 1, "pgs_iters": 18}'] python tools/collector_probe.py [n_envs] [T] [repeats]"""
+import importlib, json, os, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -12,15 +12,16 @@ T = int(sys.argv[2]) if len(sys.argv) > 2 else 128
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 dev = torch.device("cuda:0")
 
+EXTRA = json.loads(os.environ.get("USIM_ENV_KWARGS", "{}"))      # native options of the environment, e.g. '{"warm_start": 1, "pgs_iters": 18}'
+
 def make():
     torch.manual_seed(0)
-    env = usim.UltrasoundVecEnv(n, device="cuda:0", seed=3, **usim.default_robosuite_kwargs())
+    env = usim.UltrasoundVecEnv(n, device="cuda:0", seed=3, **usim.default_robosuite_kwargs(), **EXTRA)
     policy = pol.MlpActorCritic(19, env.action_dim).to(dev)
     vn = pol.DeviceVecNormalize(n, 19, device=dev, training=True, norm_reward=True)
     buf = pol.DeviceRolloutBuffer(T, n, 19, env.action_dim, device=dev)
     return env, policy, vn, buf
 
-import os
 FUSED_ONLY = bool(os.environ.get('FUSED_ONLY'))
 # --- same numbers?  (default generator re-seeded identically; the graphed collector runs `warmup_steps` eager steps first, so does the eager side)
 if not FUSED_ONLY:

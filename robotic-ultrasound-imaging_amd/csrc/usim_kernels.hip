@@ -1,7 +1,7 @@
 // usim_kernels.hip -- CDNA4 (gfx950) device code of the batched Ultrasound simulator; the translation unit is usim_api.hip, which includes it.
 //
 // This file holds
-//   - the lattice and contact phases of the soft torso (lattice_front, collide_*, contact_rows / contact_solve), which the 16-lane step kernels
+//   - the lattice and contact phases of the soft torso (lattice_rhs, lattice_solve, collide_*, contact_overflow, contact_rows / contact_solve), which the 16-lane step kernels
 //     of usim_step16.h (rigid and soft torso, included at the end) call;
 //   - usim_step_kernel<2, 64, MODE>, the step / reset kernel of the full torso (physics in usim_full.h);
 //   - usim_bank_items_kernel (refill work list of the reset / set_state paths) and usim_random_actions_kernel (the synthetic actions).
@@ -114,7 +114,9 @@ DI float half_bcast(float v, int J) {
     return __int_as_float(r);
 }
 
-// phase timeline probe (diagnostics only; profiling build): wave 0 of workgroup 0 stamps the shader clock when a buffer is given
+// Phase timeline probe (diagnostics only): wave 0 of workgroup 0 stamps the shader clock when a buffer is given.  The stamps exist only in the profiling
+// build (make prof -> libusim_prof.so): each one is a branch, and sixteen of them cost the production kernel 2 % (25.6 vs 25.1 us/step).  -DUSIM_TSTAMP_NOWAIT (what
+// `make prof` sets) keeps the stamps from draining memory traffic; -DUSIM_TSTAMP waits for it first.
 #if !defined(USIM_TSTAMP) && !defined(USIM_TSTAMP_NOWAIT)
 #define USIM_STAMP(dbg, k) do { } while (0)
 #elif defined(USIM_TSTAMP_NOWAIT)
@@ -222,219 +224,187 @@ DI bool collide_cull(const float* lds, const int e, const DevModel& M, const Dev
     return dot(v, v) < C.probe_cull2;
 }
 template <int G>
-DI void collide_queue(const float* lds, const float* queue, const int q0, const int q1, float* recs, const int gl, const int gbase, const DevModel& M, const DevCfg& C,
+DI void collide_queue(const float* lds, const float* queue, const int nq, float* recs, const int gl, const int gbase, const DevModel& M, const DevCfg& C,
                       const float* s_lds, const float dz, const f3 Kx, const f3 Ksx, const f3 Ksy, const f3 Ksz, int& nc) {
-    for (int j0 = q0; __any(j0 < q1); j0 += G) {
+    for (int j0 = 0; __any(j0 < nq); j0 += G) {
         const int j = j0 + gl;
-        const bool valid = j < q1;
+        const bool valid = j < nq;
         const int e = valid ? __float_as_int(queue[j]) : 0;
         collide_elem<G>(lds, recs, valid, e, gl, gbase, M, C, s_lds[e], dz, Kx, Ksx, Ksy, Ksz, nc);
     }
 }
 
-// More penetrating elements than contact slots (rare in a mixed batch, common right after a synchronous reset): keep the MAXC deepest of the
-// first MAXCAND candidates (ties keep the lower id), list still in ascending shell id.  The caller clamps its count to MAXC afterwards.
+#define EBF(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
+
+// More penetrating elements than contact slots (rare in a mixed batch, common right after a synchronous reset: 4 % of the environments): keep the MAXC
+// deepest of the first MAXCAND candidates (ties keep the lower id), list still in ascending shell id.  The caller clamps its count to MAXC afterwards.
 template <int G>
 DI void contact_overflow(float* lds, const int eb, const int gl, const int gbase, const int nc) {
-#define EBF(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
     if (nc > MAXC) {
-                        // more penetrating elements than contact slots (rare in a mixed batch, common right after a synchronous reset: 4 % of
-                        // the environments).  Keep the MAXC deepest of the first MAXCAND candidates (ties keep the lower id), list still in
-                        // ascending shell id.
-                        group_sync();
-                        if constexpr (G == 16) {
-                            // one candidate per lane of the group: rank by depth with sixteen row broadcasts, compact with a ballot
-                            const int m = nc < MAXCAND ? nc : MAXCAND;
-                            const bool cand = gl < m;
-                            const float4* rec = reinterpret_cast<const float4*>(&EBF(GE_CG + gl * CG_WORDS));
-                            const float4 r0 = rec[0], r1 = rec[1];
-                            const float d = cand ? r1.w : 1.0f;
-                            int rank = 0;
+        group_sync();
+        if constexpr (G == 16) {
+            // one candidate per lane of the group: rank by depth with sixteen row broadcasts, compact with a ballot
+            const int m = nc < MAXCAND ? nc : MAXCAND;
+            const bool cand = gl < m;
+            const float4* rec = reinterpret_cast<const float4*>(&EBF(GE_CG + gl * CG_WORDS));
+            const float4 r0 = rec[0], r1 = rec[1];
+            const float d = cand ? r1.w : 1.0f;
+            int rank = 0;
 #define USIM_RANK_STEP(I) { const float di = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(d), 0x150 + I, 0xf, 0xf, true)); \
-                            rank += (di < d || (di == d && I < gl)) ? 1 : 0; }
-                            USIM_RANK_STEP(0) USIM_RANK_STEP(1) USIM_RANK_STEP(2) USIM_RANK_STEP(3) USIM_RANK_STEP(4) USIM_RANK_STEP(5) USIM_RANK_STEP(6) USIM_RANK_STEP(7)
-                            USIM_RANK_STEP(8) USIM_RANK_STEP(9) USIM_RANK_STEP(10) USIM_RANK_STEP(11) USIM_RANK_STEP(12) USIM_RANK_STEP(13) USIM_RANK_STEP(14) USIM_RANK_STEP(15)
+                                rank += (di < d || (di == d && I < gl)) ? 1 : 0; }
+            USIM_RANK_STEP(0) USIM_RANK_STEP(1) USIM_RANK_STEP(2) USIM_RANK_STEP(3) USIM_RANK_STEP(4) USIM_RANK_STEP(5) USIM_RANK_STEP(6) USIM_RANK_STEP(7)
+            USIM_RANK_STEP(8) USIM_RANK_STEP(9) USIM_RANK_STEP(10) USIM_RANK_STEP(11) USIM_RANK_STEP(12) USIM_RANK_STEP(13) USIM_RANK_STEP(14) USIM_RANK_STEP(15)
 #undef USIM_RANK_STEP
-                            const bool keep = cand && rank < MAXC;
-                            const unsigned gm = (unsigned)(__ballot(keep) >> gbase) & 0xffffu;
-                            const int slot = __popc(gm & ((1u << gl) - 1u));
-                            group_sync();                                  // every record is in registers before any slot is overwritten
-                            if (keep) {
-                                float4* dst = reinterpret_cast<float4*>(&EBF(GE_CG + slot * CG_WORDS));
-                                dst[0] = r0; dst[1] = r1;
-                            }
-                        } else if (gl == 0) {
-                            // (8 lanes per environment: one lane of the group edits the records in place)
-                            const int m = nc < MAXCAND ? nc : MAXCAND;
-                            for (int drop = m - MAXC; drop > 0; --drop) {
-                                int worst = 0; float wd = -1.0e30f;
-                                for (int j = 0; j < m; ++j) {
-                                    const float dj = EBF(GE_CG + j * CG_WORDS + 7);
-                                    if (dj < 0.f && dj >= wd) { wd = dj; worst = j; }
-                                }
-                                EBF(GE_CG + worst * CG_WORDS + 7) = 1.0f;                       // dropped
-                            }
-                            int wpos = 0;
-                            for (int j = 0; j < m; ++j) {
-                                if (EBF(GE_CG + j * CG_WORDS + 7) < 0.f) {
-                                    if (wpos != j)
-                                        for (int a = 0; a < CG_WORDS; ++a) EBF(GE_CG + wpos * CG_WORDS + a) = EBF(GE_CG + j * CG_WORDS + a);
-                                    ++wpos;
-                                }
-                            }
-                        }
-                    }
-#undef EBF
+            const bool keep = cand && rank < MAXC;
+            const unsigned gm = (unsigned)(__ballot(keep) >> gbase) & 0xffffu;
+            const int slot = __popc(gm & ((1u << gl) - 1u));
+            group_sync();                                  // every record is in registers before any slot is overwritten
+            if (keep) {
+                float4* dst = reinterpret_cast<float4*>(&EBF(GE_CG + slot * CG_WORDS));
+                dst[0] = r0; dst[1] = r1;
+            }
+        } else if (gl == 0) {
+            // (8 lanes per environment: one lane of the group edits the records in place)
+            const int m = nc < MAXCAND ? nc : MAXCAND;
+            for (int drop = m - MAXC; drop > 0; --drop) {
+                int worst = 0; float wd = -1.0e30f;
+                for (int j = 0; j < m; ++j) {
+                    const float dj = EBF(GE_CG + j * CG_WORDS + 7);
+                    if (dj < 0.f && dj >= wd) { wd = dj; worst = j; }
+                }
+                EBF(GE_CG + worst * CG_WORDS + 7) = 1.0f;                       // dropped
+            }
+            int wpos = 0;
+            for (int j = 0; j < m; ++j) {
+                if (EBF(GE_CG + j * CG_WORDS + 7) < 0.f) {
+                    if (wpos != j)
+                        for (int a = 0; a < CG_WORDS; ++a) EBF(GE_CG + wpos * CG_WORDS + a) = EBF(GE_CG + j * CG_WORDS + a);
+                    ++wpos;
+                }
+            }
+        }
+    }
 }
 
-// Lattice front end of one forward pass, executed by the G lanes of a group on the group's LDS block: stage (s, sdot), build
-// the right-hand side of the soft-equality system, a~ = Linv rhs, collide the probe capsule with the 99 cap spheres and
-// leave the contact records (ascending shell id; the MAXC deepest when more were found) in LDS.  Returns the number found (may exceed MAXC).
-// PART 0: everything; 1: staging + right-hand side only (needs no arm quantity); 2: solve + collision only (after a PART 1 call); 3: solve only
-// (needs no arm quantity either: the split kernel's lattice side runs it while it would otherwise wait for the site pose); 4: collision only (after PART 3).
-template <int G, int NE, int PART = 0, bool QM = false>
-DI int lattice_front(float* lds, const int eb, const int gl, const int gbase, const DevModel& M, const DevCfg& C, const int tsim,
-                     const float kst, const float kdmp, const bool live, const float* s_pre, const float* sd_pre,
-                     const f3 Kx, const f3 Ksy, const f3 Ksz, unsigned long long* dbg, const float* queue = nullptr, const int q0 = 0, const int q1 = 0) {
-#if !defined(USIM_TSTAMP) && !defined(USIM_TSTAMP_NOWAIT)
-#define LSTAMP(k) do { } while (0)
-#else
-#define LSTAMP(k) do { if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[k] = __builtin_readcyclecounter(); } while (0)
-#endif
-#define EBF(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
-    float dz, vz, az;
-    torso_motion(C, tsim, dz, vz, az);
-                    if constexpr (PART == 0 || PART == 1) {
-                                    // ---- stage s, sdot and the spring-damper potential u = k_t s + b_t sdot: lane gl of the group owns elements
-                    //      gl, gl+G, ...  u goes into a zero-bordered 11 x 13 copy of the 9 x 11 grid, so that the four neighbours of an
-                    //      element are four unconditional reads; a pinned rim neighbour (s = 0) is a border cell.
-                    // (the loads of s, sdot were issued together with the scalar state at the top of the kernel)
-                    const float kfix = 1.0f / (SI_DMAX * SR_TC * SR_TC), bfix = 2.0f / (SI_DMAX * SR_TC);
-                    const float kten = kst * (1.0f / SI_DMAX), bten = kdmp * (1.0f / SI_DMAX);
-                    {
-                        float4* uz = reinterpret_cast<float4*>(&EBF(GE_U));
-    #pragma unroll
-                        for (int v = gl; v < GE_U_WORDS / 4; v += G) uz[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-                    int up[NE];
-                    float u_own[NE];
-    #pragma unroll
-                    for (int i = 0; i < NE; ++i) {
-                        const int e = gl + i * G;
-                        const int ix = (e * 373) >> 12, iz = e - LAT_NC * ix;            // e / 11 for e < 682
-                        up[i] = (ix + 1) * (LAT_NC + 2) + iz + 1;
-                        const float se = live ? s_pre[i] : 0.f, sde = live ? sd_pre[i] : 0.f;
-                        u_own[i] = fmaf(kten, se, bten * sde);
-                        if (e < N_TOP) { EBF(GE_SD + e) = sde; EBF(GE_U + up[i]) = u_own[i]; }     // (s itself stays in the owner's registers)
-                    }
-                    group_sync();
-                                    // ---- lattice right-hand side: a_s + w_fix aref_fix + w_ten sum_j aref_ij
-                    //      = a_s - w_fix (k_fix s + b_fix sdot) - w_ten (deg u - sum of the four neighbour cells), deg = 4 (3 at the corners) ----
-    #pragma unroll
-                    for (int i = 0; i < NE; ++i) {
-                        const int e = gl + i * G;
-                        if (e >= N_TOP) continue;
-                        const float se = live ? s_pre[i] : 0.f, sde = live ? sd_pre[i] : 0.f;
-                        const float* uc = &EBF(GE_U + up[i]);
-                        const float nb = (uc[-1] + uc[1]) + (uc[-(LAT_NC + 2)] + uc[LAT_NC + 2]);
-                        const bool corner = (e == 0) | (e == LAT_NC - 1) | (e == N_TOP - LAT_NC) | (e == N_TOP - 1);
-                        float r = -(GRAV + az) * lds[TB_AXIS + 3 * e + 2] - M.wfix * fmaf(bfix, sde, kfix * se);
-                        r = fmaf(-M.wten, fmaf(corner ? 3.f : 4.f, u_own[i], -nb), r);
-                        EBF(GE_X + e) = r;
-                    }
-                    if (gl == 0) EBF(GE_X + N_TOP) = 0.f;          // pad word read by the 16-byte row chunks
-                    group_sync();
-                    }
-                    if constexpr (PART == 1) return 0;
-                    LSTAMP(5);
-                                    // ---- collision: seven rounds of one element per lane (collide_elem), scheduled between the pieces of the matrix-core
-                    //      solve below -- or, in the split kernel (QM), this wave's share [q0, q1) of the broad phase's queue (collide_cull / collide_queue;
-                    //      the arm wave, which has the site pose first, builds the queue and takes the other share; the two hit lists are merged
-                    //      after hand-off (2)) ----
-                    const f3 Ksx = cross(Ksy, Ksz);
-                    int nc = 0;
-                    // single-wave kernels: broad phase and narrow phase in one go -- element positions into the environment's LDS block, the ids
-                    // that pass collide_cull (ascending) into a queue that overlays the a~ area (free until the solve stores its result), then the
-                    // queue G elements at a time.  Same per-element arithmetic and the same ballot slots as walking all rounds.
-                    auto collide_all = [&]() {
-                        float* const q = &EBF(GE_A);
-                        int nq = 0;
+// The lattice phases of one forward pass, executed by the G lanes of a group on the group's LDS block.  Lane gl of the group owns elements gl, gl + G, ...
+// (NE of them); az is the acceleration of the torso base (torso_motion), live = false puts the lattice at rest (reset computation).
+//
+// lattice_rhs: stage sdot and the spring-damper potential, build the right-hand side of the soft-equality system.  Needs no arm quantity.
+template <int G, int NE>
+DI void lattice_rhs(float* lds, const int eb, const int gl, const DevModel& M, const float az, const float kst, const float kdmp, const bool live,
+                    const float* s_pre, const float* sd_pre) {
+    // ---- stage sdot and the spring-damper potential u = k_t s + b_t sdot.  u goes into a zero-bordered 11 x 13 copy of the 9 x 11 grid, so that the four
+    //      neighbours of an element are four unconditional reads; a pinned rim neighbour (s = 0) is a border cell.
+    //      (the loads of s, sdot were issued together with the scalar state at the top of the kernel) ----
+    const float kfix = 1.0f / (SI_DMAX * SR_TC * SR_TC), bfix = 2.0f / (SI_DMAX * SR_TC);
+    const float kten = kst * (1.0f / SI_DMAX), bten = kdmp * (1.0f / SI_DMAX);
+    {
+        float4* uz = reinterpret_cast<float4*>(&EBF(GE_U));
 #pragma unroll
-                        for (int i = 0; i < NE; ++i) {
-                            const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
-                            const float se = live ? s_pre[i] : 0.f;
-                            if (eraw < N_TOP) EBF(GE_S + eraw) = se;
-                            const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, se, dz, Kx, Ksx, Ksz);
-                            const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & ((1u << G) - 1u);
-                            if (cand) q[nq + __popc(gm & ((1u << gl) - 1u))] = __int_as_float(e);
-                            nq += __popc(gm);
-                        }
-                        group_sync();
-                        collide_queue<G>(lds, q, 0, nq, &EBF(GE_CG), gl, gbase, M, C, &EBF(GE_S), dz, Kx, Ksx, Ksy, Ksz, nc);
-                        group_sync();                                      // the queue area is rewritten by the solve's result
-                    };
-                    auto collide_round = [&](const int i) {
-                        if (i != 0 || PART == 3) return;
-                        if constexpr (QM) collide_queue<G>(lds, queue, q0, q1, &EBF(GE_CG), gl, gbase, M, C, &EBF(GE_S), dz, Kx, Ksx, Ksy, Ksz, nc);
-                        else collide_all();
-                    };
-                                    // ---- a~ = Linv * rhs ----
-                    if constexpr (PART == 4) {
-                        collide_round(0);
-                    } else {
-                        // Matrix-core form (every lane of the wave is active here): the wave's environments are the columns of one dense
-                        // product A~[99 x EPW] = Linv[99 x 100] X[100 x EPW], issued as v_mfma_f32_4x4x1 (16 blocks of 4 rows x 4 columns
-                        // per instruction).  Lane l feeds Linv row l (and row 64 + l) as the A operand and the rhs of environment l % 4 as
-                        // the B operand; it receives rows 4 (l / 4) .. + 3 of that environment (layout: tools/probe/mfma_4x4x1_layout.hip).
-                        // The k loop is unrolled in NE pieces with one collision round after each: the rounds do not depend on the
-                        // product and fill the issue slots the matrix pipeline leaves free.
-                        typedef float v4f __attribute__((ext_vector_type(4)));
-                        constexpr int EPW = 64 / G, NSET = (EPW >= 4 && EPW <= 8) ? EPW / 4 : 1, NCH = LROW / 4;
-                        const int lane = gbase + gl, ebw = eb - gbase / G, blk = lane >> 2;
-                        const int r1 = (64 + lane < N_TOP) ? 64 + lane : N_TOP - 1;
-                        const float4* la0 = reinterpret_cast<const float4*>(&lds[TB_LINV + lane * LROW]);
-                        const float4* la1 = reinterpret_cast<const float4*>(&lds[TB_LINV + r1 * LROW]);
-                        const float4* xb[NSET];
-                        v4f acc0[NSET], acc1[NSET];
-    #pragma unroll
-                        for (int u = 0; u < NSET; ++u) {
-                            xb[u] = reinterpret_cast<const float4*>(&lds[TB_WORDS + (ebw + 4 * u + (lane & 3)) * GE_STRIDE + GE_X]);
-                            acc0[u] = (v4f){0.f, 0.f, 0.f, 0.f}; acc1[u] = (v4f){0.f, 0.f, 0.f, 0.f};
-                        }
-    #pragma unroll
-                        for (int i = 0; i < NE; ++i) {
-    #pragma unroll
-                            for (int c = (i * NCH) / NE; c < ((i + 1) * NCH) / NE; ++c) {
-                                const float4 a0 = la0[c], a1 = la1[c];
-    #pragma unroll
-                                for (int u = 0; u < NSET; ++u) {
-                                    const float4 b = xb[u][c];
-                                    acc0[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0.x, b.x, acc0[u], 0, 0, 0);
-                                    acc1[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.x, b.x, acc1[u], 0, 0, 0);
-                                    acc0[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0.y, b.y, acc0[u], 0, 0, 0);
-                                    acc1[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.y, b.y, acc1[u], 0, 0, 0);
-                                    acc0[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0.z, b.z, acc0[u], 0, 0, 0);
-                                    acc1[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.z, b.z, acc1[u], 0, 0, 0);
-                                    acc0[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0.w, b.w, acc0[u], 0, 0, 0);
-                                    acc1[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.w, b.w, acc1[u], 0, 0, 0);
-                                }
-                            }
-                            collide_round(i);
-                        }
-    #pragma unroll
-                        for (int u = 0; u < NSET; ++u) {
-                            float* dst = &lds[TB_WORDS + (ebw + 4 * u + (lane & 3)) * GE_STRIDE + GE_A];
-                            *reinterpret_cast<float4*>(&dst[4 * blk]) = make_float4(acc0[u][0], acc0[u][1], acc0[u][2], acc0[u][3]);
-                            if (64 + 4 * blk < LROW)                       // rows 64..99 (word 99 is padding)
-                                *reinterpret_cast<float4*>(&dst[64 + 4 * blk]) = make_float4(acc1[u][0], acc1[u][1], acc1[u][2], acc1[u][3]);
-                        }
-                        group_sync();
-                    }
-                    if constexpr (!QM && PART != 3) contact_overflow<G>(lds, eb, gl, gbase, nc);
-    return nc;
-#undef EBF
-#undef LSTAMP
+        for (int v = gl; v < GE_U_WORDS / 4; v += G) uz[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    int up[NE];
+    float u_own[NE];
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int e = gl + i * G;
+        const int ix = (e * 373) >> 12, iz = e - LAT_NC * ix;            // e / 11 for e < 682
+        up[i] = (ix + 1) * (LAT_NC + 2) + iz + 1;
+        const float se = live ? s_pre[i] : 0.f, sde = live ? sd_pre[i] : 0.f;
+        u_own[i] = fmaf(kten, se, bten * sde);
+        if (e < N_TOP) { EBF(GE_SD + e) = sde; EBF(GE_U + up[i]) = u_own[i]; }     // (s itself stays in the owner's registers)
+    }
+    group_sync();
+    // ---- lattice right-hand side: a_s + w_fix aref_fix + w_ten sum_j aref_ij
+    //      = a_s - w_fix (k_fix s + b_fix sdot) - w_ten (deg u - sum of the four neighbour cells), deg = 4 (3 at the corners) ----
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int e = gl + i * G;
+        if (e >= N_TOP) continue;
+        const float se = live ? s_pre[i] : 0.f, sde = live ? sd_pre[i] : 0.f;
+        const float* uc = &EBF(GE_U + up[i]);
+        const float nb = (uc[-1] + uc[1]) + (uc[-(LAT_NC + 2)] + uc[LAT_NC + 2]);
+        const bool corner = (e == 0) | (e == LAT_NC - 1) | (e == N_TOP - LAT_NC) | (e == N_TOP - 1);
+        float r = -(GRAV + az) * lds[TB_AXIS + 3 * e + 2] - M.wfix * fmaf(bfix, sde, kfix * se);
+        r = fmaf(-M.wten, fmaf(corner ? 3.f : 4.f, u_own[i], -nb), r);
+        EBF(GE_X + e) = r;
+    }
+    if (gl == 0) EBF(GE_X + N_TOP) = 0.f;          // pad word read by the 16-byte row chunks
+    group_sync();
 }
+
+// lattice_solve: a~ = Linv rhs into the GE_A area of every environment of the wave.  Needs no arm quantity either.
+// Matrix-core form (every lane of the wave is active here): the wave's environments are the columns of one dense product
+// A~[99 x EPW] = Linv[99 x 100] X[100 x EPW], issued as v_mfma_f32_4x4x1 (16 blocks of 4 rows x 4 columns per instruction).  Lane l feeds Linv row l (and
+// row 64 + l) as the A operand and the rhs of environment l % 4 as the B operand; it receives rows 4 (l / 4) .. + 3 of that environment (layout:
+// tools/probe/mfma_4x4x1_layout.hip).
+template <int G>
+DI void lattice_solve(float* lds, const int eb, const int gl, const int gbase) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    constexpr int EPW = 64 / G, NSET = (EPW >= 4 && EPW <= 8) ? EPW / 4 : 1, NCH = LROW / 4;
+    const int lane = gbase + gl, ebw = eb - gbase / G, blk = lane >> 2;
+    const int r1 = (64 + lane < N_TOP) ? 64 + lane : N_TOP - 1;
+    const float4* la0 = reinterpret_cast<const float4*>(&lds[TB_LINV + lane * LROW]);
+    const float4* la1 = reinterpret_cast<const float4*>(&lds[TB_LINV + r1 * LROW]);
+    const float4* xb[NSET];
+    v4f acc0[NSET], acc1[NSET];
+#pragma unroll
+    for (int u = 0; u < NSET; ++u) {
+        xb[u] = reinterpret_cast<const float4*>(&lds[TB_WORDS + (ebw + 4 * u + (lane & 3)) * GE_STRIDE + GE_X]);
+        acc0[u] = (v4f){0.f, 0.f, 0.f, 0.f}; acc1[u] = (v4f){0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const float4 a0 = la0[c], a1 = la1[c];
+#pragma unroll
+        for (int u = 0; u < NSET; ++u) {
+            const float4 b = xb[u][c];
+            acc0[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0.x, b.x, acc0[u], 0, 0, 0);
+            acc1[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.x, b.x, acc1[u], 0, 0, 0);
+            acc0[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0.y, b.y, acc0[u], 0, 0, 0);
+            acc1[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.y, b.y, acc1[u], 0, 0, 0);
+            acc0[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0.z, b.z, acc0[u], 0, 0, 0);
+            acc1[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.z, b.z, acc1[u], 0, 0, 0);
+            acc0[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0.w, b.w, acc0[u], 0, 0, 0);
+            acc1[u] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1.w, b.w, acc1[u], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NSET; ++u) {
+        float* dst = &lds[TB_WORDS + (ebw + 4 * u + (lane & 3)) * GE_STRIDE + GE_A];
+        *reinterpret_cast<float4*>(&dst[4 * blk]) = make_float4(acc0[u][0], acc0[u][1], acc0[u][2], acc0[u][3]);
+        if (64 + 4 * blk < LROW)                       // rows 64..99 (word 99 is padding)
+            *reinterpret_cast<float4*>(&dst[64 + 4 * blk]) = make_float4(acc1[u][0], acc1[u][1], acc1[u][2], acc1[u][3]);
+    }
+    group_sync();
+}
+
+// collide_all (single-wave kernels): broad phase and narrow phase in one go -- element positions into the environment's LDS block, the ids that pass
+// collide_cull (ascending) into a queue, then the queue G elements at a time (collide_queue).  Same per-element arithmetic and the same ballot slots as
+// walking all NE rounds.  Leaves the contact records (ascending shell id) in the GE_CG area and returns the number found (may exceed MAXC: contact_overflow).
+// The queue overlays the GE_A area, which is free until lattice_solve stores its result there: collide first, then solve.
+template <int G, int NE>
+DI int collide_all(float* lds, const int eb, const int gl, const int gbase, const DevModel& M, const DevCfg& C, const bool live, const float* s_pre,
+                   const float dz, const f3 Kx, const f3 Ksy, const f3 Ksz) {
+    const f3 Ksx = cross(Ksy, Ksz);
+    float* const q = &EBF(GE_A);
+    int nq = 0, nc = 0;
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
+        const float se = live ? s_pre[i] : 0.f;
+        if (eraw < N_TOP) EBF(GE_S + eraw) = se;
+        const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, se, dz, Kx, Ksx, Ksz);
+        const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & ((1u << G) - 1u);
+        if (cand) q[nq + __popc(gm & ((1u << gl) - 1u))] = __int_as_float(e);
+        nq += __popc(gm);
+    }
+    group_sync();
+    collide_queue<G>(lds, q, nq, &EBF(GE_CG), gl, gbase, M, C, &EBF(GE_S), dz, Kx, Ksx, Ksy, Ksz, nc);
+    group_sync();                                      // the queue area is rewritten by the solve's result
+    return nc;
+}
+#undef EBF
 
 // sum over the lanes of a group, delivered to every lane (three or four DPP steps; lane k + 8 first, so that a 16-lane group whose halves carry the two contacts
 // of a pair adds in the order of an 8-lane group that holds both in one lane: the same bits)
@@ -537,7 +507,7 @@ DI typename LaneVec<T>::mask cone_local(const T b00, const T b01, const T b02, c
 }
 
 // Contact solve of one forward pass (called when some environment of the wave has a contact): contact k of an environment lives in the
-// registers of lane k of its group.  Inputs: contact records in LDS (lattice_front), element indices cel[], the site-space operator
+// registers of lane k of its group.  Inputs: contact records in LDS (collide_queue, contact_overflow), element indices cel[], the site-space operator
 // Lambda^-1 (packed lower 6 x 6), the site acceleration / velocity of the unconstrained arm (alpha, vs).  Outputs: net contact wrench on the
 // site W[6] (accumulated) and the impulse gf[k] along each contact's element axis.
 // The arm-independent half of a contact lane's set-up (everything the row needs from the record, the lattice tables and the element state): the split
@@ -1071,17 +1041,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
 #define ST(f) st[scalar_index((f), (size_t)ei)]
 #define STI(f) (reinterpret_cast<int*>(st))[scalar_index((f), (size_t)ei)]
 #define LAT(w) st[(size_t)F_LAT * npad + (size_t)ei * LATF_ENV_WORDS + (w)]
-// phase timeline probe (diagnostics only): wave 0 of workgroup 0 stamps the shader clock when io.dbg is set
-// The stamps exist only in the profiling build (make prof -> libusim_prof.so, -DUSIM_TSTAMP): each one is a branch, and sixteen of them
-// cost the production kernel 2 % (25.6 vs 25.1 us/step).  -DUSIM_TSTAMP_NOWAIT additionally keeps the stamps from draining memory traffic.
-#if !defined(USIM_TSTAMP) && !defined(USIM_TSTAMP_NOWAIT)
-#define TSTAMP(k) do { } while (0)
-#elif defined(USIM_TSTAMP_NOWAIT)
-#define TSTAMP(k) do { if (io.dbg && blockIdx.x == 0 && threadIdx.x == 0) { io.dbg[k] = __builtin_readcyclecounter(); } } while (0)
-#else
-#define TSTAMP(k) do { if (io.dbg && blockIdx.x == 0 && threadIdx.x == 0) { __builtin_amdgcn_s_waitcnt(0); io.dbg[k] = __builtin_readcyclecounter(); } } while (0)
-#endif
-    TSTAMP(0);
+    USIM_STAMP(io.dbg, 0);
     // ---------------- load state ----------------
     float sv[F_NSCALAR];                               // the 40 scalar words of the environment, in Field order: ten 16-byte loads
     {
@@ -1119,7 +1079,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
         body.v = mk(bw[7], bw[8], bw[9]); body.w = mk(bw[10], bw[11], bw[12]);
     }
 
-    TSTAMP(1);
+    USIM_STAMP(io.dbg, 1);
     // ---------------- action ----------------
     float act[7] = {0, 0, 0, 0, 0, 0, 0};
     if (!reset_only) {
@@ -1278,7 +1238,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
                         Li[PK(a, b)] = s;
                     }
             }
-            TSTAMP(2);
+            USIM_STAMP(io.dbg, 2);
             // ---------------- OSC_POSE torque (robosuite osc.py run_controller; rl_config.yaml:33-51) ----------------
             float tau[NJ];
             if (pass == 0) {
@@ -1388,7 +1348,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
 #pragma unroll
                 for (int a = 0; a < 7; ++a) L[46 + a] = act[a];
             }
-            TSTAMP(3);
+            USIM_STAMP(io.dbg, 3);
             // ---------------- smooth acceleration ----------------
             float qs[NJ];
 #pragma unroll
@@ -1471,7 +1431,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
             if (pass == 1 && valid && !refill) {                         // a reset of the live state: the episode starts without a warm start
                 for (int w = gl; w < LATF_WARM_WORDS; w += G) LAT(LATF_WTAB + w) = (w >= 4 * NSH && w < 4 * NSH + 8) ? __int_as_float(-1) : 0.f;
             }
-            TSTAMP(12);
+            USIM_STAMP(io.dbg, 12);
             // ---------------- constrained arm acceleration: qacc = qs + M^-1 J^T W ----------------
 #pragma unroll
             for (int i = 0; i < NJ; ++i) qacc[i] = qs[i];
@@ -1510,7 +1470,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
                 f3 tw = N + cross(K.o[NJ - 1] + rc - K.x, Fp) - mk(W[3], W[4], W[5]);
                 R.tq[0] = dot(K.sx, tw); R.tq[1] = dot(K.sy, tw); R.tq[2] = dot(K.sz, tw);
             }
-            TSTAMP(13);
+            USIM_STAMP(io.dbg, 13);
             // ---------------- integrate the arm: mj_Euler with implicit joint damping ----------------
             if (pass == 0) {
                 // (M + h D) x = M qacc with D = d I, h d = 2e-5: x = qacc - h d M^-1 x.  One step from x = qacc reuses the factor of M; the
@@ -1539,7 +1499,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
                 }
                 hv = mk(vs2[0], vs2[1], vs2[2]) + cross(mk(vs2[3], vs2[4], vs2[5]), K.hand - K.x);
             }
-            TSTAMP(14);
+            USIM_STAMP(io.dbg, 14);
             // ---------------- observation (ultrasound.py:363-401) ----------------
             {
                 const int tprev = (pass == 0) ? t - 1 : 0;
@@ -1680,7 +1640,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
         if (store) order_refill(io, env, episode);
     }
 
-    TSTAMP(15);
+    USIM_STAMP(io.dbg, 15);
     // ---------------- store state ----------------
     if (store && !(MODE == 1 && (refill || !need))) {
         {
@@ -1708,8 +1668,7 @@ __global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const De
     if (refill) group_sync();                         // next item reuses the per-environment LDS block
     }   // item loop
     if (MODE == 1 && refill) work_list_close(io);
-    TSTAMP(16);
-#undef TSTAMP
+    USIM_STAMP(io.dbg, 16);
 }
 
 // work items (env, episode + k), k = 1..BANK_DEPTH, for the environments selected by mask (reset / set_state paths)

@@ -19,7 +19,7 @@
 // (DevModel::tables + TB_ARM, usim_device.h ArmTable): per lane the fixed transform to the parent link frame, a joint about the local z axis,
 // inertial parameters in the link frame -- the kernel is the same for every chain of up to seven joints.
 //
-// Lattice / contact phases (soft torso) are the ones of usim_kernels.hip (lattice_front, contact_solve): the G = 16 mapping is unchanged there.
+// Lattice / contact phases (soft torso) are the ones of usim_kernels.hip (lattice_rhs, lattice_solve, collide_*, contact_solve): the G = 16 mapping is unchanged there.
 #pragma once
 #include <type_traits>
 
@@ -236,41 +236,31 @@ constexpr int X16_RIGID_STRIDE = 84;                  // rigid-torso launches: o
 // (kinematics ... controller, then acceleration, sensors, reward, bookkeeping), ROLE 2 the lattice / contact side (staging, right-hand side,
 // matrix-core solve, collision, contact solve, element integration).  They meet at workgroup barriers and hand over through per-environment
 // LDS mailboxes: site pose (1 -> 2), Lambda^-1 / alpha / vs (1 -> 2), contact wrench and contact list (2 -> 1).  ROLE 0 = one wave does both.
-// behind the per-environment blocks (16 with 16-lane groups, 32 with 8-lane groups): arm scratch + mailboxes of the split kernel
+//
 // waves per role in a workgroup of the split kernel (4: one 512-thread workgroup per CU; 2: two 256-thread workgroups per CU with barrier domains of their own)
 #ifndef USIM_WPR16
 #define USIM_WPR16 4
-#endif
-#ifndef USIM_ROLE_FLIP_BIT
-#define USIM_ROLE_FLIP_BIT -1
 #endif
 #ifndef USIM_WPR8
 #define USIM_WPR8 4
 #endif
 template <int G> constexpr int wpr() { return G == 16 ? USIM_WPR16 : USIM_WPR8; }
+// Split kernel: behind the per-environment blocks (16 with 16-lane groups, 32 with 8-lane groups) every environment has a mailbox block, one layout for both
+// group sizes (word offsets):
+constexpr int MB_POSE = X16_WORDS;                    // (before it: the 8 x 8 transpose scratch of the arm wave)  site pose 9 words; word 10: length of the broad-phase queue
+constexpr int MB_OP = MB_POSE + 12;                   // op-space quantities: 6 x 8 Lambda^-1, alpha 6, vs 6
+constexpr int MB_W = MB_OP + 64;                      // contact wrench 6, contact count, overflow flag, shell ids 8 (between the steps of a resident launch: the new episode's parameters)
+constexpr int MB_Q = MB_W + 16;                       // broad-phase queue (element ids; the spare last word takes the non-candidates' stores)
+constexpr int MB_GOAL = MB_Q + 100;                   // `fixed` mode with physics substeps: the goal anchored at the policy step (12 words)
+constexpr int X2_STRIDE = MB_GOAL + 12;
 template <int G> constexpr int x2_base() { return TB_WORDS + (64 * wpr<G>() / G) * GE_STRIDE; }
-// 64 transpose scratch | 12 pose (+ the arm side's hit count in word 9) | 64 op-space (6 x 8 Lambda^-1, alpha 6, vs 6) | 16 wrench + contacts | the arm side's contact records
-// 16-lane groups: 64 transpose scratch | 12 pose | 64 op-space | 16 wrench + contacts | 17 x 8 arm-side contact records | 100 queue.
-// 8-lane groups (32 environments per workgroup have to fit the CU's 160 KB): the arm side's contact records overlay the transpose scratch, which
-// is idle from the arm side's narrow-phase share until the next step, plus 72 words behind it; the mailboxes follow.
-template <int G> constexpr int mb_pose() { return G == 16 ? 64 : (MAXCAND + 1) * CG_WORDS; }
-template <int G> constexpr int mb_op() { return mb_pose<G>() + 12; }
-template <int G> constexpr int mb_w() { return mb_op<G>() + 64; }
-template <int G> constexpr int mb_ca() { return G == 16 ? mb_w<G>() + 16 : 0; }                                       // arm-side contact records
-template <int G> constexpr int mb_q() { return G == 16 ? mb_ca<G>() + (MAXCAND + 1) * CG_WORDS : mb_w<G>() + 16; }    // broad-phase queue (element ids)
-template <int G> constexpr int mb_goal() { return mb_q<G>() + 100; }                                              // `fixed` mode with physics substeps: the goal anchored at the policy step (12 words)
-template <int G> constexpr int x2_stride() { return mb_goal<G>() + 12; }
-static_assert((mb_ca<16>() % 4) == 0 && (mb_pose<8>() % 4) == 0 && (x2_stride<16>() % 4) == 0 && (x2_stride<8>() % 4) == 0, "mailbox block");
-static_assert((x2_base<8>() + 32 * x2_stride<8>()) * 4 <= 160 * 1024, "split kernel with 8-lane groups: LDS of a CU");
-// Collision in the split kernel: the ARM side, which has the site pose first, runs the broad phase over all 99 elements (collide_cull) while the
-// lattice side still stages its right-hand side, and leaves the survivors' ids (ascending) in the queue; after hand-off (1) the arm side takes
-// the first ARM_SHARE_NUM / ARM_SHARE_DEN of the queue, the lattice side the rest, each typically in one pass of its 16 lanes per environment.
-// (With the broad phase the narrow phase is short enough that the lattice side does best with all of it; the sharing machinery stays for
-// other probe shapes.)
+static_assert(x2_base<16>() % 4 == 0 && x2_base<8>() % 4 == 0 && X2_STRIDE % 4 == 0 && MB_OP % 4 == 0 && MB_W % 4 == 0, "mailbox block: 16-byte accesses");
+static_assert((x2_base<8>() + 32 * X2_STRIDE) * 4 <= 160 * 1024, "split kernel with 8-lane groups: LDS of a CU");
+// Collision in the split kernel: the ARM side, which has the site pose first, runs the broad phase (collide_cull) while the lattice side still stages its
+// right-hand side and solves, and leaves the survivors' ids (ascending) in the queue; after hand-off (1) the lattice side appends what the arm side left of the
+// broad phase and evaluates the whole queue (collide_queue), typically in one pass of its 16 lanes per environment.  (Giving the arm side a share of the narrow
+// phase measured slower for every share and both group sizes -- DESIGN.md section 4.6 -- and was removed.)
 template <int G> constexpr int arm_cull_rounds() { return 7; }   // broad-phase rounds the arm side runs before hand-off (1); the lattice side runs the rest after it.  16-lane groups, measured (us/step, one box): 0 -> 15.67, 2 -> 15.98, 4 -> 15.92, 7 (all) -> 15.48
-constexpr int ARM_SHARE_DEN = 4;
-template <int G> constexpr int arm_share_num() { return 0; }     // quarters of the queue the arm side evaluates.  Measured (us/step, one box): 16-lane groups 0 -> 15.48, 1 -> 15.80, 2 -> 15.77; 8-lane groups at 8192 envs 0 -> 23.06, 2 -> 23.93, 3 -> 24.06 (the two waves share a SIMD: what the arm wave does while it would wait costs the lattice wave issue slots)
-// 16-lane groups     // measured (us/step, one box): 0 -> 15.48, 1/4 -> 15.80, 1/3 -> 15.61, 1/2 -> 15.77
 
 // workgroup barrier of the step kernels; the profiling build counts them per role (BARRIER INVARIANT at usim_step32_kernel)
 #if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
@@ -296,7 +286,7 @@ struct Carry {
 };
 
 template <int TORSO, int ROLE, int G> constexpr int arm_lds_base() {
-    return ROLE != 0 ? x2_base<G>() + (64 * wpr<G>() / G) * x2_stride<G>() : (TORSO ? GroupGeom<16>::LDS_WORDS : 16 * X16_RIGID_STRIDE);
+    return ROLE != 0 ? x2_base<G>() + (64 * wpr<G>() / G) * X2_STRIDE : (TORSO ? GroupGeom<16>::LDS_WORDS : 16 * X16_RIGID_STRIDE);
 }
 static_assert((arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS) * 4 <= 160 * 1024 && arm_lds_base<1, 1, 8>() % 4 == 0 && arm_lds_base<1, 1, 16>() % 4 == 0 && arm_lds_base<1, 0, 16>() % 4 == 0
               && arm_lds_base<0, 0, 16>() % 4 == 0, "arm table behind the LDS blocks of every 16-lane kernel");
@@ -312,7 +302,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     constexpr int WPR = (ROLE != 0) ? wpr<G>() : 4;
     constexpr int EPW = 64 / G, EPB = WPR * EPW;                        // environments per wave / per workgroup (WPR waves per role)
     static_assert(!RES || MODE == 0, "resident state: step launches only");
-    constexpr int X2_BASE = x2_base<G>(), X2_STRIDE = x2_stride<G>(), MB_Q = mb_q<G>(), MB_POSE = mb_pose<G>(), MB_OP = mb_op<G>(), MB_W = mb_w<G>(), MB_CA = mb_ca<G>();
+    constexpr int X2_BASE = x2_base<G>();
     constexpr unsigned GMASK = (G == 16) ? 0xffffu : 0xffu;
     static_assert(G == 16 || (TORSO == 1 && MODE == 0 && ROLE != 0), "8-lane groups: the split soft-torso step only");
     constexpr int NE = TORSO ? (N_TOP + G - 1) / G : 1;
@@ -355,7 +345,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     static_assert(GE_WS + X16_WORDS <= GE_STRIDE, "transpose scratch overlays the wrench records");
     // `fixed`-mode goal held across physics substeps: split kernel -- in the mailbox block; single wave, soft torso -- the last 12 words of the environment's
     // block, behind the spare contact record; rigid torso -- behind the transpose scratch
-    constexpr int GOAL_OFF = (ROLE != 0) ? mb_goal<G>() : (TORSO ? GE_CG + (MAXCAND + 1) * CG_WORDS - GE_WS : X16_WORDS);
+    constexpr int GOAL_OFF = (ROLE != 0) ? MB_GOAL : (TORSO ? GE_CG + (MAXCAND + 1) * CG_WORDS - GE_WS : X16_WORDS);
     static_assert(GE_CG + (MAXCAND + 1) * CG_WORDS + 12 <= GE_STRIDE && X16_WORDS + 12 <= X16_RIGID_STRIDE, "room for the goal");
     float* const goal_lds = xl + GOAL_OFF;
 
@@ -469,44 +459,45 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         RSTAMP(0);
         float* const mb = &lds[mbo];
         const int* tb_shell = reinterpret_cast<const int*>(lds + TB_SHELL);
-        const int tsim = tphys;
         float dz, vz, az;
-        torso_motion(C, tsim, dz, vz, az);
-        lattice_front<G, NE, 1>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, mk(0, 0, 0), mk(0, 0, 0), mk(0, 0, 0), dbg);
+        torso_motion(C, tphys, dz, vz, az);
+        lattice_rhs<G, NE>(lds, eb, gl, M, az, kst, kdmp, true, s_pre, sd_pre);
         // The matrix-core solve a~ = Linv rhs needs nothing from the arm side: it runs here, where this wave used to wait for the site pose (hand-off (1)
         // comes when the arm side has finished its kinematics and the broad phase), and leaves only the narrow phase for after the hand-off: one box,
         // 14.38 -> 13.65 us/step at 4096 envs, 20.8 -> 20.2 at 8192 (8-lane groups).  Splitting the product around the hand-off so that both sides reach
         // hand-offs (1) and (2) together (18 / 14 / 21 of the 25 k chunks before it, accumulators live across the barrier) is slower: 13.9 / 14.1 / 13.85,
         // and with 8-lane groups the accumulators of both column sets spill (44 us).
-        lattice_front<G, NE, 3, true>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, mk(0, 0, 0), mk(0, 0, 0), mk(0, 0, 0), dbg);
+        lattice_solve<G>(lds, eb, gl, gbase);
         RSTAMP(1);
         USIM_BAR();                                                 // (1) the arm side has published the site pose
         RSTAMP(2);
         const f3 xs = mk(mb[MB_POSE], mb[MB_POSE + 1], mb[MB_POSE + 2]), sy = mk(mb[MB_POSE + 3], mb[MB_POSE + 4], mb[MB_POSE + 5]),
                  sz = mk(mb[MB_POSE + 6], mb[MB_POSE + 7], mb[MB_POSE + 8]);
+        const f3 sxc = cross(sy, sz);
         int nq = __float_as_int(mb[MB_POSE + 10]);
-        {
-            // the rest of the broad phase (elements 16 arm_cull_rounds<G>() ..): appended to the arm side's part of the queue
-            const f3 sxc = cross(sy, sz);
+        // the rest of the broad phase (elements G arm_cull_rounds<G>() ..): appended to the arm side's part of the queue
 #pragma unroll
-            for (int i = arm_cull_rounds<G>(); i < NE; ++i) {
-                const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
-                const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz, xs, sxc, sz);
-                const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & GMASK;
-                mb[MB_Q + (cand ? nq + __popc(gm & ((1u << gl) - 1u)) : 99)] = __int_as_float(e);       // (as on the arm side: the spare last word takes the non-candidates)
-                nq += __popc(gm);
-            }
-            group_sync();
+        for (int i = arm_cull_rounds<G>(); i < NE; ++i) {
+            const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
+            const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz, xs, sxc, sz);
+            const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & GMASK;
+            mb[MB_Q + (cand ? nq + __popc(gm & ((1u << gl) - 1u)) : 99)] = __int_as_float(e);       // (as on the arm side: the spare last word takes the non-candidates)
+            nq += __popc(gm);
         }
-        const int na = (__float_as_int(mb[MB_POSE + 10]) * arm_share_num<G>() + ARM_SHARE_DEN - 1) / ARM_SHARE_DEN;
-        const int ncl = lattice_front<G, NE, 4, true>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, true, s_pre, sd_pre, xs, sy, sz, dbg, mb + MB_Q, na, nq);
-        // Without an arm-side share of the narrow phase the contact list is complete here: the slot rule, the contact elements and the arm-independent half
-        // of every contact row (frame, lever arms, lattice coupling, regulariser) can be formed before hand-off (2), while the arm side still forms Lambda^-1.
-        // One box, kernel us/step: 8-lane groups at 8192 envs 20.19 -> 19.97 (scratch 176 -> 112 bytes per lane); 16-lane groups at 4096 envs 13.67 -> 13.82
-        // (same scratch; the two waves share a SIMD's issue slots, so what moves ahead of the barrier is taken from the arm wave) -- only the 8-lane kernel does it.
-        constexpr bool EARLY = arm_share_num<G>() == 0 && G == 8;
+        group_sync();
+        // narrow phase: the whole queue, against the element positions the arm side parked in the environment's block
+        int nc = 0;
+        collide_queue<G>(lds, mb + MB_Q, nq, &EB(GE_CG), gl, gbase, M, C, &EB(GE_S), dz, xs, sxc, sy, sz, nc);
+        // The contact list is complete here.  8-lane groups (EARLY) apply the slot rule and form the contact elements and the arm-independent half of every
+        // contact row (frame, lever arms, lattice coupling, regulariser) before hand-off (2), while the arm side still forms Lambda^-1; 16-lane groups do it
+        // after the hand-off.  One box, kernel us/step: 8-lane groups at 8192 envs 20.19 -> 19.97 (scratch 176 -> 112 bytes per lane); 16-lane groups at 4096
+        // envs 13.67 -> 13.82 (same scratch; what moves ahead of the barrier lengthens the path the arm wave waits for) -- only the 8-lane kernel does it.
+        constexpr bool EARLY = G == 8;
         ContactRows P;
-        int nc_early = ncl, overflow_early = 0, ncmax_early = 0, cel_early[MAXC];
+        // (The early list lives in variables of its own and is adopted after the hand-off.  Forming it in nc / overflow / ncmax / cel directly, with the slot rule as
+        //  one lambda called on either side of the barrier, reads better and cost the 8-lane multi-step kernel two more spilled registers, 8 B of scratch and 0.6 % of
+        //  the 8192-environment step: DESIGN.md section 10.)
+        int nc_early = nc, overflow_early = 0, ncmax_early = 0, cel_early[MAXC];
         if constexpr (EARLY) {
             contact_overflow<G>(lds, eb, gl, gbase, nc_early);
             if (nc_early > MAXC) { overflow_early = 1; nc_early = MAXC; }
@@ -518,28 +509,8 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             if (ncmax_early > 0) contact_rows<G>(lds, eb, gl, M, C, nc_early, cel_early, vz, P);
         }
         RSTAMP(3);
-        USIM_BAR();                                                 // (2) ... and Lambda^-1, alpha = J qs, vs = J qd, and the arm side's contact records
+        USIM_BAR();                                                 // (2) ... and Lambda^-1, alpha = J qs, vs = J qd
         RSTAMP(4);
-        // one list in ascending shell id: the arm side's records (first part of the queue) first, this side's behind them
-        const int nca = EARLY ? 0 : __float_as_int(mb[MB_POSE + 9]);
-        int nc = nca + ncl;
-        if (!EARLY && __any(nca > 0)) {
-            constexpr int RPL = MAXCAND / G;                             // records per lane of the group
-            const int na = nca < MAXCAND ? nca : MAXCAND;
-            float4 r0[RPL], r1[RPL];
-#pragma unroll
-            for (int hh = 0; hh < RPL; ++hh) {
-                const int gg = gl + hh * G, li = gg - na;
-                const float4* src = reinterpret_cast<const float4*>(gg < na ? &mb[MB_CA + gg * CG_WORDS] : &EB(GE_CG + (li > 0 ? li : 0) * CG_WORDS));
-                r0[hh] = src[0]; r1[hh] = src[1];
-            }
-            group_sync();                                                // every record is in registers before any slot is overwritten
-#pragma unroll
-            for (int hh = 0; hh < RPL; ++hh) {
-                float4* dst = reinterpret_cast<float4*>(&EB(GE_CG + (gl + hh * G) * CG_WORDS));
-                dst[0] = r0[hh]; dst[1] = r1[hh];
-            }
-        }
         if constexpr (!EARLY) contact_overflow<G>(lds, eb, gl, gbase, nc);
         int overflow = 0;
         if (nc > MAXC) { overflow = 1; nc = MAXC; }
@@ -990,16 +961,6 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 #pragma unroll
     for (int k = 0; k < MAXC; ++k) con_shell[k] = -1;
     if constexpr (ROLE == 1) {
-        {
-            // the arm side's share of the narrow phase: the first part of the queue against the site pose it computed itself
-            float dz_, vz_, az_;
-            torso_motion(C, tphys, dz_, vz_, az_);
-            const f3 sxc = cross(sy, sz);
-            const int nq = __float_as_int(xl[MB_POSE + 10]), na = (nq * arm_share_num<G>() + ARM_SHARE_DEN - 1) / ARM_SHARE_DEN;
-            int nca = 0;
-            collide_queue<G>(lds, xl + MB_Q, 0, na, xl + MB_CA, gl, gbase, M, C, &EB(GE_S), dz_, xs, sxc, sy, sz, nca);
-            if (gl == 0) xl[MB_POSE + 9] = __int_as_float(nca);
-        }
         // hand Lambda^-1 (row a from task lane a), alpha = J qs and vs = J qd to the lattice side; take the contact wrench back
         if (is_task) {
             const int arow = blk ? 3 + comp : comp;
@@ -1022,10 +983,14 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         for (int k = 0; k < MAXC; ++k) con_shell[k] = __float_as_int(xl[MB_W + 8 + k]);
     } else if constexpr (TORSO != 0) {
         const int* tb_shell = reinterpret_cast<const int*>(lds + TB_SHELL);
-        const int tsim = tphys;
         float dz, vz, az;
-        torso_motion(C, tsim, dz, vz, az);
-        int nc = lattice_front<G, NE>(lds, eb, gl, gbase, M, C, tsim, kst, kdmp, MODE == 0, s_pre, sd_pre, xs, sy, sz, dbg);
+        torso_motion(C, tphys, dz, vz, az);
+        lattice_rhs<G, NE>(lds, eb, gl, M, az, kst, kdmp, MODE == 0, s_pre, sd_pre);
+        USIM_STAMP(dbg, 5);
+        // (collision before the solve: its queue overlays the area the solve's result is stored to)
+        int nc = collide_all<G, NE>(lds, eb, gl, gbase, M, C, MODE == 0, s_pre, dz, xs, sy, sz);
+        lattice_solve<G>(lds, eb, gl, gbase);
+        contact_overflow<G>(lds, eb, gl, gbase, nc);
         USIM_STAMP(dbg, 7);
         if (nc > MAXC) { overflow = 1; nc = MAXC; }
         ncon = nc;
@@ -1352,10 +1317,8 @@ __global__ __launch_bounds__(128 * wpr<G>()) __attribute__((amdgpu_waves_per_eu(
     // Through the pointer a field is a scalar load (SMEM, scalar cache) where it is used.
     const DevModel& M = *Mp; const DevCfg& C = *Cp;
     constexpr int NT = 128 * wpr<G>();
-    // (two workgroups per CU: the role order alternates with a bit of the workgroup index, so that a SIMD holds an arm wave of one and a lattice wave of the other)
-    const bool flip = USIM_ROLE_FLIP_BIT >= 0 && ((blockIdx.x >> (USIM_ROLE_FLIP_BIT >= 0 ? USIM_ROLE_FLIP_BIT : 0)) & 1);
     typedef typename std::conditional<WARM, typename WarmOf<G>::type, NoWarm>::type WR;
-    if ((threadIdx.x < NT / 2) != flip) step16_body<1, 0, 1, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
+    if (threadIdx.x < NT / 2) step16_body<1, 0, 1, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
     else step16_body<1, 0, 2, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
 }
 

@@ -54,6 +54,15 @@ def _ptr(a, t=C.c_double):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
 
 
+def deep_spawn_params(state, n):
+    """reset_explicit parameters [n, 13] that keep the trajectories, stiffness, damping and friction of `state` (a get_state() dictionary of the
+    oracle or of the GPU environment) and spawn every probe 1.2-3 cm deep: up to 11 elements penetrate, more than the 8 contact slots"""
+    rng = np.random.default_rng(5)
+    noise = np.stack([rng.normal(scale=5e-3, size=n), rng.normal(scale=5e-3, size=n), -rng.uniform(0.012, 0.03, size=n)], axis=1)
+    return np.concatenate([state["traj_start"], state["traj_end"], state["u0"][:, None], noise, state["stiffness"][:, None],
+                           state["damping"][:, None], state["mu"][:, None]], axis=1)
+
+
 class Oracle:
     """n independent Ultrasound envs stepped by the C oracle.  precision: 'f64' (checker) or 'f32'."""
 

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle_lib import Oracle
+from oracle_lib import Oracle, deep_spawn_params
 
 pytestmark = pytest.mark.gpu
 
@@ -438,11 +438,7 @@ def test_contact_slot_overflow_parity(usim, lanes):
         env.close()
         env = usim.UltrasoundVecEnv(n, device="cuda:0", seed=3, torso="soft", lanes_per_env=64, **usim.default_robosuite_kwargs())
     env.reset(); ora.reset()
-    st = ora.get_state()
-    rng = np.random.default_rng(5)
-    noise = np.stack([rng.normal(scale=5e-3, size=n), rng.normal(scale=5e-3, size=n), -rng.uniform(0.012, 0.03, size=n)], axis=1)
-    p = np.concatenate([st["traj_start"], st["traj_end"], st["u0"][:, None], noise, st["stiffness"][:, None], st["damping"][:, None],
-                        st["mu"][:, None]], axis=1)
+    p = deep_spawn_params(ora.get_state(), n)
     og, oo = env.reset_explicit_tensor(p).cpu().numpy(), ora.reset_explicit(p)
     assert np.allclose(og[:, 12:19], oo[:, 12:19], atol=2e-6) and np.allclose(og[:, :3], oo[:, :3], atol=5e-2, rtol=2e-3)
     sg, so = env.get_state(), ora.get_state()

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from oracle_lib import deep_spawn_params
+
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -476,6 +478,32 @@ def test_split_kernel_equals_the_single_wave_kernel_bit_for_bit(usim):
             assert all(torch.equal(a, b) for a, b in zip(res[0], r)) and torch.equal(envs[0].contacts, e.contacts), k
         ended += int(res[0][2].sum())
     assert ended > 100
+    s0 = envs[0].get_state()
+    for e in envs[1:]:
+        s = e.get_state()
+        assert all(np.array_equal(s0[key], s[key]) for key in s0)
+    for e in envs:
+        e.close()
+
+
+def test_every_mapping_resolves_a_slot_overflow_to_the_same_bits(usim):
+    """probes spawned 1.2-3 cm deep (the reset of test_contact_slot_overflow_parity, which checks it against the oracle): more elements penetrate than there are
+    contact slots in every workgroup, so the slot rule of the single-wave kernel (lanes_per_env 16), of the split kernel with 16-lane groups (32; after hand-off
+    (2)) and with 8-lane groups (64; before it) all run -- same bits at the reset and over the 25 steps that follow"""
+    n = 256
+    envs = [_env(usim, n, lanes_per_env=lanes) for lanes in (16, 32, 64)]
+    for e in envs:
+        e.reset_tensor()
+    p = deep_spawn_params(envs[0].get_state(), n)
+    obs0 = [e.reset_explicit_tensor(p).clone() for e in envs]
+    assert all(torch.equal(obs0[0], o) for o in obs0[1:])
+    status = [e.get_state()["status"].astype(int) & 1 for e in envs]
+    assert status[0].sum() > 20 and all(np.array_equal(status[0], s) for s in status[1:])
+    act = torch.full((n, 6), 0.5, dtype=torch.float32, device=envs[0].device)
+    for k in range(25):
+        res = [[x.clone() for x in e.step_tensor(act, auto_reset=False)] for e in envs]
+        for r, e in zip(res[1:], envs[1:]):
+            assert all(torch.equal(a, b) for a, b in zip(res[0], r)) and torch.equal(envs[0].contacts, e.contacts), k
     s0 = envs[0].get_state()
     for e in envs[1:]:
         s = e.get_state()

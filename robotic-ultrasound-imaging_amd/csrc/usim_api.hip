@@ -2,7 +2,7 @@
 //
 // Builds the model constants in double precision (link-7 composite inertia, torso lattice tables, the inverse
 // of the lattice normal matrix), owns the SoA state block in HBM and enqueues the kernels of
-// usim_kernels.hip on the caller's HIP stream.  No torch types, no exceptions across the boundary.
+// usim_kernels.hip (and of usim_full.h, usim_step16.h, which it includes) on the caller's HIP stream.  No torch types, no exceptions across the boundary.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -68,7 +68,7 @@ static Kernel kernel_of(Mapping m, int mode, bool multi, bool warm) {
     }
     constexpr int L16 = arm_lds_base<1, 0, 16>() + ARM_LDS_WORDS;
     switch (m) {
-        case Mapping::FULL: return {r ? usim_step_kernel<2, 64, 1> : usim_step_kernel<2, 64, 0>, nullptr, GroupGeom<64>::EPB, GroupGeom<64>::NT, GroupGeom<64>::LDS_WORDS};
+        case Mapping::FULL: return {r ? usim_step_kernel<2, 64, 1> : usim_step_kernel<2, 64, 0>, nullptr, FULL_EPB, FULL_NT, FULL_LDS_WORDS};
         case Mapping::RIGID16: return {r ? usim_step16_kernel<0, 2, 1, false> : mu ? usim_step16_kernel<0, 2, 0, true> : usim_step16_kernel<0, 2, 0, false>, nullptr, 16, 256, arm_lds_base<0, 0, 16>() + ARM_LDS_WORDS};
         case Mapping::SOFT16_W1: return {mu ? usim_step16_kernel<1, 1, 0, true> : usim_step16_kernel<1, 1, 0, false>, nullptr, 16, 256, L16};
         case Mapping::SOFT16_W2: return {r ? usim_step16_kernel<1, 2, 1, false> : mu ? usim_step16_kernel<1, 2, 0, true> : usim_step16_kernel<1, 2, 0, false>, nullptr, 16, 256, L16};

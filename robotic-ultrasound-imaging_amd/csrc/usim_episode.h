@@ -1,5 +1,5 @@
 // usim_episode.h -- per-environment pieces of what the reference's Ultrasound env does around mj_step.  The Episode struct, the reset-bank
-// addressing, episode_begin, order_refill, work_list_close and finite_or_zero serve the step kernel of the full torso (usim_kernels.hip) and the
+// addressing, episode_begin, order_refill, work_list_close and finite_or_zero serve the step kernel of the full torso (usim_full.h) and the
 // 16-lane kernels of the rigid and soft torsos (usim_step16.h); synthetic_action serves the full-torso kernel and usim_random_actions_kernel.
 // The functions work on per-environment scalars; what is laid out per lane (joint words, the Philox evaluation) stays with the kernels.
 // Still one copy per kernel family: reset draws, observation, reward terms, bookkeeping, termination, episode record, bank park / adopt, and
@@ -7,7 +7,7 @@
 // out with a different instruction schedule and register allocation (the callee is simplified on its own before it is inlined; synthetic_action
 // in step16_one changes 7 of the 14), which needs an A/B of its own.
 #pragma once
-// (included by usim_kernels.hip inside namespace usim)
+// (included by usim_kernels.hip inside namespace usim, before usim_full.h)
 
 // the per-episode scalar words of the state (Field F_TS .. F_STATUS)
 struct Episode {

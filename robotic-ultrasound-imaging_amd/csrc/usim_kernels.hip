@@ -3,9 +3,9 @@
 // This file holds
 //   - the lattice and contact phases of the soft torso (lattice_rhs, lattice_solve, collide_*, contact_overflow, contact_rows / contact_solve), which the 16-lane step kernels
 //     of usim_step16.h (rigid and soft torso, included at the end) call;
-//   - usim_step_kernel<2, 64, MODE>, the step / reset kernel of the full torso (physics in usim_full.h);
 //   - usim_bank_items_kernel (refill work list of the reset / set_state paths) and usim_random_actions_kernel (the synthetic actions).
-// Pieces of the env logic that the step kernels share are in usim_episode.h.  Every step kernel replaces, per environment:
+// The full torso -- its physics and its step / reset kernel usim_step_kernel<2, 64, MODE> -- is usim_full.h, included below.  Pieces of the env logic that the step
+// kernels share are in usim_episode.h.  Every step kernel replaces, per environment:
 //   a1 robosuite MujocoEnv.step driver            a2 OSC_POSE controller (rl_config.yaml:33-51)
 //   a3 MuJoCo mj_step (forward dynamics + soft constraints + Euler)
 //   a4 Ultrasound.reward  ultrasound.py:230-269   a5 sensors ultrasound.py:363-401
@@ -26,7 +26,7 @@
 //                  - contacts keep ascending shell-id order through a wave ballot;
 //                  - contact k lives in the registers of lane k; the dual problem is solved on 3 x 3 Delassus blocks held
 //                    per lane, a Gauss-Seidel visit broadcasts three force increments with DPP row_newbcast.
-//   full torso   G = 64: usim_step_kernel<2, 64, MODE> below, one wave per environment (usim_full.h).
+//   full torso   one wave per environment: usim_step_kernel<2, 64, MODE> (usim_full.h).
 // Per-environment state is read and written once per step as rows of the SoA state block in HBM.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,13 +62,7 @@ constexpr int GE_STRIDE = 548;                        // 548 mod 64 = 36: disjoi
 static_assert(GE_WS + MAXC * 8 <= GE_STRIDE && GE_CG + (MAXCAND + 1) * CG_WORDS <= GE_STRIDE && GE_U + GE_U_WORDS <= GE_STRIDE, "per-environment LDS block overflow");
 static_assert((LAT_NA + 2) * (LAT_NC + 2) <= GE_U_WORDS && LAT_NA * LAT_NC == N_TOP, "padded lattice grid");
 
-template <int G> struct GroupGeom {
-    static constexpr int EPW = 64 / G;                // environments per wave
-    static constexpr int WAVES = (G >= 4) ? G / 4 : 1;
-    static constexpr int EPB = EPW * WAVES;           // environments per workgroup (64 for G = 1, else 16)
-    static constexpr int NT = 64 * WAVES;
-    static constexpr int LDS_WORDS = TB_WORDS + EPB * GE_STRIDE;
-};
+constexpr int SOFT16_LDS_WORDS = TB_WORDS + 16 * GE_STRIDE;   // the tables and the blocks of the 16 environments of a workgroup (16-lane kernels, one wave each)
 
 DI void group_sync() {
     // the lanes of a group exchange data through LDS inside one wave: order the LDS traffic, no s_barrier needed
@@ -996,680 +990,8 @@ _Pragma("unroll") \
 #undef EB
 }
 
-#include "usim_full.h"
 #include "usim_episode.h"
-
-struct StepOut {               // results of one forward pass that the env logic needs
-    float fc[3];               // net contact force on the probe (cfrc_ext[probe][3:6])
-    float tq[3];               // torque sensor at ft_frame (site frame)
-    int ncon;
-    int con_shell[MAXC];
-    int overflow;
-};
-
-// Step kernel of the full torso (TORSO = 2, G = 64: one wave per environment, usim_full.h); the rigid and soft torsos run the kernels of usim_step16.h.
-// MODE 0: one env.step() per environment; a finished environment takes its next initial state from the reset bank.
-// MODE 1: reset computation (draws, initial-pose IK, zero-torque forward pass) for the environments selected by the mask
-//         (written to the live state) or for the (env, episode) items of the refill work list (written to the reset bank).
-template <int TORSO, int G, int MODE>
-__global__ __launch_bounds__(GroupGeom<G>::NT, 2) void usim_step_kernel(const DevModel M, const DevCfg C, float* __restrict__ st, int n, int npad,
-                                                                      const DevIO io, int flags, long long rstep) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    // step waves outrank the background refill waves that may share their SIMD (priority, then age, arbitrates VALU issue)
-    __builtin_amdgcn_s_setprio(MODE == 0 ? 3 : 0);
-    static_assert(TORSO == 2 && G == 64, "the full torso's mapping only");
-    constexpr int EPW = GroupGeom<G>::EPW, EPB = GroupGeom<G>::EPB;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int gl = lane % G, ge = lane / G;           // lane within the group, group (= environment) within the wave
-    const int eb = wave * EPW + ge;                   // environment within the workgroup
-    // refill launches walk the work list with a grid-stride loop; every other launch runs the body once
-    const bool refill = (MODE == 1) && io.refill != 0;
-    const int item_cnt = refill ? io.count[0] : 1;
-    for (int item0 = refill ? (int)blockIdx.x * EPB : 0; item0 < item_cnt; item0 += refill ? (int)gridDim.x * EPB : 1) {
-    int env = blockIdx.x * EPB + eb;
-    bool valid = env < n;                             // lattice rows are stored by every lane of the group
-    int item_ep = 0;
-    if (refill) {
-        valid = item0 + eb < item_cnt;
-        const int2 it = valid ? io.items[item0 + eb] : make_int2(0, 0);
-        env = it.x; item_ep = it.y;
-    }
-    const bool store = valid && gl == 0;              // per-environment scalars and outputs by its first lane
-    const int ei = valid ? env : (refill ? 0 : n - 1);               // clamp so that every lane has something to read; stores are guarded
-    constexpr bool reset_only = (MODE == 1);
-    const bool auto_reset = (flags & LF_AUTO_RESET) != 0;
-#define ST(f) st[scalar_index((f), (size_t)ei)]
-#define STI(f) (reinterpret_cast<int*>(st))[scalar_index((f), (size_t)ei)]
-#define LAT(w) st[(size_t)F_LAT * npad + (size_t)ei * LATF_ENV_WORDS + (w)]
-    USIM_STAMP(io.dbg, 0);
-    // ---------------- load state ----------------
-    float sv[F_NSCALAR];                               // the 40 scalar words of the environment, in Field order: ten 16-byte loads
-    {
-        const float4* sp = reinterpret_cast<const float4*>(st + scalar_index(0, (size_t)ei));
-#pragma unroll
-        for (int v = 0; v < F_NSCALAR / 4; ++v) { const float4 x = sp[v]; sv[4 * v] = x.x; sv[4 * v + 1] = x.y; sv[4 * v + 2] = x.z; sv[4 * v + 3] = x.w; }
-    }
-    float q[NJ], qd[NJ], q0[NJ], dq[NJ];             // the joint words of the state hold dq = q - q0 (usim_device.h)
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) { dq[i] = sv[F_Q + i]; qd[i] = sv[F_QD + i]; q0[i] = sv[F_Q0 + i]; q[i] = q0[i] + dq[i]; }
-    Episode E;
-    f3 &ts = E.ts, &te = E.te;
-    float &u0 = E.u0, &vbar = E.vbar, &fzbar = E.fzbar, &fzprev = E.fzprev, &dfz = E.dfz, &kst = E.kst, &kdmp = E.kdmp, &mu = E.mu, &epret = E.epret;
-    int &t = E.t, &touched = E.touched, &episode = E.episode, &status = E.status;
-    ts = mk(sv[F_TS], sv[F_TS + 1], sv[F_TS + 2]); te = mk(sv[F_TE], sv[F_TE + 1], sv[F_TE + 2]);
-    u0 = sv[F_U0]; vbar = sv[F_VBAR]; fzbar = sv[F_FZBAR]; fzprev = sv[F_FZPREV]; dfz = sv[F_DFZ];
-    kst = sv[F_KST]; kdmp = sv[F_KDMP]; mu = sv[F_MU]; epret = sv[F_EPRET];
-    t = __float_as_int(sv[F_T]); touched = __float_as_int(sv[F_TOUCH]); episode = __float_as_int(sv[F_EPISODE]); status = __float_as_int(sv[F_STATUS]);
-    // sliders of this lane (lane l owns elements 5 l .. 5 l + 4): prefetched now, consumed after the arm phase
-    float s_pre[FE], sd_pre[FE];
-#pragma unroll
-    for (int i = 0; i < FE; ++i) {
-        const int e = FE * gl + i;
-        s_pre[i] = 0.f; sd_pre[i] = 0.f;
-        if (MODE == 0 && e < NSH) { s_pre[i] = LAT(LATF_S + e); sd_pre[i] = LAT(LATF_SD + e); }
-    }
-    // the free body (spawn pose at a reset: ultrasound.py:426-431)
-    FullBody body;
-    body.p = mk(M.torso[0], M.torso[1], M.torso[2]); body.q[0] = 1.f; body.q[1] = body.q[2] = body.q[3] = 0.f; body.v = mk(0.f, 0.f, 0.f); body.w = mk(0.f, 0.f, 0.f);
-    if (MODE == 0) {
-        float bw[13];
-#pragma unroll
-        for (int a = 0; a < 13; ++a) bw[a] = LAT(LATF_BODY + a);
-        body.p = mk(bw[0], bw[1], bw[2]); body.q[0] = bw[3]; body.q[1] = bw[4]; body.q[2] = bw[5]; body.q[3] = bw[6];
-        body.v = mk(bw[7], bw[8], bw[9]); body.w = mk(bw[10], bw[11], bw[12]);
-    }
-
-    USIM_STAMP(io.dbg, 1);
-    // ---------------- action ----------------
-    float act[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (!reset_only) {
-        if (flags & LF_RANDOM_ACT) {
-            uint32_t gid = (uint32_t)(C.env_offset + ei);
-            u4 r1 = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 1u, C.key0, C.key1);
-            u4 r2 = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 2u, C.key0, C.key1);
-            uint32_t rr[8] = {r1.a, r1.b, r1.c, r1.d, r2.a, r2.b, r2.c, r2.d};
-#pragma unroll
-            for (int a = 0; a < 7; ++a) {
-                act[a] = synthetic_action(C, rr[a], a);
-                if (io.act_out && store && a < C.adim) io.act_out[(size_t)ei * C.adim + a] = act[a];
-            }
-        } else {
-#pragma unroll
-            for (int a = 0; a < 7; ++a) if (a < C.adim) act[a] = finite_or_zero(io.act[(size_t)ei * C.adim + a]);
-        }
-    }
-
-    bool need = reset_only ? (io.mask ? io.mask[ei] != 0 : true) : false;   // lanes that (re)initialise in pass 1
-    if (refill) need = valid;
-    bool done = false;
-    const float dt = C.dt, inv_h = rcp_((float)C.horizon);
-
-    constexpr int pass = MODE;                        // 0: step from the live state, 1: reset computation
-    int ep_t = episode;                               // episode index the reset draws are keyed on
-    do {
-        const bool active = (pass == 0) ? true : need;
-        if (pass == 1) {
-            if (!__any(need)) break;
-            if (need) {
-                // ================= reset draws (ultrasound.py:416-478) =================
-                ep_t = refill ? item_ep : episode + 1;                   // listed bank episode, or the live reset
-                if (!refill) episode = ep_t;
-                uint32_t gid = (uint32_t)(C.env_offset + ei);
-                u4 A = philox(gid, (uint32_t)ep_t, 0u, 0u, C.key0, C.key1);
-                u4 B = philox(gid, (uint32_t)ep_t, 1u, 0u, C.key0, C.key1);
-                u4 Cc = philox(gid, (uint32_t)ep_t, 2u, 0u, C.key0, C.key1);
-                const float tz = M.torso[2] + M.base[2] + C.top_off;      // ultrasound.py:184,807
-                f3 noise = mk(0, 0, 0);
-                kst = C.stiffness; kdmp = C.damping;
-                if (io.reset_params) {
-                    const float* p = io.reset_params + (size_t)ei * 13;
-                    ts = mk(p[0], p[1], p[2]); te = mk(p[3], p[4], p[5]); u0 = p[6]; noise = mk(p[7], p[8], p[9]);
-                    kst = p[10]; kdmp = p[11]; mu = p[12];
-                } else {
-                    if (C.det_traj) { ts = mk(0.062f, -0.020f, 0.896f); te = mk(-0.032f, -0.075f, 0.896f); }   // ultrasound.py:763-764
-                    else {
-                        // ultrasound.py:787-788: np.linspace grids over the torso top, 50 points each
-                        const float tx = M.torso[0] + M.base[0], ty = M.torso[1] + M.base[1];
-                        const float xs = -0.15f + tx + 0.03f, xstep = (0.15f + tx - xs) / 49.f;
-                        const float ys = -C.y_range + ty, ystep = 2.f * C.y_range / 49.f;
-                        ts = mk(xs + (float)urange(A.a, 50u) * xstep, ys + (float)urange(A.b, 50u) * ystep, tz);
-                        te = mk(xs + (float)urange(A.c, 50u) * xstep, ys + (float)urange(A.d, 50u) * ystep, tz);
-                    }
-                    u0 = u01(B.a);                                           // ultrasound.py:443
-                    if (C.rand_pos) {                                        // ultrasound.py:880-881
-                        float r1 = sqrtf(-2.f * logf(u01_open(B.b))), th1 = 2.f * PI_F * u01(B.c);
-                        float r2 = sqrtf(-2.f * logf(u01_open(B.d))), th2 = 2.f * PI_F * u01(Cc.a);
-                        noise = mk(r1 * cosf(th1) * 0.0025f, r1 * sinf(th1) * 0.0025f, r2 * cosf(th2) * 0.010f);
-                    }
-                    if (C.rand_solref) { kst = 1300.f + (float)urange(Cc.b, 300u); kdmp = 17.f + (float)urange(Cc.c, 24u); }   // ultrasound.py:293-294
-                    float pf = C.probe_fric;
-                    if (C.rand_fric) pf *= 0.5f + 1.5f * u01(Cc.d);
-                    mu = fmaxf(pf, C.elem_fric);
-            if (C.probe_geoms == 2 && !C.pair) mu = 0.5f * (mu + fmaxf(C.probe_fric2, C.elem_fric));   // two coincident contacts per pair restated as one (usim_config.probe_geoms)
-                }
-                // ================= initial pose: damped-least-squares IK from init_qpos (ultrasound.py:812-844) ==========
-                float uu = clampf(u0, 0.f, 1.f);
-                f3 tp0 = ts + (te - ts) * uu;
-                f3 target = mk(tp0.x + noise.x + M.ikb[0] - M.base[0], tp0.y + noise.y + M.ikb[1] - M.base[1], tp0.z + noise.z + M.ikb[2] - M.base[2]);
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) q[i] = INITQ[i];
-                for (int it = 0; it < C.ik_iters; ++it) {
-                    Kin K; fk(M, q, K);
-                    f3 gx = mk(M.grot[0], M.grot[3], M.grot[6]), gy = mk(M.grot[1], M.grot[4], M.grot[7]), gz = mk(M.grot[2], M.grot[5], M.grot[8]);
-                    f3 eo = (cross(K.sx, gx) + cross(K.sy, gy) + cross(K.sz, gz)) * 0.5f;
-                    f3 ep = target - K.x;
-                    float e[6] = {ep.x, ep.y, ep.z, eo.x, eo.y, eo.z};
-                    float J[6][NJ];
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        f3 jv = cross(K.z[j], K.x - K.o[j]);
-                        J[0][j] = jv.x; J[1][j] = jv.y; J[2][j] = jv.z; J[3][j] = K.z[j].x; J[4][j] = K.z[j].y; J[5][j] = K.z[j].z;
-                    }
-                    float A6[21], id6[6];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a)
-#pragma unroll
-                        for (int b = 0; b <= a; ++b) {
-                            float s = (a == b) ? 1e-6f : 0.f;
-#pragma unroll
-                            for (int j = 0; j < NJ; ++j) s = fmaf(J[a][j], J[b][j], s);
-                            A6[PK(a, b)] = s;
-                        }
-                    chol_packed<6>(A6, id6);
-                    chol_solve<6>(A6, id6, e);
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        float s = 0.f;
-#pragma unroll
-                        for (int a = 0; a < 6; ++a) s = fmaf(J[a][j], e[a], s);
-                        q[j] += s;
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) { q0[i] = q[i]; qd[i] = 0.f; dq[i] = 0.f; }
-                episode_begin(E, 0);
-            }
-        } else {
-            t += 1;                                                  // MujocoEnv.step: timestep += 1
-        }
-
-        // =====================================================================================================
-        // forward pass at (q, qd): kinematics, dynamics, controller, constrained accelerations, sensors
-        // =====================================================================================================
-        StepOut R;
-        R.ncon = 0; R.overflow = 0;
-        float qacc[NJ];
-        f3 hv = mk(0, 0, 0);
-        float obs[OBS_DIM];
-        float pos_err_norm = 0.f, ori_err = 0.f;
-        if (active) {
-            Kin K; fk(M, q, K);
-            Dyn D; dynamics(M, K, qd, D);
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) D.M[PK(i, i)] += M.armature[i];          // rotor inertias (usim_config.armature_scale)
-            // site Jacobian J = [Jv; Jw]
-            float J[6][NJ];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                f3 jv = cross(K.z[j], K.x - K.o[j]);
-                J[0][j] = jv.x; J[1][j] = jv.y; J[2][j] = jv.z; J[3][j] = K.z[j].x; J[4][j] = K.z[j].y; J[5][j] = K.z[j].z;
-            }
-            float Lm[28], idm[NJ];
-#pragma unroll
-            for (int k = 0; k < 28; ++k) Lm[k] = D.M[k];
-            chol_packed<NJ>(Lm, idm);
-            // Lambda^-1 = J M^-1 J^T = Y^T Y with Y = Lm^-1 J^T (six forward substitutions only; packed lower 6x6)
-            float Li[21];
-            {
-                float Y[6][NJ];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) Y[a][j] = J[a][j];
-                    chol_forward<NJ>(Lm, idm, Y[a]);
-                }
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int b = 0; b <= a; ++b) {
-                        float s = 0.f;
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) s = fmaf(Y[a][j], Y[b][j], s);
-                        Li[PK(a, b)] = s;
-                    }
-            }
-            USIM_STAMP(io.dbg, 2);
-            // ---------------- OSC_POSE torque (robosuite osc.py run_controller; rl_config.yaml:33-51) ----------------
-            float tau[NJ];
-            if (pass == 0) {
-                float kp[6], kd[6];
-                f3 gpos, gx, gy, gz;
-                float up = clampf((float)(t - 1) * inv_h + u0, 0.f, 1.f);   // controller.traj_pos from the previous _post_action
-                f3 tpw = ts + (te - ts) * up;
-                if (C.mode == 1) {
-                    float d[6];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) d[a] = clampf(act[a], -1.f, 1.f) * (a < 3 ? C.out_pos : C.out_ori);
-                    gpos = K.x + mk(d[0], d[1], d[2]);
-                    float ang = sqrt_(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-                    if (ang < 1e-12f) { gx = K.sx; gy = K.sy; gz = K.sz; }
-                    else {
-                        float hh = 0.5f * ang, sh = sinf(hh) * rcp_(ang), qw = cosf(hh), qx = d[3] * sh, qy = d[4] * sh, qz = d[5] * sh;
-                        // rotation matrix of the delta quaternion, applied on the left of the current orientation
-                        f3 e0 = mk(1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy + qw * qz), 2.f * (qx * qz - qw * qy));
-                        f3 e1 = mk(2.f * (qx * qy - qw * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz + qw * qx));
-                        f3 e2 = mk(2.f * (qx * qz + qw * qy), 2.f * (qy * qz - qw * qx), 1.f - 2.f * (qx * qx + qy * qy));
-                        gx = e0 * K.sx.x + e1 * K.sx.y + e2 * K.sx.z;
-                        gy = e0 * K.sy.x + e1 * K.sy.y + e2 * K.sy.z;
-                        gz = e0 * K.sz.x + e1 * K.sz.y + e2 * K.sz.z;
-                    }
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) { kp[a] = C.kp_fixed; kd[a] = 2.f * sqrt_(C.kp_fixed) * C.damping_ratio; }
-                } else {
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) {
-                        float v = (C.mode == 3) ? 0.f : clampf(act[a], 0.f, 1.f);     // wrench mode: no impedance term
-                        kp[a] = C.kp_min + v * (C.kp_max - C.kp_min);
-                        kd[a] = 2.f * sqrt_(kp[a]) * C.damping_ratio;
-                    }
-                    gpos = mk(tpw.x - M.base[0], tpw.y - M.base[1], tpw.z - M.base[2]);
-                    if (C.mode == 2) gpos.z += clampf(act[6], -1.f, 1.f) * C.out_pos;
-                    gx = mk(M.grot[0], M.grot[3], M.grot[6]); gy = mk(M.grot[1], M.grot[4], M.grot[7]); gz = mk(M.grot[2], M.grot[5], M.grot[8]);
-                }
-                float v6[6];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) s = fmaf(J[a][j], qd[j], s);
-                    v6[a] = s;
-                }
-                f3 eo = (cross(K.sx, gx) + cross(K.sy, gy) + cross(K.sz, gz)) * 0.5f;
-                f3 ep = gpos - K.x;
-                float Fp[3] = {ep.x * kp[0] - v6[0] * kd[0], ep.y * kp[1] - v6[1] * kd[1], ep.z * kp[2] - v6[2] * kd[2]};
-                float Tp[3] = {eo.x * kp[3] - v6[3] * kd[3], eo.y * kp[4] - v6[4] * kd[4], eo.z * kp[5] - v6[5] * kd[5]};
-                if (C.mode == 3) {
-                    // fork-only "wrench" baseline (utils/plot.py:267-268; checkpoint action box [-10,10]^6): the action takes the place
-                    // of desired_force / desired_torque in the OSC law, i.e. wrench = [Lambda_pos a_f; Lambda_ori a_t].  Inferred; the
-                    // shipped `wrench` policy replayed under this reading earns 9.2 reward/step (8.6 on MuJoCo), under "action =
-                    // wrench" it fails within 80 steps (tests/test_gpu_policy_replay.py)
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) { Fp[a] = clampf(act[a], -WRENCH_MAX, WRENCH_MAX); Tp[a] = clampf(act[3 + a], -WRENCH_MAX, WRENCH_MAX); }
-                }
-                // lambda_pos F, lambda_ori T : solves with the 3x3 diagonal blocks of Li (uncouple_pos_ori, rl_config.yaml:48)
-                {
-                    float P3[6] = {Li[PK(0, 0)], Li[PK(1, 0)], Li[PK(1, 1)], Li[PK(2, 0)], Li[PK(2, 1)], Li[PK(2, 2)]}, ip[3];
-                    chol_packed<3>(P3, ip); chol_solve<3>(P3, ip, Fp);
-                    float O3[6] = {Li[PK(3, 3)], Li[PK(4, 3)], Li[PK(4, 4)], Li[PK(5, 3)], Li[PK(5, 4)], Li[PK(5, 5)]}, io3[3];
-                    chol_packed<3>(O3, io3); chol_solve<3>(O3, io3, Tp);
-                }
-                float wr[6] = {Fp[0], Fp[1], Fp[2], Tp[0], Tp[1], Tp[2]};
-                // nullspace torque N^T M (10 (q0 - q) - 2 sqrt(10) qd)
-                float pt[NJ], y[NJ];
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) pt[i] = 10.f * (q0[i] - q[i]) - 6.3245553203367586f * qd[i];
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) s = fmaf((i >= j) ? D.M[PK(i, j)] : D.M[PK(j, i)], pt[j], s);
-                    y[i] = s;
-                }
-                float jb[6];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) s = fmaf(J[a][j], pt[j], s);      // (M^-1 J^T)^T (M pt) = J pt
-                    jb[a] = s;
-                }
-                {
-                    float L6[21], i6[6];
-#pragma unroll
-                    for (int k = 0; k < 21; ++k) L6[k] = Li[k];
-                    chol_packed<6>(L6, i6); chol_solve<6>(L6, i6, jb);
-                }
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) {
-                    float s = D.bias[i] + y[i];
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) s = fmaf(J[a][i], wr[a] - jb[a], s);
-                    tau[i] = clampf(s, -TAUMAX[i], TAUMAX[i]);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) tau[i] = 0.f;      // reset: sim.forward() with zero ctrl
-            }
-            if (pass == 0 && store && io.log) {
-                // torque and action channels of the episode record leave the registers here instead of living to the end of the step
-                float* L = io.log + (size_t)ei * LOG_WIDTH;
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) L[33 + i] = tau[i];
-#pragma unroll
-                for (int a = 0; a < 7; ++a) L[46 + a] = act[a];
-            }
-            USIM_STAMP(io.dbg, 3);
-            // ---------------- smooth acceleration ----------------
-            float qs[NJ];
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) qs[i] = tau[i] - D.bias[i] - JOINT_DAMP * qd[i];
-            chol_solve<NJ>(Lm, idm, qs);
-            joint_friction(D.M, Lm, idm, qd, C.frictionloss, qs);
-
-            float W[6] = {0, 0, 0, 0, 0, 0};          // site-space wrench of the contact forces
-            float full_chk = 0.f;                     // |free body| + sum |sliders| after the integration, for the numerical fault guard
-            // ---------------- torso (usim_full.h): 270 sliders on the free body, probe and table contacts ----------------
-            float alpha[6], vs[6];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                float s = 0.f, u = 0.f;
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) { s = fmaf(J[a][j], qs[j], s); u = fmaf(J[a][j], qd[j], u); }
-                alpha[a] = s; vs[a] = u;
-            }
-            float acc_e[FE], ab[6], lat_chk = 0.f;
-            int cel[MAXC], nc = 0, ovf = 0;
-            // (the contact solve starts from the forces of the previous physics step, kept in the environment's lattice block; a reset pass starts cold and leaves none)
-            float* const latp = &LAT(0);
-            full_forward(lds, gl, M, C, kst, kdmp, mu, s_pre, sd_pre, body, K.x, K.sx, K.sy, K.sz, Li, alpha, vs, W, acc_e, ab, nc, cel, ovf,
-                         (pass == 0) ? latp : nullptr, (pass == 0 && valid) ? latp : nullptr);
-            // The arm quantities the rest of the pass needs (kinematics, mass matrix and its factor, bias, site Jacobian: ~250 words) are formed AGAIN here, from joint
-            // state the compiler cannot recognise, instead of living through the contact solve: 2.5 k instructions against the solve's 700 k, and without them the
-            // kernel fits 256 registers with no scratch -- two environments per SIMD.  Same inputs, same instructions: the same bits.
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) asm volatile("" : "+v"(q[i]), "+v"(qd[i]));
-            fk(M, q, K);
-            dynamics(M, K, qd, D);
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) D.M[PK(i, i)] += M.armature[i];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                f3 jv = cross(K.z[j], K.x - K.o[j]);
-                J[0][j] = jv.x; J[1][j] = jv.y; J[2][j] = jv.z; J[3][j] = K.z[j].x; J[4][j] = K.z[j].y; J[5][j] = K.z[j].z;
-            }
-#pragma unroll
-            for (int k = 0; k < 28; ++k) Lm[k] = D.M[k];
-            chol_packed<NJ>(Lm, idm);
-            R.ncon = nc; R.overflow = ovf;
-#pragma unroll
-            for (int k = 0; k < MAXC; ++k) R.con_shell[k] = cel[k];
-            // semi-implicit Euler: sliders; free body (linear part in world axes, angular velocity in the body frame, quaternion by the exponential of dt w / 2)
-#pragma unroll
-            for (int i = 0; i < FE; ++i) {
-                const int e = FE * gl + i;
-                float sdn = 0.f, sn = 0.f;
-                if (pass == 0) { sdn = fmaf(dt, acc_e[i], sd_pre[i]); sn = fmaf(dt, sdn, s_pre[i]); }
-                if (valid && e < NSH && (pass == 0 || !refill)) { LAT(LATF_SD + e) = sdn; LAT(LATF_S + e) = sn; }
-                if (e < NSH) lat_chk += fabsf(sn) + 1e-3f * fabsf(sdn);
-            }
-            if (pass == 0) {
-                const float qw = body.q[0], qx = body.q[1], qy = body.q[2], qz = body.q[3];
-                const f3 abl = mk(ab[0], ab[1], ab[2]);
-                const f3 aw = mk((1.f - 2.f * (qy * qy + qz * qz)) * abl.x + 2.f * (qx * qy - qw * qz) * abl.y + 2.f * (qx * qz + qw * qy) * abl.z,
-                                 2.f * (qx * qy + qw * qz) * abl.x + (1.f - 2.f * (qx * qx + qz * qz)) * abl.y + 2.f * (qy * qz - qw * qx) * abl.z,
-                                 2.f * (qx * qz - qw * qy) * abl.x + 2.f * (qy * qz + qw * qx) * abl.y + (1.f - 2.f * (qx * qx + qy * qy)) * abl.z);
-                body.v = madd(body.v, aw, dt); body.p = madd(body.p, body.v, dt);
-                body.w = madd(body.w, mk(ab[3], ab[4], ab[5]), dt);
-                const float wn = sqrt_(dot(body.w, body.w)), hh = 0.5f * dt * wn;
-                float shh, chh; sincosf(hh, &shh, &chh);
-                const float sh = (wn > 1e-12f) ? shh * rcp_(wn) : 0.5f * dt;
-                const float dx = body.w.x * sh, dy = body.w.y * sh, dz2 = body.w.z * sh;
-                const float n0 = qw * chh - qx * dx - qy * dy - qz * dz2, n1 = qw * dx + qx * chh + qy * dz2 - qz * dy;
-                const float n2 = qw * dy - qx * dz2 + qy * chh + qz * dx, n3 = qw * dz2 + qx * dy - qy * dx + qz * chh;
-                const float irn = rsq_(n0 * n0 + n1 * n1 + n2 * n2 + n3 * n3);
-                body.q[0] = n0 * irn; body.q[1] = n1 * irn; body.q[2] = n2 * irn; body.q[3] = n3 * irn;
-                // what the numerical fault guard below sees of the torso: the free body's 13 words and every slider (a non-finite word makes the sum non-finite; without
-                // this a torso gone NaN fails every comparison of full_forward, its contacts vanish silently and the arm -- all the guard used to look at -- stays finite)
-                full_chk = wave_sum(lat_chk) + fabsf(body.p.x) + fabsf(body.p.y) + fabsf(body.p.z) + fabsf(body.q[0]) + fabsf(body.q[1]) + fabsf(body.q[2]) + fabsf(body.q[3])
-                         + 1e-3f * (fabsf(body.v.x) + fabsf(body.v.y) + fabsf(body.v.z) + fabsf(body.w.x) + fabsf(body.w.y) + fabsf(body.w.z));
-            }
-            if (store && (pass == 0 || !refill)) {
-                const float bw[13] = {body.p.x, body.p.y, body.p.z, body.q[0], body.q[1], body.q[2], body.q[3], body.v.x, body.v.y, body.v.z, body.w.x, body.w.y, body.w.z};
-#pragma unroll
-                for (int a = 0; a < 13; ++a) LAT(LATF_BODY + a) = bw[a];
-            }
-            if (pass == 1 && valid && !refill) {                         // a reset of the live state: the episode starts without a warm start
-                for (int w = gl; w < LATF_WARM_WORDS; w += G) LAT(LATF_WTAB + w) = (w >= 4 * NSH && w < 4 * NSH + 8) ? __int_as_float(-1) : 0.f;
-            }
-            USIM_STAMP(io.dbg, 12);
-            // ---------------- constrained arm acceleration: qacc = qs + M^-1 J^T W ----------------
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) qacc[i] = qs[i];
-            {
-                float z[NJ];
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) s = fmaf(J[a][i], W[a], s);
-                    z[i] = s;
-                }
-                chol_solve<NJ>(Lm, idm, z);
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) qacc[i] += z[i];
-            }
-            R.fc[0] = W[0]; R.fc[1] = W[1]; R.fc[2] = W[2];
-            // ---------------- torque sensor at ft_frame (MuJoCo cfrc_int of the probe body, site frame) ----------------
-            {
-                // link-7 accelerations from the site Jacobian: alpha = alpha_bias + Jw qacc, a(o7) = a_bias + Jv qacc - (Jw qacc) x (x - o7)
-                float aq[6];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    float sacc = 0.f;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) sacc = fmaf(J[a][j], qacc[j], sacc);
-                    aq[a] = sacc;
-                }
-                const f3 alq = mk(aq[3], aq[4], aq[5]);
-                f3 al = D.al7 + alq;
-                f3 a7 = D.a7 + mk(aq[0], aq[1], aq[2]) - cross(alq, K.x - K.o[NJ - 1]);
-                f3 rc = K.r7x * M.pcom7[0] + K.r7y * M.pcom7[1] + K.r7z * M.pcom7[2];
-                f3 ac = a7 + cross(al, rc) + cross(D.w7, cross(D.w7, rc));
-                f3 N = rot_inertia_mul(K, M.pI7, al) + cross(D.w7, rot_inertia_mul(K, M.pI7, D.w7));
-                f3 Fp = ac * PROBE_MASS;
-                f3 tw = N + cross(K.o[NJ - 1] + rc - K.x, Fp) - mk(W[3], W[4], W[5]);
-                R.tq[0] = dot(K.sx, tw); R.tq[1] = dot(K.sy, tw); R.tq[2] = dot(K.sz, tw);
-            }
-            USIM_STAMP(io.dbg, 13);
-            // ---------------- integrate the arm: mj_Euler with implicit joint damping ----------------
-            if (pass == 0) {
-                // (M + h D) x = M qacc with D = d I, h d = 2e-5: x = qacc - h d M^-1 x.  One step from x = qacc reuses the factor of M; the
-                // contraction is h d / lambda_min(M) = 2.8e-4 (lambda_min(M) = 0.071 kg m^2 over the workspace), so the remainder
-                // is 8e-8 relative -- fp32 rounding.  No second factorisation, and the mass matrix is dead before the contact phase.
-                float rhs[NJ];
-                {
-                    const float hd = dt * JOINT_DAMP;
-                    float xk[NJ];
-#pragma unroll
-                    for (int i = 0; i < NJ; ++i) xk[i] = qacc[i];
-                    chol_solve<NJ>(Lm, idm, xk);
-#pragma unroll
-                    for (int i = 0; i < NJ; ++i) rhs[i] = fmaf(-hd, xk[i], qacc[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < NJ; ++i) { qd[i] = fmaf(dt, rhs[i], qd[i]); dq[i] = fmaf(dt, qd[i], dq[i]); q[i] = q0[i] + dq[i]; }
-                // hand velocity: Jacobian from before the integration, qvel from after (mj_step data semantics)
-                float vs2[6];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) s = fmaf(J[a][j], qd[j], s);
-                    vs2[a] = s;
-                }
-                hv = mk(vs2[0], vs2[1], vs2[2]) + cross(mk(vs2[3], vs2[4], vs2[5]), K.hand - K.x);
-            }
-            USIM_STAMP(io.dbg, 14);
-            // ---------------- observation (ultrasound.py:363-401) ----------------
-            {
-                const int tprev = (pass == 0) ? t - 1 : 0;
-                float up = clampf((float)tprev * inv_h + u0, 0.f, 1.f);
-                f3 tpw = ts + (te - ts) * up;
-                if (pass == 1) fzbar = R.fc[2];                          // ultrasound.py:477
-                obs[0] = R.fc[0]; obs[1] = R.fc[1]; obs[2] = R.fc[2];
-                obs[3] = R.tq[0]; obs[4] = R.tq[1]; obs[5] = R.tq[2];
-                obs[6] = hv.x; obs[7] = hv.y; obs[8] = hv.z;
-                obs[9] = fzbar - 5.0f; obs[10] = dfz - 0.0f; obs[11] = vbar - 0.04f;
-                f3 xw = mk(K.x.x + M.base[0], K.x.y + M.base[1], K.x.z + M.base[2]);
-                obs[12] = xw.x - tpw.x; obs[13] = xw.y - tpw.y; obs[14] = xw.z - tpw.z;
-                float qe[4]; mat2quat_xyzw(K.sx, K.sy, K.sz, qe);
-                difference_quat(qe, M.gquat, obs + 15);               // xyzw arrays through the wxyz routine (ultrasound.py:390)
-                if (pass == 0) {
-                    // ---------------- reward (ultrasound.py:230-269) ----------------
-                    const bool contact = R.ncon > 0;
-                    if (contact) touched = 1;
-                    float pe0 = 90.f * (xw.x - tpw.x), pe1 = 90.f * (xw.y - tpw.y);
-                    pe0 *= pe0; pe1 *= pe1;
-                    pos_err_norm = sqrt_(pe0 * pe0 + pe1 * pe1);
-                    float pos_rew = 5.f * exp_(-pos_err_norm);
-                    float qc[4] = {qe[3], qe[0], qe[1], qe[2]};
-                    ori_err = 0.2f * distance_quat_goal(qc, M.ghat, M.geps);
-                    float ori_rew = exp_(-ori_err);
-                    float ve = 45.f * (vbar - 0.04f); ve *= ve;
-                    float vel_rew = exp_(-ve);
-                    float fe = 0.7f * (fzbar - 5.f); fe *= fe;
-                    float force_rew = contact ? 3.f * exp_(-fe) : 0.f;
-                    float de = 0.01f * dfz; de *= de;
-                    float dforce_rew = contact ? 2.f * exp_(-de) : 0.f;
-                    float reward = pos_rew + ori_rew + vel_rew + force_rew + dforce_rew;
-                    done = t >= C.horizon;
-                    // ---------------- bookkeeping (ultrasound.py:528-546) ----------------
-                    float hvn = sqrt_(dot(hv, hv));
-                    vbar += (hvn - vbar) * rcp_((float)t);
-                    float fz = R.fc[2];
-                    dfz = (fz - fzprev) * rcp_(C.dt_ctrl);                 // ultrasound.py:542: self.control_timestep
-                    fzprev = fz;
-                    fzbar = 0.1f * fz + 0.9f * fzbar;
-                    if (C.early_term) {                                // ultrasound.py:635-670
-                        bool term = false;
-#pragma unroll
-                        for (int i = 0; i < NJ; ++i) term = term || (q[i] < QMIN[i] + 0.1f) || (q[i] > QMAX[i] - 0.1f);
-                        term = term || (pos_err_norm > 1.0f) || (contact && ori_err > 0.10f) || (touched && !contact);
-                        done = done || term;
-                    }
-                    epret += reward;
-                    if (store && io.log) {
-                        // per-step episode record in the order of the reference's CSV dump (ultrasound.py:552-614)
-                        float* L = io.log + (size_t)ei * LOG_WIDTH;
-                        const float upn = clampf((float)t * inv_h + u0, 0.f, 1.f);
-                        const f3 tpn = ts + (te - ts) * upn;                                    // trajectory point after this step's update (:532)
-                        L[0] = xw.x; L[1] = xw.y; L[2] = xw.z; L[3] = tpn.x; L[4] = tpn.y; L[5] = tpn.z;
-                        L[6] = hv.x; L[7] = hv.y; L[8] = hv.z; L[9] = 0.04f; L[10] = vbar;
-                        L[11] = qe[0]; L[12] = qe[1]; L[13] = qe[2]; L[14] = qe[3];
-                        L[15] = M.gquat[0]; L[16] = M.gquat[1]; L[17] = M.gquat[2]; L[18] = M.gquat[3];
-                        L[19] = ori_err * 5.0f;                                                 // distance_quat (ori_err = 0.2 * distance)
-                        L[20] = fz; L[21] = 5.0f; L[22] = fzbar; L[23] = dfz; L[24] = 0.f; L[25] = contact ? 1.f : 0.f;
-#pragma unroll
-                        for (int i = 0; i < NJ; ++i) L[26 + i] = q[i];
-                        L[40] = (float)(t - 1) * inv_h * 100.f;
-                        L[41] = pos_rew; L[42] = ori_rew; L[43] = vel_rew; L[44] = force_rew; L[45] = dforce_rew;
-                    }
-                    if (R.overflow) status |= R.overflow & 3;                            // (bit 1: more element-table contacts than the kernel keeps)
-                    {
-                        // numerical fault guard: a non-finite or run-away state ends the episode and is flagged
-                        float chk = full_chk;
-#pragma unroll
-                        for (int i = 0; i < NJ; ++i) chk += fabsf(q[i]) + 1e-3f * fabsf(qd[i]);
-                        if (!(chk < 1.0e3f)) { status |= 4; done = true; epret -= reward; reward = 0.f; if (!(epret == epret)) epret = 0.f; }
-                    }
-                    if (store) {
-                        io.rew[ei] = reward;
-                        if (io.status_out) io.status_out[ei] = status;
-                        io.done[ei] = done ? 1 : 0;
-                        if (io.contacts) {
-                            io.contacts[(size_t)ei * (1 + MAXC)] = R.ncon;
-#pragma unroll
-                            for (int k = 0; k < MAXC; ++k) io.contacts[(size_t)ei * (1 + MAXC) + 1 + k] = R.con_shell[k];
-                        }
-                        if (done) {
-                            if (io.term_obs) {
-#pragma unroll
-                                for (int a = 0; a < OBS_DIM; ++a) io.term_obs[(size_t)ei * OBS_DIM + a] = obs[a];
-                            }
-                            if (io.ep_ret) io.ep_ret[ei] = epret;
-                            if (io.ep_len) io.ep_len[ei] = t;
-                        }
-                    }
-                    need = done && auto_reset;
-                }
-                if (pass == 1 && refill) {
-                    // reset computed ahead of time: park it in the bank slot of episode ep_t
-                    if (store && need) {
-                        const int sl = ep_t & (BANK_DEPTH - 1);
-#pragma unroll
-                        for (int i = 0; i < NJ; ++i) BK(sl, BQ0 + i) = q[i];
-                        BK(sl, BTS) = ts.x; BK(sl, BTS + 1) = ts.y; BK(sl, BTS + 2) = ts.z; BK(sl, BTE) = te.x; BK(sl, BTE + 1) = te.y; BK(sl, BTE + 2) = te.z;
-                        BK(sl, BU0) = u0; BK(sl, BKST) = kst; BK(sl, BKDMP) = kdmp; BK(sl, BMU) = mu; BK(sl, BFZ) = fzbar;
-#pragma unroll
-                        for (int a = 0; a < OBS_DIM; ++a) BK(sl, BOBS + a) = obs[a];
-                        BKI(sl, BSTATUS) = R.overflow & 3;
-                    }
-                } else if (store && io.obs && (pass == 1 ? need : !need)) {
-#pragma unroll
-                    for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = obs[a];
-                }
-                if (pass == 1 && R.overflow) status |= R.overflow & 3;
-            }
-        }
-    } while (0);
-
-    if (MODE == 0 && need) {
-        // ================= auto-reset: adopt the initial state prepared in the reset bank (SB3 VecEnv semantics: the
-        // observation returned for a finished environment is its reset observation) and queue the slot for refill ==========
-        episode += 1;
-        const int sl = episode & (BANK_DEPTH - 1);
-#pragma unroll
-        for (int i = 0; i < NJ; ++i) { q[i] = BK(sl, BQ0 + i); q0[i] = q[i]; qd[i] = 0.f; dq[i] = 0.f; }
-        ts = mk(BK(sl, BTS), BK(sl, BTS + 1), BK(sl, BTS + 2)); te = mk(BK(sl, BTE), BK(sl, BTE + 1), BK(sl, BTE + 2));
-        u0 = BK(sl, BU0); kst = BK(sl, BKST); kdmp = BK(sl, BKDMP); mu = BK(sl, BMU); fzbar = BK(sl, BFZ);
-        episode_begin(E, BKI(sl, BSTATUS));
-        if (store && io.obs) {
-#pragma unroll
-            for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = BK(sl, BOBS + a);
-        }
-        if (valid) {
-            // (every word by the lane that wrote it in the step above)
-            for (int i = 0; i < FE; ++i) { const int e = FE * gl + i; if (e < NSH) { LAT(LATF_S + e) = 0.f; LAT(LATF_SD + e) = 0.f; } }
-            if (gl == 0) {
-                const float bw[13] = {M.torso[0], M.torso[1], M.torso[2], 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                for (int a = 0; a < 13; ++a) LAT(LATF_BODY + a) = bw[a];
-            }
-            group_sync();                                                    // (the step above left its warm start through other lanes)
-            for (int w = gl; w < LATF_WARM_WORDS; w += G) LAT(LATF_WTAB + w) = (w >= 4 * NSH && w < 4 * NSH + 8) ? __int_as_float(-1) : 0.f;
-        }
-        if (store) order_refill(io, env, episode);
-    }
-
-    USIM_STAMP(io.dbg, 15);
-    // ---------------- store state ----------------
-    if (store && !(MODE == 1 && (refill || !need))) {
-        {
-            // 16-byte stores of the quads that hold a changed word (q, qd | running statistics | counters); the quads of per-episode
-            // constants only when an episode starts
-            float o[F_NSCALAR];
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) { o[F_Q + i] = dq[i]; o[F_QD + i] = qd[i]; o[F_Q0 + i] = q0[i]; }
-            o[F_TS] = ts.x; o[F_TS + 1] = ts.y; o[F_TS + 2] = ts.z; o[F_TE] = te.x; o[F_TE + 1] = te.y; o[F_TE + 2] = te.z;
-            o[F_U0] = u0; o[F_VBAR] = vbar; o[F_FZBAR] = fzbar; o[F_FZPREV] = fzprev; o[F_DFZ] = dfz;
-            o[F_KST] = kst; o[F_KDMP] = kdmp; o[F_MU] = mu; o[F_EPRET] = epret;
-            o[F_T] = __int_as_float(t); o[F_TOUCH] = __int_as_float(touched); o[F_EPISODE] = __int_as_float(episode); o[F_STATUS] = __int_as_float(status);
-            float4* sp = reinterpret_cast<float4*>(st + scalar_index(0, (size_t)ei));
-            const bool all = (MODE == 1) || need;
-#pragma unroll
-            for (int v = 0; v < F_NSCALAR / 4; ++v) {
-                const bool changed = (v <= 3) || v == 7 || v == 8 || v == 9;      // words 0-15 (q, qd, q0[0..1]), 28-31, 32-39
-                if (changed || all) sp[v] = make_float4(o[4 * v], o[4 * v + 1], o[4 * v + 2], o[4 * v + 3]);
-            }
-        }
-    }
-#undef ST
-#undef STI
-#undef LAT
-    if (refill) group_sync();                         // next item reuses the per-environment LDS block
-    }   // item loop
-    if (MODE == 1 && refill) work_list_close(io);
-    USIM_STAMP(io.dbg, 16);
-}
+#include "usim_full.h"
 
 // work items (env, episode + k), k = 1..BANK_DEPTH, for the environments selected by mask (reset / set_state paths)
 __global__ void usim_bank_items_kernel(const float* __restrict__ st, int n, const uint8_t* __restrict__ mask, int2* items, int* count) {

@@ -286,7 +286,7 @@ struct Carry {
 };
 
 template <int TORSO, int ROLE, int G> constexpr int arm_lds_base() {
-    return ROLE != 0 ? x2_base<G>() + (64 * wpr<G>() / G) * X2_STRIDE : (TORSO ? GroupGeom<16>::LDS_WORDS : 16 * X16_RIGID_STRIDE);
+    return ROLE != 0 ? x2_base<G>() + (64 * wpr<G>() / G) * X2_STRIDE : (TORSO ? SOFT16_LDS_WORDS : 16 * X16_RIGID_STRIDE);
 }
 static_assert((arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS) * 4 <= 160 * 1024 && arm_lds_base<1, 1, 8>() % 4 == 0 && arm_lds_base<1, 1, 16>() % 4 == 0 && arm_lds_base<1, 0, 16>() % 4 == 0
               && arm_lds_base<0, 0, 16>() % 4 == 0, "arm table behind the LDS blocks of every 16-lane kernel");

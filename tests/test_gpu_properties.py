@@ -191,6 +191,31 @@ def test_full_torso_checkpoint_determinism_and_auto_reset(usim):
     e.close()
 
 
+def test_full_torso_banked_reset_equals_live_reset(usim):
+    """torso="full": an episode adopted from the reset bank (computed ahead by a refill launch, parked in the bank, adopted inside the step that ends the episode
+    before it) is bit for bit the episode that a live reset of the same environment and episode index computes: reset draws, initial-pose IK, zero-torque forward
+    pass, park and adopt.  Horizon 12 without early termination: every episode of handle A ends at step 12; handle B gets to the same episode index by resets only."""
+    kw = usim.default_robosuite_kwargs(); kw["horizon"] = 12; kw["early_termination"] = False
+    def mk():
+        return usim.UltrasoundVecEnv(64, device="cuda:0", seed=5, torso="full", **kw)
+    a, b = mk(), mk()
+    a.reset_tensor()
+    for k in range(12):
+        obs_a, _, done = a.step_tensor(a.random_actions_tensor(k))
+    assert done.all()
+    obs_a = obs_a.clone()
+    b.reset_tensor()
+    obs_b = b.reset_tensor().clone()
+    torch.cuda.synchronize()
+    sa, sb = a.get_state(), b.get_state()
+    assert np.array_equal(sa["episode"], sb["episode"])
+    assert torch.equal(obs_a, obs_b)
+    assert set(sa) == set(sb) and {"q", "qd", "body", "s", "sd", "solver_warm_start"} <= set(sa)
+    for k in sa:                                       # q, qd, q0 and every per-episode scalar; body, s, sd, solver_warm_start
+        assert np.array_equal(sa[k], sb[k]), k
+    a.close(); b.close()
+
+
 def test_full_torso_rejects_the_configurations_it_does_not_run(usim):
     """torso="full" runs the Panda at control_freq 500 (the reference's callers: rl_config.yaml:26, robots Panda); the UR5e (ultrasound.py:137) and control_freq below
     500 (ultrasound.py:119: physics substeps) are refused at creation with USIM_ERR_UNSUPPORTED and a message, not run as something else; the top-face model runs both."""

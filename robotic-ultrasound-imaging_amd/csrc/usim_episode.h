@@ -7,7 +7,7 @@
 // out with a different instruction schedule and register allocation (the callee is simplified on its own before it is inlined; synthetic_action
 // in step16_one changes 7 of the 14), which needs an A/B of its own.
 #pragma once
-// (included by usim_kernels.hip inside namespace usim, before usim_full.h)
+// (included by usim_kernels.hip inside namespace usim, after usim_contact.h, before usim_full.h)
 
 // the per-episode scalar words of the state (Field F_TS .. F_STATUS)
 struct Episode {

@@ -20,7 +20,7 @@
 //   * A visit is scalar work (the 3 x 3 block's cone_local) replicated in the lanes: the step is a chain of (contacts x sweeps) visits, ~1 k cycles each; the table visits
 //     are software-pipelined by hand (record and L^-1 words of the next contact are loaded during the current visit).
 #pragma once
-// (included by usim_kernels.hip inside namespace usim, after probe_sdf / group_sync / cone_local and usim_episode.h)
+// (included by usim_kernels.hip inside namespace usim, after probe_sdf / group_sync, cone_local of usim_contact.h and usim_episode.h)
 
 constexpr int NSH = 270;                      // shell elements (soft_box.xml:9 count="9 4 11")
 constexpr int FE = 5;                         // elements per lane: element e = FE * lane + i  (64 * 5 = 320 >= 270; elements >= 270 do not exist: mass-less, zero everywhere)
@@ -414,7 +414,7 @@ DI void full_forward(float* lds, const int lane, const DevModel& M, const DevCfg
         // ---- block Gauss-Seidel, order: probe contacts A, table contacts, probe contacts B; pgs_iters sweeps, cold start ----
         auto visit = [&](const float b00, const float b01, const float b02, const float b11, const float b12, const float b22, float (&r)[3], const float (&f)[3],
                          const float muv, float& lam, float (&fc)[3]) {
-            // cone_local (usim_kernels.hip), the continuous local solve of the top-face model's iteration, taken in full (Gauss-Seidel: no line search)
+            // cone_local (usim_contact.h), the continuous local solve of the top-face model's iteration, taken in full (Gauss-Seidel: no line search)
             float lam_new = lam;
             const bool haslim = cone_local(b00, b01, b02, b11, b12, b22, r[0], r[1], r[2], f[0], f[1], f[2], muv, lam_new, fc[0], fc[1], fc[2]);
             lam = haslim ? lam_new : lam;

@@ -1,11 +1,12 @@
 // usim_kernels.hip -- CDNA4 (gfx950) device code of the batched Ultrasound simulator; the translation unit is usim_api.hip, which includes it.
 //
 // This file holds
-//   - the lattice and contact phases of the soft torso (lattice_rhs, lattice_solve, collide_*, contact_overflow, contact_rows / contact_solve), which the 16-lane step kernels
-//     of usim_step16.h (rigid and soft torso, included at the end) call;
+//   - the LDS layout and the group primitives (group_sync, group_bcast) of the soft torso's top face, its lattice phases (lattice_rhs, lattice_solve) and its collision
+//     (collide_*, contact_overflow), which the 16-lane step kernels of usim_step16.h (rigid and soft torso, included at the end) call;
 //   - usim_bank_items_kernel (refill work list of the reset / set_state paths) and usim_random_actions_kernel (the synthetic actions).
-// The full torso -- its physics and its step / reset kernel usim_step_kernel<2, 64, MODE> -- is usim_full.h, included below.  Pieces of the env logic that the step
-// kernels share are in usim_episode.h.  Every step kernel replaces, per environment:
+// The contact solve of the top face (contact_rows / contact_solve and its phases) is usim_contact.h, the full torso -- its physics and its step / reset kernel
+// usim_step_kernel<2, 64, MODE> -- is usim_full.h, pieces of the env logic that the step kernels share are in usim_episode.h: all three included below.
+// Every step kernel replaces, per environment:
 //   a1 robosuite MujocoEnv.step driver            a2 OSC_POSE controller (rl_config.yaml:33-51)
 //   a3 MuJoCo mj_step (forward dynamics + soft constraints + Euler)
 //   a4 Ultrasound.reward  ultrasound.py:230-269   a5 sensors ultrasound.py:363-401
@@ -400,596 +401,7 @@ DI int collide_all(float* lds, const int eb, const int gl, const int gbase, cons
 }
 #undef EBF
 
-// sum over the lanes of a group, delivered to every lane (three or four DPP steps; lane k + 8 first, so that a 16-lane group whose halves carry the two contacts
-// of a pair adds in the order of an 8-lane group that holds both in one lane: the same bits)
-template <int G>
-DI float group_allsum(float x) {
-    if constexpr (G == 16) x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true));   // row_ror:8
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xf, 0xf, true));                         // row_half_mirror: k <-> 7 - k
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));                          // quad_perm [1 0 3 2]
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, true));                          // quad_perm [2 3 0 1]
-    return x;
-}
-
-// Two floats per lane, handled by the packed float32 instructions of the part (v_pk_fma_f32, v_pk_mul_f32, v_pk_add_f32: both halves in one issue slot): with 8-lane
-// groups a lane carries BOTH contacts of a probe-element pair, and their visits are the same instruction sequence on different data.  Every operation below is the
-// scalar one per component (IEEE fma / mul / add; v_rcp, v_rsq, min, max and the selects run once per half), so a pair visited in one lane has the bits of a pair
-// visited in lanes k and 8 + k of a 16-lane group.
-typedef float v2f __attribute__((ext_vector_type(2)));
-struct b2 { bool x, y; };
-template <class T> struct LaneVec;
-template <> struct LaneVec<float> {
-    typedef bool mask;
-    static DI float splat(float a) { return a; }
-    static DI float fma(float a, float b, float c) { return fmaf(a, b, c); }
-    static DI float rcp(float a) { return rcp_(a); }
-    static DI float rsq(float a) { return rsq_(a); }
-    static DI float max(float a, float b) { return fmaxf(a, b); }
-    static DI float min(float a, float b) { return fminf(a, b); }
-    static DI bool gt(float a, float b) { return a > b; }
-    static DI bool lt(float a, float b) { return a < b; }
-    static DI bool both(bool a, bool b) { return bool(int(a) & int(b)); }
-    static DI float sel(bool c, float a, float b) { return c ? a : b; }
-    static DI float hsum(float a) { return a; }                       // sum over the lane's virtual contacts, in their order
-    static DI float nsum(float a) { return -a; }                      // minus that sum, as the scalar code accumulates it: (-a0) - a1
-};
-template <> struct LaneVec<v2f> {
-    typedef b2 mask;
-    static DI v2f splat(float a) { return (v2f)(a); }
-    static DI v2f fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-    static DI v2f rcp(v2f a) { v2f r; r.x = rcp_(a.x); r.y = rcp_(a.y); return r; }
-    static DI v2f rsq(v2f a) { v2f r; r.x = rsq_(a.x); r.y = rsq_(a.y); return r; }
-    static DI v2f max(v2f a, v2f b) { v2f r; r.x = fmaxf(a.x, b.x); r.y = fmaxf(a.y, b.y); return r; }
-    static DI v2f min(v2f a, v2f b) { v2f r; r.x = fminf(a.x, b.x); r.y = fminf(a.y, b.y); return r; }
-    static DI b2 gt(v2f a, v2f b) { return b2{a.x > b.x, a.y > b.y}; }
-    static DI b2 lt(v2f a, v2f b) { return b2{a.x < b.x, a.y < b.y}; }
-    static DI b2 both(b2 a, b2 b) { return b2{bool(int(a.x) & int(b.x)), bool(int(a.y) & int(b.y))}; }
-    static DI v2f sel(b2 c, v2f a, v2f b) { v2f r; r.x = c.x ? a.x : b.x; r.y = c.y ? a.y : b.y; return r; }
-    static DI float hsum(v2f a) { return a.x + a.y; }
-    static DI float nsum(v2f a) { return -a.x - a.y; }
-};
-
-// One contact's block of the Jacobi iteration (oracle: cone_local_solve): from the force f, the residual r of its three rows and its block B (regulariser included),
-// a better force h of the cone |h_t| <= mu h_n for the block's own problem.
-//   (1) ray: exact line minimisation along the current force, f <- (1 + x) f, x >= -1;
-//   (2) second ray, always, from the new point and its residual: along (1, 0, 0) or, when friction alone makes a force pay (r_n < mu |r_t|), along
-//       (1, -mu r_t / |r_t|), x2 >= 0 -- a contact whose force the first ray has taken to zero starts again within the same visit, and the visit is a continuous
-//       function of its inputs (no switch that float32 and float64 could take differently);
-//   (3) friction with the normal fixed: the minimiser of the tangential 2 x 2 problem on the disc |t| <= mu n, t = -(B_tt + lambda I)^-1 r~ in adjugate form, one
-//       Newton step on the secular equation from the contact's lambda of the iteration before, radial clamp.
-// T = float: one contact per lane; T = v2f: the two contacts of a pair (same block, own residual, force, cone and multiplier) in the two halves.
-// Returns whether the contact has a friction disc (lambda is meaningful).
-template <class T>
-DI typename LaneVec<T>::mask cone_local(const T b00, const T b01, const T b02, const T b11, const T b12, const T b22, T r0, T r1, T r2,
-                                        const T f0, const T f1, const T f2, const T mu, T& lam, T& h0, T& h1, T& h2) {
-    typedef LaneVec<T> V;
-    const T Bf0 = V::fma(b02, f2, V::fma(b01, f1, b00 * f0)), Bf1 = V::fma(b12, f2, V::fma(b11, f1, b01 * f0)), Bf2 = V::fma(b22, f2, V::fma(b12, f1, b02 * f0));
-    const T vr = V::fma(f2, r2, V::fma(f1, r1, f0 * r0)), vBv = V::fma(f2, Bf2, V::fma(f1, Bf1, f0 * Bf0));
-    // (a force below 1e-10 N is left to the second ray: the damped steps of the iteration shrink a force that has to vanish geometrically, and once f0^2 underflows in
-    //  float32 the quotient is inf -- oracle: same threshold)
-    const T x = V::sel(V::gt(f0, V::splat(1e-10f)), V::max(-vr * V::rcp(vBv), V::splat(-1.f)), V::splat(0.f));
-    r0 = V::fma(x, Bf0, r0); r1 = V::fma(x, Bf1, r1); r2 = V::fma(x, Bf2, r2);
-    T n0 = V::fma(x, f0, f0), n1 = V::fma(x, f1, f1), n2 = V::fma(x, f2, f2);
-    const T rt2 = V::fma(r1, r1, r2 * r2);
-    const T irt = V::rsq(V::max(rt2, V::splat(1e-30f))), rtn = rt2 * irt;
-    const T sl = V::sel(V::both(V::gt(rt2, V::splat(0.f)), V::lt(r0, mu * rtn)), -mu * irt, V::splat(0.f));
-    const T u1 = sl * r1, u2 = sl * r2;                                            // second direction (1, u1, u2)
-    const T Bu0 = V::fma(b02, u2, V::fma(b01, u1, b00)), Bu1 = V::fma(b12, u2, V::fma(b11, u1, b01)), Bu2 = V::fma(b22, u2, V::fma(b12, u1, b02));
-    const T ur = V::fma(u2, r2, V::fma(u1, r1, r0)), uBu = V::fma(u2, Bu2, V::fma(u1, Bu1, Bu0));
-    const T x2 = V::max(-ur * V::rcp(uBu), V::splat(0.f));
-    n0 += x2; n1 = V::fma(x2, u1, n1); n2 = V::fma(x2, u2, n2);
-    r1 = V::fma(x2, Bu1, r1); r2 = V::fma(x2, Bu2, r2);
-    // friction on the disc |t| <= mu n0
-    const T lim = mu * n0;
-    // (a friction disc below 1e-7 N is no friction: the multiplier of such a disc is ~ |r~| / lim, and beyond 1e10 the squares below leave float32 -- oracle: same threshold)
-    const typename V::mask haslim = V::gt(lim, V::splat(1e-7f));
-    const T q1 = r1 - V::fma(b12, n2, b11 * n1), q2 = r2 - V::fma(b22, n2, b12 * n1);
-    T m11 = b11 + lam, m22 = b22 + lam, det = V::fma(m11, m22, -(b12 * b12));
-    T a1 = V::fma(m22, q1, -(b12 * q2)), a2 = V::fma(m11, q2, -(b12 * q1));
-    {
-        const T aa = V::fma(a1, a1, a2 * a2);
-        const T aAa = V::fma(m11 * a2, a2, V::fma(m22 * a1, a1, -2.f * b12 * a1 * a2));
-        const T an = aa * V::rsq(V::max(aa, V::splat(1e-30f)));
-        lam = V::max(V::fma(V::fma(-det, lim, an) * aa, V::rcp(V::max(lim * aAa, V::splat(1e-30f))), lam), V::splat(0.f));
-    }
-    m11 = b11 + lam; m22 = b22 + lam; det = V::fma(m11, m22, -(b12 * b12));
-    a1 = V::fma(m22, q1, -(b12 * q2)); a2 = V::fma(m11, q2, -(b12 * q1));
-    const T aa = V::fma(a1, a1, a2 * a2);
-    const T sc = -V::min(lim * V::rsq(aa), V::rcp(det));                           // (v_min keeps the number when aa = 0 makes the product inf or NaN)
-    h0 = n0; h1 = V::sel(haslim, a1 * sc, V::splat(0.f)); h2 = V::sel(haslim, a2 * sc, V::splat(0.f));
-    return haslim;
-}
-
-// Contact solve of one forward pass (called when some environment of the wave has a contact): contact k of an environment lives in the
-// registers of lane k of its group.  Inputs: contact records in LDS (collide_queue, contact_overflow), element indices cel[], the site-space operator
-// Lambda^-1 (packed lower 6 x 6), the site acceleration / velocity of the unconstrained arm (alpha, vs).  Outputs: net contact wrench on the
-// site W[6] (accumulated) and the impulse gf[k] along each contact's element axis.
-// The arm-independent half of a contact lane's set-up (everything the row needs from the record, the lattice tables and the element state): the split
-// kernel's lattice side runs it before hand-off (2), while the arm side still forms Lambda^-1.
-struct ContactRows {
-    float w[3][6], g[3], Rd[3], Km[MAXC], vrel0[3], ae0, kdist;
-};
-// Kept contact list of an environment (usim_config.warm_start; oracle: uso_env.warm_el / warm_fv / warm_lamv): the element of every contact slot of the previous
-// physics step with the force and the friction multiplier of its two virtual contacts.  The lane that runs a slot's visits keeps its record -- T = float: 16-lane
-// groups, contact A of slot k in lane k, contact B in lane 8 + k; T = v2f: 8-lane groups, both in lane k -- in registers from step to step of a multi-step launch and
-// in the environment's warm rows in HBM (usim_device.h WARM_*: one layout for every mapping) across launches.  NoWarm: handles without a warm start carry nothing.
-struct NoWarm {};
-template <class T> struct WarmRec { int el; T f[3], lam; };
-template <int G> struct WarmOf { typedef WarmRec<typename std::conditional<G == 16, float, v2f>::type> type; };
-template <class T> DI void warm_clear(WarmRec<T>& r) { r.el = -1; r.f[0] = r.f[1] = r.f[2] = r.lam = LaneVec<T>::splat(0.f); }
-DI void warm_clear(NoWarm&) {}
-// an environment's warm rows <-> the records of its group's lanes (every lane of the group calls; 16-byte accesses)
-DI void warm_load(const float* wp, const int gl, WarmRec<float>& r) {
-    const float4 x = *reinterpret_cast<const float4*>(wp + WARM_F + 4 * gl);
-    r.el = __float_as_int(wp[WARM_EL + (gl & 7)]); r.f[0] = x.x; r.f[1] = x.y; r.f[2] = x.z; r.lam = x.w;
-}
-DI void warm_load(const float* wp, const int gl, WarmRec<v2f>& r) {
-    const float4 a = *reinterpret_cast<const float4*>(wp + WARM_F + 4 * gl), b = *reinterpret_cast<const float4*>(wp + WARM_F + 4 * (MAXC + gl));
-    r.el = __float_as_int(wp[WARM_EL + gl]);
-    r.f[0].x = a.x; r.f[1].x = a.y; r.f[2].x = a.z; r.lam.x = a.w; r.f[0].y = b.x; r.f[1].y = b.y; r.f[2].y = b.z; r.lam.y = b.w;
-}
-DI void warm_store(float* wp, const int gl, const WarmRec<float>& r) {
-    *reinterpret_cast<float4*>(wp + WARM_F + 4 * gl) = make_float4(r.f[0], r.f[1], r.f[2], r.lam);
-    if (gl < MAXC) wp[WARM_EL + gl] = __int_as_float(r.el);
-}
-DI void warm_store(float* wp, const int gl, const WarmRec<v2f>& r) {
-    *reinterpret_cast<float4*>(wp + WARM_F + 4 * gl) = make_float4(r.f[0].x, r.f[1].x, r.f[2].x, r.lam.x);
-    *reinterpret_cast<float4*>(wp + WARM_F + 4 * (MAXC + gl)) = make_float4(r.f[0].y, r.f[1].y, r.f[2].y, r.lam.y);
-    wp[WARM_EL + gl] = __int_as_float(r.el);
-}
-// the rows of an environment whose episode begins: no kept contact (G lanes of a group; every word of the rows)
-template <int G> DI void warm_rows_clear(float* wp, const int gl) {
-    for (int v = gl; v < WARM_WORDS / 4; v += G) reinterpret_cast<float4*>(wp)[v] = (v < MAXC / 4) ? make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), __int_as_float(-1)) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-template <int G>
-DI void contact_rows(float* lds, const int eb, const int gl, const DevModel& M, const DevCfg& C, const int nc, const int* cel, const float vz, ContactRows& P) {
-#define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
-    const bool own = gl < nc;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) P.Km[c] = 0.f;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        P.g[d] = 0.f; P.Rd[d] = 0.f; P.vrel0[d] = 0.f;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) P.w[d][a] = 0.f;
-    }
-    P.ae0 = 0.f; P.kdist = 0.f;
-    if (own) {
-        const int b = GE_CG + gl * CG_WORDS;
-        f3 nn = mk(EB(b + 0), EB(b + 1), EB(b + 2)), rr = mk(EB(b + 3), EB(b + 4), EB(b + 5));
-        const int e = __float_as_int(EB(b + 6));
-        const float dist = EB(b + 7);
-        // tangent frame without a case distinction (Frisvad 2012: continuous except at n.z = -1; contact normals point from the element towards the probe,
-        // and no element sits above it): the iterate of a fixed number of row-by-row sweeps depends on the frame, so float32 and float64 must not be able
-        // to choose different ones (oracle: same lines)
-        const float aa = -rcp_(1.f + nn.z), bb = nn.x * nn.y * aa;
-        f3 t1 = mk(1.f + nn.x * nn.x * aa, bb, -nn.x);
-        f3 t2 = mk(bb, 1.f + nn.y * nn.y * aa, -nn.y);
-        f3 ax = mk(lds[TB_AXIS + 3 * e], lds[TB_AXIS + 3 * e + 1], lds[TB_AXIS + 3 * e + 2]);
-        const float sde = EB(GE_SD + e);
-        float xx = fminf(-dist * (1.0f / SI_WIDTH), 1.f);
-        float yy = (xx < 0.5f) ? 2.f * xx * xx : 1.f - 2.f * (1.f - xx) * (1.f - xx);
-        float dimp = SI_D0 + yy * (SI_DMAX - SI_D0);
-        float kk = dimp * (1.0f / (SI_DMAX * SI_DMAX * SR_TC * SR_TC));
-        float Rn = (1.f - dimp) * rcp_(dimp) * M.invw;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) { const float t = lds[TB_LINV + e * LROW + cel[c]] * (1.0f / ELEM_MASS); P.Km[c] = (c < nc) ? t : 0.f; }
-        P.ae0 = EB(GE_A + e);
-        P.kdist = kk * dist;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            f3 dir = (d == 0) ? nn : (d == 1 ? t1 : t2);
-            f3 rx = cross(rr, dir);
-            P.w[d][0] = dir.x; P.w[d][1] = dir.y; P.w[d][2] = dir.z; P.w[d][3] = rx.x; P.w[d][4] = rx.y; P.w[d][5] = rx.z;
-            P.g[d] = -dot(dir, ax);
-            P.vrel0[d] = P.g[d] * sde - dir.z * vz;
-            P.Rd[d] = (d == 0) ? Rn * C.rn_scale : Rn * (1.0f / IMPRATIO);    // (two colliding probe geoms: two equal normal rows in parallel = half the regulariser)
-        }
-    }
-#undef EB
-}
-
-// PRE: the arm-independent half of the rows comes from contact_rows (P); otherwise the whole set-up is formed here (vz and the records; P is not read) -- one
-// statement sequence for the kernels that do not split it: handing the rows through the struct cost the 16-lane split kernel 0.5 us per step.
-// WR = WarmRec: the solve starts from the kept record `wr` of the lane (matched by element against this pass's contact list) and leaves the new one in it.
-template <int G, bool PRE, class WR>
-DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M, const DevCfg& C, const int nc, const int ncmax, const int* cel,
-                      const float* Li, const float* alpha, const float* vs, const float mu, const float vz, const ContactRows& P, float* W, float* gf,
-                      unsigned long long* dbg, WR& wr) {
-    constexpr bool WARM = !std::is_same<WR, NoWarm>::value;
-#define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
-    // ---- contact k lives in the registers of lane k of its group.  Set-up: row directions w, Lambda^-1 w, element
-    //      coupling g, reference acceleration, regulariser; Km[c] = Linv[e_own][e_c] / m ----
-    USIM_CSTAMP(dbg, 0);
-    // 16 lanes per environment, eight contact slots: lanes 8-15 would idle through the set-up.  They CLONE lanes 0-7 instead (lane 8 + k forms the same rows
-    // of contact k, at no cost: same instructions) and take half of the Delassus blocks off them below.  Everything that leaves this function is masked to
-    // lanes 0-7 or to lane k: forces stay zero in the clones (only lane k keeps an increment), the wrench sum and the publications read lanes < MAXC.
-    constexpr bool CLONE = (G == 16) && !PRE;
-    const int cl = CLONE ? (gl & 7) : gl;
-    const bool own = cl < nc;
-    float w[3][6], Liw[3][6], g[3], Rd[3], f[3] = {0.f, 0.f, 0.f}, cres[3] = {0.f, 0.f, 0.f}, Km[MAXC];
-    if constexpr (PRE) {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) Km[c] = P.Km[c];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        g[d] = P.g[d]; Rd[d] = P.Rd[d];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) { w[d][a] = P.w[d][a]; Liw[d][a] = 0.f; }
-    }
-    if (own) {
-        const float bcon = 2.0f / (SI_DMAX * SR_TC);
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            float vrel = P.vrel0[d], wa = 0.f;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                float s = 0.f;
-#pragma unroll
-                for (int bb = 0; bb < 6; ++bb) s = fmaf((a >= bb) ? Li[PK(a, bb)] : Li[PK(bb, a)], w[d][bb], s);
-                Liw[d][a] = s;
-                vrel = fmaf(w[d][a], vs[a], vrel);
-                wa = fmaf(w[d][a], alpha[a], wa);
-            }
-            const float aref = -bcon * vrel - (d == 0 ? P.kdist : 0.f);
-            cres[d] = fmaf(g[d], P.ae0, wa) - aref;           // residual of row d at zero force
-        }
-    }
-    } else {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) Km[c] = 0.f;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        g[d] = 0.f; Rd[d] = 0.f;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) { w[d][a] = 0.f; Liw[d][a] = 0.f; }
-    }
-    if (own) {
-        const int b = GE_CG + cl * CG_WORDS;
-        f3 nn = mk(EB(b + 0), EB(b + 1), EB(b + 2)), rr = mk(EB(b + 3), EB(b + 4), EB(b + 5));
-        const int e = __float_as_int(EB(b + 6));
-        const float dist = EB(b + 7);
-        // tangent frame without a case distinction (Frisvad 2012: continuous except at n.z = -1; contact normals point from the element towards the probe,
-        // and no element sits above it): the iterate of a fixed number of row-by-row sweeps depends on the frame, so float32 and float64 must not be able
-        // to choose different ones (oracle: same lines)
-        const float aa = -rcp_(1.f + nn.z), bb = nn.x * nn.y * aa;
-        f3 t1 = mk(1.f + nn.x * nn.x * aa, bb, -nn.x);
-        f3 t2 = mk(bb, 1.f + nn.y * nn.y * aa, -nn.y);
-        f3 ax = mk(lds[TB_AXIS + 3 * e], lds[TB_AXIS + 3 * e + 1], lds[TB_AXIS + 3 * e + 2]);
-        const float sde = EB(GE_SD + e);
-        const float bcon = 2.0f / (SI_DMAX * SR_TC);
-        float xx = fminf(-dist * (1.0f / SI_WIDTH), 1.f);
-        float yy = (xx < 0.5f) ? 2.f * xx * xx : 1.f - 2.f * (1.f - xx) * (1.f - xx);
-        float dimp = SI_D0 + yy * (SI_DMAX - SI_D0);
-        float kk = dimp * (1.0f / (SI_DMAX * SI_DMAX * SR_TC * SR_TC));
-        float Rn = (1.f - dimp) * rcp_(dimp) * M.invw;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) { const float t = lds[TB_LINV + e * LROW + cel[c]] * (1.0f / ELEM_MASS); Km[c] = (c < nc) ? t : 0.f; }   // (cel[c] = 0 beyond the count: the read is always in range, and a select costs less than a branch around it)
-        const float ae0 = EB(GE_A + e);
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            f3 dir = (d == 0) ? nn : (d == 1 ? t1 : t2);
-            f3 rx = cross(rr, dir);
-            w[d][0] = dir.x; w[d][1] = dir.y; w[d][2] = dir.z; w[d][3] = rx.x; w[d][4] = rx.y; w[d][5] = rx.z;
-            g[d] = -dot(dir, ax);
-            float vrel = g[d] * sde - dir.z * vz, wa = 0.f;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                float s = 0.f;
-#pragma unroll
-                for (int bb = 0; bb < 6; ++bb) s = fmaf((a >= bb) ? Li[PK(a, bb)] : Li[PK(bb, a)], w[d][bb], s);
-                Liw[d][a] = s;
-                vrel = fmaf(w[d][a], vs[a], vrel);
-                wa = fmaf(w[d][a], alpha[a], wa);
-            }
-            const float aref = -bcon * vrel - (d == 0 ? kk * dist : 0.f);
-            Rd[d] = (d == 0) ? Rn * C.rn_scale : Rn * (1.0f / IMPRATIO);      // (two colliding probe geoms: two equal normal rows in parallel = half the regulariser)
-            cres[d] = fmaf(g[d], ae0, wa) - aref;             // residual of row d at zero force
-        }
-    }
-    }
-    USIM_STAMP(dbg, 9);
-    USIM_CSTAMP(dbg, 1);
-    // ---- Delassus blocks: B[k][d][d'] = d(residual of row d of this lane's contact) / d(force on row d' of contact k)
-    //      = w_d . Lambda^-1 w^k_d' + g_d Km[k] g^k_d' (+ the regulariser on the diagonal of the lane's own block); the sweeps below then
-    //      need three broadcasts per visit.
-    //      Lane k publishes Lambda^-1 w^k (18 words) and g^k (3) once in the environment's LDS block (the right-hand-side / staging area is
-    //      free by now); every lane then reads contact k's record with six 16-byte broadcast reads -- a quarter of the issue slots the 21 DPP
-    //      broadcasts took --, the reads of contact k + 1 in flight while the block of contact k is formed.
-    const int ncr = ncmax;                                        // (the iterations run exactly the wave's largest contact count)
-    // B[k] = d(residual of this lane's rows) / d(force on contact k), WITHOUT the regulariser; written and read only under k < ncr.  16-lane groups keep FOUR blocks per
-    // lane (round 6): those of contacts 0-3 in both halves while the wave has at most four contacts, those of contacts 0-3 in lanes 0-7 and of contacts 4-7 in lanes 8-15
-    // beyond -- each half then sums its own four products of an iteration and one rotation adds the halves (below).
-    constexpr int NB = CLONE ? 4 : MAXC;
-    float B[NB][3][3];
-    float b00 = 0.f, b01 = 0.f, b02 = 0.f, b11 = 0.f, b12 = 0.f, b22 = 0.f;      // the lane's own diagonal block (regulariser added below)
-    static_assert(MAXC * 24 <= GE_SD, "Delassus records overlay the rhs / staging area");
-    if (gl < MAXC) {
-        float4* pub = reinterpret_cast<float4*>(&EB(gl * 24));
-        pub[0] = make_float4(Liw[0][0], Liw[0][1], Liw[0][2], Liw[0][3]); pub[1] = make_float4(Liw[0][4], Liw[0][5], Liw[1][0], Liw[1][1]);
-        pub[2] = make_float4(Liw[1][2], Liw[1][3], Liw[1][4], Liw[1][5]); pub[3] = make_float4(Liw[2][0], Liw[2][1], Liw[2][2], Liw[2][3]);
-        pub[4] = make_float4(Liw[2][4], Liw[2][5], g[0], g[1]); pub[5] = make_float4(g[2], 0.f, 0.f, 0.f);
-    }
-    group_sync();
-    if constexpr (CLONE) {
-        // Lane k carries contact A of pair k, lane 8 + k contact B: the same rows.  Up to four contacts in the wave: both halves form blocks 0-3 (the same instructions:
-        // no cost).  More: lanes 0-7 form the blocks of contacts 0-3, lanes 8-15 those of contacts 4-7 -- and keep them (rounds 3-5 rotated every block to the other half:
-        // 36 rotations, 72 selects and 36 more registers per lane; the iteration below no longer needs them).  A slot beyond an environment's count holds zeros (its lane
-        // published zero rows), so its block is exactly zero.
-        const bool hi = gl >= 8;
-        const bool wide = ncr > 4;                                       // (wave-uniform)
-        const int k0 = (hi && wide) ? 4 : 0;
-        float4 rk[6];
-        {
-            const float4* src = reinterpret_cast<const float4*>(&EB(k0 * 24));
-#pragma unroll
-            for (int v = 0; v < 6; ++v) rk[v] = src[v];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (j < ncr) {
-                const float Kmj = (hi && wide) ? Km[4 + j] : Km[j];
-                const float Lk[3][6] = {{rk[0].x, rk[0].y, rk[0].z, rk[0].w, rk[1].x, rk[1].y}, {rk[1].z, rk[1].w, rk[2].x, rk[2].y, rk[2].z, rk[2].w},
-                                        {rk[3].x, rk[3].y, rk[3].z, rk[3].w, rk[4].x, rk[4].y}};
-                const float gk[3] = {rk[4].z * Kmj, rk[4].w * Kmj, rk[5].x * Kmj};
-                if (j + 1 < 4) {
-                    const float4* src = reinterpret_cast<const float4*>(&EB((k0 + j + 1) * 24));
-#pragma unroll
-                    for (int v = 0; v < 6; ++v) rk[v] = src[v];
-                }
-#pragma unroll
-                for (int dd = 0; dd < 3; ++dd) {
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) {
-                        float r1 = fmaf(w[d][4], Lk[dd][4], fmaf(w[d][2], Lk[dd][2], w[d][0] * Lk[dd][0]));
-                        float r2 = fmaf(w[d][5], Lk[dd][5], fmaf(w[d][3], Lk[dd][3], w[d][1] * Lk[dd][1]));
-                        B[j][d][dd] = fmaf(g[d], gk[dd], r1 + r2);
-                    }
-                }
-                // the lane's own diagonal block, if this half formed it (cl - k0 == j); otherwise the partner lane (the other half, same cl) did: one rotation below
-                const bool me = (cl - k0) == j;
-                b00 = me ? B[j][0][0] : b00; b01 = me ? B[j][0][1] : b01; b02 = me ? B[j][0][2] : b02;
-                b11 = me ? B[j][1][1] : b11; b12 = me ? B[j][1][2] : b12; b22 = me ? B[j][2][2] : b22;
-            }
-        }
-        if (wide) {
-            // (exactly one lane of a pair holds the block, the other holds zeros: x + 0)
-            b00 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b00), 0x128, 0xf, 0xf, true)); b01 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b01), 0x128, 0xf, 0xf, true));
-            b02 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b02), 0x128, 0xf, 0xf, true)); b11 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b11), 0x128, 0xf, 0xf, true));
-            b12 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b12), 0x128, 0xf, 0xf, true)); b22 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b22), 0x128, 0xf, 0xf, true));
-        }
-    } else {
-    float4 rk[6];
-    {
-        const float4* src = reinterpret_cast<const float4*>(&EB(0));
-#pragma unroll
-        for (int v = 0; v < 6; ++v) rk[v] = src[v];
-    }
-#pragma unroll
-    for (int k = 0; k < MAXC; ++k) {
-        if (k < ncr) {
-            const float Lk[3][6] = {{rk[0].x, rk[0].y, rk[0].z, rk[0].w, rk[1].x, rk[1].y}, {rk[1].z, rk[1].w, rk[2].x, rk[2].y, rk[2].z, rk[2].w},
-                                    {rk[3].x, rk[3].y, rk[3].z, rk[3].w, rk[4].x, rk[4].y}};
-            const float gk[3] = {rk[4].z * Km[k], rk[4].w * Km[k], rk[5].x * Km[k]};
-            if (k + 1 < MAXC) {                                          // next contact's record (a slot beyond the count holds stale words: unused)
-                const float4* src = reinterpret_cast<const float4*>(&EB((k + 1) * 24));
-#pragma unroll
-                for (int v = 0; v < 6; ++v) rk[v] = src[v];
-            }
-#pragma unroll
-            for (int dd = 0; dd < 3; ++dd) {
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    float r1 = fmaf(w[d][4], Lk[dd][4], fmaf(w[d][2], Lk[dd][2], w[d][0] * Lk[dd][0]));
-                    float r2 = fmaf(w[d][5], Lk[dd][5], fmaf(w[d][3], Lk[dd][3], w[d][1] * Lk[dd][1]));
-                    B[k][d][dd] = fmaf(g[d], gk[dd], r1 + r2);
-                }
-            }
-        }
-    }
-    }
-    USIM_CSTAMP(dbg, 2);
-    // ---- BLOCK JACOBI WITH AN EXACT LINE SEARCH on the dual  min 1/2 f'(A + R) f + b'f,  f_v in {|f_t| <= mu_v f_n}  (round 5; oracle: constrained_forward,
-    //      cone_solver 2 -- same optimum as the exact-cone Gauss-Seidel of round 4, i.e. MuJoCo's Newton solver's).  A Gauss-Seidel sweep is one visit per contact, one
-    //      after the other, in which one lane of sixteen does useful work -- and two visits per probe-element pair once its two coincident contacts
-    //      (ultrasound_probe_gripper.xml:8-9: probe_collision, mu 0.01 after MuJoCo's max rule, and probe_visual, mu 1) are modelled explicitly.  A wave issues one
-    //      instruction per ~4 cycles whatever its lanes do (profiles/r05/micro_two_wave.txt), so here EVERY virtual contact runs its visit at the same time: contact A of
-    //      pair k in lane k, contact B in lane 8 + k (16-lane groups; both in lane k with 8-lane groups), each on its own 3 x 3 block from the current residual
-    //      (cone_local: ray update with an immediate restart from zero, friction QCQP with one Newton step on the carried multiplier).  The step along d = f^ - f is
-    //      t = (sum_v d_v'B_v d_v) / (d'Qd) <= 1 (the exact minimiser of the quadratic when every block is solved exactly, never longer) -- a convex combination of feasible points, no projection --; the shared residual moves by t A D,
-    //      D_k = d_Ak + d_Bk (three row broadcasts and nine multiply-adds per pair: the only part that grows with the contact count).  pgs_iters iterations, cold start.
-    // Virtual contacts per lane: one (16-lane groups: contact A of pair k in lane k, contact B in lane 8 + k) or two (8-lane groups: both in lane k, in the two halves
-    // of packed registers -- one visit for the pair at the issue cost of ~1.2 instead of two: round 6).
-    typedef typename std::conditional<CLONE, float, v2f>::type VT;
-    typedef LaneVec<VT> V;
-    const bool pairB = C.pair != 0;
-    const float muB = fmaxf(C.probe_fric2, C.elem_fric);
-    typename V::mask ownv; VT muv, fv[3], lamv = V::splat(0.f);
-    if constexpr (CLONE) { ownv = own && (gl < 8 || pairB); muv = (gl < 8) ? mu : muB; }
-    else { ownv = b2{own, own && pairB}; muv.x = mu; muv.y = muB; }
-    fv[0] = fv[1] = fv[2] = V::splat(0.f);
-    int myel = -1;
-    if constexpr (WARM) {
-        // ---- warm start: the kept list goes through the environment's LDS block (words 0 .. 71, laid out as the warm rows; the Delassus records above have been
-        //      read by every lane), a lane finds its contact's element among the eight kept ones and takes that slot's force and multiplier.  No match, no contact:
-        //      zero, as in a cold start.
-        static_assert(std::is_same<WR, WarmRec<VT>>::value, "warm record of the mapping");
-        static_assert(WARM_WORDS <= GE_SD, "kept list overlays the rhs / staging area");
-        myel = own ? __float_as_int(EB(GE_CG + cl * CG_WORDS + 6)) : -1;
-        group_sync();
-        warm_store(&EB(0), gl, wr);
-        group_sync();
-        const float4 k0 = *reinterpret_cast<const float4*>(&EB(WARM_EL)), k1 = *reinterpret_cast<const float4*>(&EB(WARM_EL + 4));
-        const int kel[MAXC] = {__float_as_int(k0.x), __float_as_int(k0.y), __float_as_int(k0.z), __float_as_int(k0.w),
-                               __float_as_int(k1.x), __float_as_int(k1.y), __float_as_int(k1.z), __float_as_int(k1.w)};
-        int m = -1;
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) m = (own && kel[k] == myel) ? k : m;
-        const bool hit = m >= 0;
-        const int ms = hit ? m : 0;
-        if constexpr (CLONE) {
-            const float4 x = *reinterpret_cast<const float4*>(&EB(WARM_F + 4 * ((gl & 8) + ms)));
-            const bool take = hit && ownv;
-            fv[0] = take ? x.x : 0.f; fv[1] = take ? x.y : 0.f; fv[2] = take ? x.z : 0.f; lamv = take ? x.w : 0.f;
-        } else {
-            const float4 xa = *reinterpret_cast<const float4*>(&EB(WARM_F + 4 * ms)), xb = *reinterpret_cast<const float4*>(&EB(WARM_F + 4 * (MAXC + ms)));
-            const bool ta = hit && ownv.x, tb = hit && ownv.y;
-            fv[0].x = ta ? xa.x : 0.f; fv[1].x = ta ? xa.y : 0.f; fv[2].x = ta ? xa.z : 0.f; lamv.x = ta ? xa.w : 0.f;
-            fv[0].y = tb ? xb.x : 0.f; fv[1].y = tb ? xb.y : 0.f; fv[2].y = tb ? xb.z : 0.f; lamv.y = tb ? xb.w : 0.f;
-        }
-    }
-    // the lane's own diagonal block, regulariser included
-    if constexpr (!CLONE) {
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) {
-            if (k < ncr) {
-                const bool me = cl == k;
-                b00 = me ? B[k][0][0] : b00; b01 = me ? B[k][0][1] : b01; b02 = me ? B[k][0][2] : b02;
-                b11 = me ? B[k][1][1] : b11; b12 = me ? B[k][1][2] : b12; b22 = me ? B[k][2][2] : b22;
-            }
-        }
-    }
-    b00 += Rd[0]; b11 += Rd[1]; b22 += Rd[2];
-    // q = A D for the pairs' summed directions D (one per lane, D_k in lane k).  Up to four contacts: one running sum over them.  More: the sum over contacts 0-3 plus the
-    // sum over contacts 4-7 -- in that association in EVERY mapping (an environment's bits must not depend on its wave's neighbours: for one with at most four contacts
-    // the second sum is exact zeros) -- which a 16-lane group evaluates in its two halves at once: lanes 0-7 take D_j, lanes 8-15 D_(4+j) from the same row (two bank-masked
-    // broadcasts per word), each half multiplies with the four blocks it formed, one rotation by eight lanes adds the halves.  Eight contacts: 63 instructions instead of
-    // 96 (round 5), six: 63 / 72.  Used by every iteration and, with a warm start, once before them (A s0): one statement of the association for both
-    // (a macro, not a lambda: through a lambda the 8-lane split kernel of a cold handle spills one more register).
-#define USIM_DELASSUS_PRODUCT(D0, D1, D2, q0, q1, q2) \
-            if constexpr (NCM <= 4) { \
-_Pragma("unroll") \
-                for (int k = 0; k < NCM; ++k) { \
-                    const float e0 = group_bcast<G>(D0, k), e1 = group_bcast<G>(D1, k), e2 = group_bcast<G>(D2, k); \
-                    q0 = fmaf(B[k][0][2], e2, fmaf(B[k][0][1], e1, fmaf(B[k][0][0], e0, q0))); \
-                    q1 = fmaf(B[k][1][2], e2, fmaf(B[k][1][1], e1, fmaf(B[k][1][0], e0, q1))); \
-                    q2 = fmaf(B[k][2][2], e2, fmaf(B[k][2][1], e1, fmaf(B[k][2][0], e0, q2))); \
-                } \
-            } else if constexpr (CLONE) { \
-_Pragma("unroll") \
-                for (int j = 0; j < 4; ++j) { \
-                    const float e0 = half_bcast(D0, j), e1 = half_bcast(D1, j), e2 = half_bcast(D2, j); \
-                    q0 = fmaf(B[j][0][2], e2, fmaf(B[j][0][1], e1, fmaf(B[j][0][0], e0, q0))); \
-                    q1 = fmaf(B[j][1][2], e2, fmaf(B[j][1][1], e1, fmaf(B[j][1][0], e0, q1))); \
-                    q2 = fmaf(B[j][2][2], e2, fmaf(B[j][2][1], e1, fmaf(B[j][2][0], e0, q2))); \
-                } \
-                q0 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q0), 0x128, 0xf, 0xf, true)); \
-                q1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q1), 0x128, 0xf, 0xf, true)); \
-                q2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(q2), 0x128, 0xf, 0xf, true)); \
-            } else { \
-                float h0 = 0.f, h1 = 0.f, h2 = 0.f; \
-_Pragma("unroll") \
-                for (int k = 0; k < NCM; ++k) { \
-                    const float e0 = group_bcast<G>(D0, k), e1 = group_bcast<G>(D1, k), e2 = group_bcast<G>(D2, k); \
-                    float& a0 = (k < 4) ? q0 : h0; float& a1 = (k < 4) ? q1 : h1; float& a2 = (k < 4) ? q2 : h2; \
-                    a0 = fmaf(B[k][0][2], e2, fmaf(B[k][0][1], e1, fmaf(B[k][0][0], e0, a0))); \
-                    a1 = fmaf(B[k][1][2], e2, fmaf(B[k][1][1], e1, fmaf(B[k][1][0], e0, a1))); \
-                    a2 = fmaf(B[k][2][2], e2, fmaf(B[k][2][1], e1, fmaf(B[k][2][0], e0, a2))); \
-                } \
-                q0 += h0; q1 += h1; q2 += h2; \
-            }
-    auto iterations = [&](auto NCM_) {
-        constexpr int NCM = decltype(NCM_)::value;
-        const VT vb00 = V::splat(b00), vb01 = V::splat(b01), vb02 = V::splat(b02), vb11 = V::splat(b11), vb12 = V::splat(b12), vb22 = V::splat(b22);
-        const VT vR0 = V::splat(Rd[0]), vR1 = V::splat(Rd[1]), vR2 = V::splat(Rd[2]);
-        if constexpr (WARM) {
-            // the shared residual at the kept forces: b + A s0, s0 = f_A + f_B per pair -- one product
-            float D0 = V::hsum(fv[0]), D1 = V::hsum(fv[1]), D2 = V::hsum(fv[2]);
-            if constexpr (CLONE) {
-                D0 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D0), 0x128, 0xf, 0xf, true));
-                D1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D1), 0x128, 0xf, 0xf, true));
-                D2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D2), 0x128, 0xf, 0xf, true));
-            }
-            float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-            USIM_DELASSUS_PRODUCT(D0, D1, D2, q0, q1, q2)
-            cres[0] += q0; cres[1] += q1; cres[2] += q2;
-        }
-        for (int it = 0; it < C.pgs_iters; ++it) {
-            VT dv[3];
-            float num, D0, D1, D2;
-            {
-                const VT r0 = V::fma(vR0, fv[0], V::splat(cres[0])), r1 = V::fma(vR1, fv[1], V::splat(cres[1])), r2 = V::fma(vR2, fv[2], V::splat(cres[2]));
-                VT h0, h1, h2, lam = lamv;
-                const typename V::mask haslim = cone_local<VT>(vb00, vb01, vb02, vb11, vb12, vb22, r0, r1, r2, fv[0], fv[1], fv[2], muv, lam, h0, h1, h2);
-                lamv = V::sel(V::both(ownv, haslim), lam, lamv);
-                dv[0] = V::sel(ownv, h0 - fv[0], V::splat(0.f)); dv[1] = V::sel(ownv, h1 - fv[1], V::splat(0.f)); dv[2] = V::sel(ownv, h2 - fv[2], V::splat(0.f));
-                // slope of the cost along d, block by block: -d'B d (for the minimiser of a block r.d <= -d'B d, with equality inside the cone) -- a sum of squares
-                // instead of r.d, whose products cancel to second order for a sliding contact and are float32 noise once |d| < 5e-3 N (oracle: same lines)
-                const VT e0 = dv[0], e1 = dv[1], e2 = dv[2];
-                const VT Be0 = V::fma(vb02, e2, V::fma(vb01, e1, vb00 * e0)), Be1 = V::fma(vb12, e2, V::fma(vb11, e1, vb01 * e0)), Be2 = V::fma(vb22, e2, V::fma(vb12, e1, vb02 * e0));
-                num = V::nsum(V::fma(e2, Be2, V::fma(e1, Be1, e0 * Be0)));          // (no 0 + x: the compiler may not fold it -- signed zeros -- and an instruction here is paid 24 times per step)
-                D0 = V::hsum(dv[0]); D1 = V::hsum(dv[1]); D2 = V::hsum(dv[2]);
-            }
-            if constexpr (CLONE) {                                       // D_k = d_Ak + d_Bk in both halves
-                D0 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D0), 0x128, 0xf, 0xf, true));
-                D1 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D1), 0x128, 0xf, 0xf, true));
-                D2 += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(D2), 0x128, 0xf, 0xf, true));
-            }
-            float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-            USIM_DELASSUS_PRODUCT(D0, D1, D2, q0, q1, q2)
-            float den = V::hsum(V::fma(dv[2], V::fma(vR2, dv[2], V::splat(q2)), V::fma(dv[1], V::fma(vR1, dv[1], V::splat(q1)), dv[0] * V::fma(vR0, dv[0], V::splat(q0)))));
-            num = group_allsum<G>(num); den = group_allsum<G>(den);
-            const float t = (den > 0.f) ? fminf(-num * rcp_(den), 1.f) : 0.f;
-            fv[0] = V::fma(V::splat(t), dv[0], fv[0]); fv[1] = V::fma(V::splat(t), dv[1], fv[1]); fv[2] = V::fma(V::splat(t), dv[2], fv[2]);
-            cres[0] = fmaf(t, q0, cres[0]); cres[1] = fmaf(t, q1, cres[1]); cres[2] = fmaf(t, q2, cres[2]);
-        }
-    };
-    // (one straight-line instantiation per wave-uniform contact count)
-    switch (ncr) {
-        case 1: iterations(std::integral_constant<int, 1>{}); break;
-        case 2: iterations(std::integral_constant<int, 2>{}); break;
-        case 3: iterations(std::integral_constant<int, 3>{}); break;
-        case 4: iterations(std::integral_constant<int, 4>{}); break;
-        case 5: iterations(std::integral_constant<int, 5>{}); break;
-        case 6: iterations(std::integral_constant<int, 6>{}); break;
-        case 7: iterations(std::integral_constant<int, 7>{}); break;
-        default: iterations(std::integral_constant<int, 8>{}); break;
-    }
-#undef USIM_DELASSUS_PRODUCT
-    if constexpr (WARM) { wr.el = myel; wr.f[0] = fv[0]; wr.f[1] = fv[1]; wr.f[2] = fv[2]; wr.lam = lamv; }     // (a virtual contact that does not exist holds zeros)
-    // the pair's total force (lanes 0-7 of a 16-lane group: contact A's own force plus contact B's from lane 8 + k)
-    if constexpr (CLONE) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) f[d] = fv[d] + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(fv[d]), 0x128, 0xf, 0xf, true));
-    } else {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) f[d] = V::hsum(fv[d]);
-    }
-    USIM_STAMP(dbg, 10);
-    USIM_CSTAMP(dbg, 3);
-    // ---- contact wrench on the site and impulse along each element axis (lanes without a contact hold w = g = f = 0, i.e. contribute
-    //      zeros) ----
-    {
-        const float Fw[6] = {w[0][0] * f[0] + w[1][0] * f[1] + w[2][0] * f[2], w[0][1] * f[0] + w[1][1] * f[1] + w[2][1] * f[2],
-                             w[0][2] * f[0] + w[1][2] * f[1] + w[2][2] * f[2], w[0][3] * f[0] + w[1][3] * f[1] + w[2][3] * f[2],
-                             w[0][4] * f[0] + w[1][4] * f[1] + w[2][4] * f[2], w[0][5] * f[0] + w[1][5] * f[1] + w[2][5] * f[2]};
-        const float gfo = (g[0] * f[0] + g[1] * f[1] + g[2] * f[2]) * (1.0f / ELEM_MASS);
-        {
-            // the sum over the eight contact lanes is a shifted-add reduction over the DPP row (16 lanes per environment: lanes 8-15 are masked;
-            // 8 lanes per environment: the shifts are fenced at the group boundary, same tree, same bits), the per-contact impulses are
-            // group broadcasts
-            auto shr_add = [&](float v, auto Dc) {
-                constexpr int D = decltype(Dc)::value;
-                float t = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x110 + D, 0xf, 0xf, true));      // row_shr:D
-                if constexpr (G == 8) t = (gl < D) ? 0.f : t;
-                return v + t;
-            };
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                float v = (gl < MAXC) ? Fw[a] : 0.f;
-                v = shr_add(v, std::integral_constant<int, 1>{});
-                v = shr_add(v, std::integral_constant<int, 2>{});
-                v = shr_add(v, std::integral_constant<int, 4>{});
-                W[a] += group_bcast<G>(v, 7);
-            }
-#pragma unroll
-            for (int k = 0; k < MAXC; ++k) gf[k] = group_bcast<G>(gfo, k);          // (no test per slot: a lane without a contact holds zeros)
-        }
-    }
-    USIM_CSTAMP(dbg, 4);
-#undef EB
-}
-
+#include "usim_contact.h"
 #include "usim_episode.h"
 #include "usim_full.h"
 

@@ -19,7 +19,7 @@
 // (DevModel::tables + TB_ARM, usim_device.h ArmTable): per lane the fixed transform to the parent link frame, a joint about the local z axis,
 // inertial parameters in the link frame -- the kernel is the same for every chain of up to seven joints.
 //
-// Lattice / contact phases (soft torso) are the ones of usim_kernels.hip (lattice_rhs, lattice_solve, collide_*, contact_solve): the G = 16 mapping is unchanged there.
+// Lattice / contact phases (soft torso) are the ones of usim_kernels.hip and usim_contact.h (lattice_rhs, lattice_solve, collide_*; contact_solve): the G = 16 mapping is unchanged there.
 #pragma once
 #include <type_traits>
 

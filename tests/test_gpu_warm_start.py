@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle_lib import deep_spawn_params
 from test_gpu_parity import _mk, _razor_edge, _run_parity
 
 pytestmark = pytest.mark.gpu
@@ -111,6 +112,35 @@ def test_warm_start_mappings_and_launch_lengths_compute_the_same_bits(usim):
         assert torch.equal(ref[0]["obs"][k], obs) and torch.equal(ref[0]["rew"][k], rew) and torch.equal(ref[0]["done"][k], done), k
     _state_equal(ref[2], e.get_state())
     e.close()
+
+
+def test_warm_start_resolves_a_slot_overflow_to_the_same_bits_in_every_mapping(usim):
+    """the warm twin of test_gpu_properties.test_every_mapping_resolves_a_slot_overflow_to_the_same_bits: probes spawned 1.2-3 cm deep, so that waves carry more than four
+    contacts (the Delassus product summed by halves, the A s0 product of the kept forces included) and the slot rule runs, under a warm start in the three mappings --
+    observations, rewards, done flags, contact lists and the final state with its kept list are the same bits"""
+    n = 256
+    envs = [_env(usim, n, lanes_per_env=lanes, **WARM) for lanes in (16, 32, 64)]
+    for e in envs:
+        e.reset_tensor()
+    p = deep_spawn_params(envs[0].get_state(), n)
+    obs0 = [e.reset_explicit_tensor(p).clone() for e in envs]
+    assert all(torch.equal(obs0[0], o) for o in obs0[1:])
+    status = [e.get_state()["status"].astype(int) & 1 for e in envs]
+    assert status[0].sum() > 20 and all(np.array_equal(status[0], s) for s in status[1:])
+    act = torch.full((n, 6), 0.5, dtype=torch.float32, device=envs[0].device)
+    most = 0
+    for k in range(25):
+        res = [[x.clone() for x in e.step_tensor(act, auto_reset=False)] for e in envs]
+        most = max(most, int(envs[0].contacts[:, 0].max()))
+        for r, e in zip(res[1:], envs[1:]):
+            assert all(torch.equal(a, b) for a, b in zip(res[0], r)) and torch.equal(envs[0].contacts, e.contacts), k
+    assert most > 4
+    s0 = envs[0].get_state()
+    assert "solver_warm_start" in s0 and (s0["solver_warm_start"][:, :8] >= 0).any()
+    for e in envs[1:]:
+        _state_equal(s0, e.get_state())
+    for e in envs:
+        e.close()
 
 
 # ---- 4. it does something, and only when asked ----

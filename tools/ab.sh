@@ -14,4 +14,7 @@ run $lib "config5 8192"         --steps 1024 --warmup 256 --envs-per-gpu 8192 --
 run $lib "soft 4096 20/5"       --steps 20 --warmup 5
 run $lib "rigid 4096"           --steps 2048 --warmup 256 --workload rigid
 run $lib "soft 4096 lanes16"    --steps 2048 --warmup 256 --lanes-per-env 16
+USIM_WARM_START=1 run $lib "soft 4096 warm18"         --steps 2048 --warmup 256 --pgs-iters 18
+USIM_WARM_START=1 run $lib "config5 8192 warm18"      --steps 1024 --warmup 256 --envs-per-gpu 8192 --randomize --pgs-iters 18
+USIM_WARM_START=1 run $lib "soft 4096 lanes16 warm18" --steps 2048 --warmup 256 --lanes-per-env 16 --pgs-iters 18
 done; done

@@ -22,6 +22,7 @@
  */
 #ifndef USIM_H
 #define USIM_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -258,6 +259,31 @@ int usim_set_warm_start(usim_handle* h, const float* w);
  * are written, max_ticks >= 17).  Only the profiling build of the library (make -C csrc prof) carries the stamps; the production build
  * returns USIM_ERR_UNSUPPORTED. */
 int usim_profile_step(usim_handle* h, const usim_step_io* io, int64_t step, uint64_t* ticks, int max_ticks);
+
+/* ---- one step's results as ONE block, for callers that hand them to the host (numpy in / numpy out: the SB3 VecEnv protocol, vec_env.py step_async / step_wait).
+ * Reads the buffers named in io -- obs_dev, rew_dev, done_dev required; term_obs_dev, ep_return_dev, ep_length_dev, status_dev may be NULL -- after the usim_step that
+ * filled them, on the same stream, and writes packed_dev, a caller-owned device buffer of USIM_PACK_WORDS(n) 32-bit words, 16-byte aligned:
+ *     word 0                      c, the number of environments whose episode ended in this step (int32 bits); words 1 - 3: zero
+ *     words 4 .. 4 + 21 n         the head [n][USIM_PACK_HEAD_WORDS]: obs[19], rew, done as 0.0f / 1.0f
+ *     then                        the episode list [c][USIM_PACK_EPISODE_WORDS], one row per finished environment IN ASCENDING ENVIRONMENT INDEX: env index (int32 bits),
+ *                                 ep_length (int32 bits), ep_return, status (int32 bits), terminal_observation[19]; the words of a NULL buffer are zero.  Exactly c rows
+ *                                 are written: rows c .. n - 1 keep what the buffer held
+ * Every float is copied as its bits (a NaN stays the same NaN).  No handle, no allocation, no synchronisation: one kernel launch, capture-safe.  The block is a function
+ * of the inputs alone (nothing is ordered by arrival).  n <= 0, a NULL io / required pointer / packed_dev or a packed_dev off the 16-byte grid: USIM_ERR_INVALID, nothing
+ * is written.  A host that wants the results of a step copies 16 + 84 n bytes, reads c, and -- when c > 0 -- copies 92 c bytes more:
+ *     float* packed_dev;  hipMalloc((void**)&packed_dev, USIM_PACK_WORDS(n) * 4);
+ *     float* host = malloc(USIM_PACK_WORDS(n) * 4);  int32_t c;
+ *     usim_step(h, &io, 1, stream);  usim_pack_step(&io, n, packed_dev, stream);
+ *     hipMemcpyAsync(host, packed_dev, (4 + (size_t)n * USIM_PACK_HEAD_WORDS) * 4, hipMemcpyDeviceToHost, stream);  hipStreamSynchronize(stream);
+ *     memcpy(&c, host, 4);                                              -- word 0
+ *     const float* row_i = host + 4 + i * USIM_PACK_HEAD_WORDS;         -- row_i[0 .. 18] observation of env i, row_i[19] reward, row_i[20] != 0: episode ended
+ *     if (c) hipMemcpy(host + 4 + (size_t)n * USIM_PACK_HEAD_WORDS, packed_dev + 4 + (size_t)n * USIM_PACK_HEAD_WORDS, (size_t)c * USIM_PACK_EPISODE_WORDS * 4, hipMemcpyDeviceToHost);
+ *     const float* ep_k = host + 4 + (size_t)n * USIM_PACK_HEAD_WORDS + k * USIM_PACK_EPISODE_WORDS;    -- k < c: ep_k[0] env index, ep_k[1] length, ep_k[3] status (read as int32),
+ *                                                                                                           ep_k[2] return, ep_k[4 .. 22] terminal observation */
+#define USIM_PACK_HEAD_WORDS 21            /* obs[19], rew, done as 0.0f / 1.0f */
+#define USIM_PACK_EPISODE_WORDS 23         /* env index (int32 bits), ep_length (int32 bits), ep_return, status (int32 bits; 0 when io->status_dev is NULL), terminal_observation[19] */
+#define USIM_PACK_WORDS(n) (4 + (size_t)(n) * (USIM_PACK_HEAD_WORDS + USIM_PACK_EPISODE_WORDS))
+int usim_pack_step(const usim_step_io* io, int n, float* packed_dev, void* stream);
 
 /* ---- the caller's side of env.step() on the device: SB3 VecNormalize + MlpPolicy forward + sampling + rollout-buffer
  * writes + GAE, fused into a few kernels per rollout step (csrc/usim_policy.hip).  Everything is a device pointer into the CALLER's tensors

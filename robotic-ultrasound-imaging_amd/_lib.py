@@ -17,6 +17,14 @@ POLICY_PACKED = 2 * 128 * 256      # USIM_POLICY_PACKED
 RESET_PARAMS = 13
 LOG_WIDTH = 53
 WARM_WORDS = 8 + 16 * 4            # USIM_WARM_WORDS
+PACK_HEAD_WORDS = 21               # USIM_PACK_HEAD_WORDS: obs[19], rew, done
+PACK_EPISODE_WORDS = 23            # USIM_PACK_EPISODE_WORDS: env index, ep_length, ep_return, status, terminal_observation[19]
+
+
+def pack_words(n):
+    """USIM_PACK_WORDS(n): 32-bit words of the block usim_pack_step fills for n environments"""
+    return 4 + int(n) * (PACK_HEAD_WORDS + PACK_EPISODE_WORDS)
+
 
 MODE = {"tracking": 0, "fixed": 1, "variable_z": 2, "wrench": 3}
 TORSO = {"none": 0, "rigid": 0, "top": 1, "soft": 1, "full": 2}
@@ -74,6 +82,7 @@ SYMBOLS = {
     "usim_policy_reward": (C.c_int, [C.POINTER(UsimNormStats), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_policy_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "usim_pack_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_void_p, C.c_void_p]),
     "usim_default_config": (C.c_int, [C.POINTER(UsimConfig)]),
     "usim_create": (C.c_int, [C.POINTER(UsimConfig), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "usim_destroy": (None, [C.c_void_p]),

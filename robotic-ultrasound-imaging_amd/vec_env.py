@@ -74,6 +74,22 @@ class UltrasoundVecEnv:
             self._status = torch.zeros(n, dtype=torch.int32, device=self.device)
         self._io = _lib.UsimStepIO(self._act.data_ptr(), self._obs.data_ptr(), self._rew.data_ptr(), self._done.data_ptr(),
                                    self._term.data_ptr(), self._contacts.data_ptr(), self._ep_ret.data_ptr(), self._ep_len.data_ptr(), None, self._status.data_ptr(), None)
+        # numpy path (step_async / step_wait): usim_pack_step puts a step's results into one device block; a pinned mirror receives its count + head with one
+        # device-to-host copy and, on the steps where episodes ended, the rows of those episodes with a second one (include/usim.h usim_pack_step)
+        head = 4 + n * _lib.PACK_HEAD_WORDS
+        with torch.cuda.device(self.device):
+            self._packed = torch.zeros(_lib.pack_words(n), dtype=torch.int32, device=self.device)
+            self._mirror = torch.zeros(_lib.pack_words(n), dtype=torch.int32, pin_memory=True)
+            self._act_host = torch.zeros((n, self.action_dim), dtype=torch.float32, pin_memory=True)
+            self._head_event = torch.cuda.Event()
+        self._packed_head, self._packed_rows = self._packed[:head], self._packed[head:]
+        self._mirror_head, self._mirror_rows = self._mirror[:head], self._mirror[head:]
+        self._act_host_np = self._act_host.numpy()
+        words = self._mirror.numpy()                                  # int32 view of the mirror; the float words through .view(np.float32)
+        self._count_np = words[:1]
+        self._head_np = words[4:head].view(np.float32).reshape(n, _lib.PACK_HEAD_WORDS)
+        self._rows_np = words[head:].reshape(n, _lib.PACK_EPISODE_WORDS)
+        self._d2h_transfers = 0                                       # device-to-host copies issued by the numpy path so far: one per step, two where an episode ended
         self._t_start = time.time()
         self._pending = False
         self.horizon = int(self.cfg.horizon)
@@ -284,30 +300,43 @@ class UltrasoundVecEnv:
         a = np.asarray(actions, dtype=np.float32)
         if a.shape != (self.num_envs, self.action_dim):
             raise ValueError(f"actions must have shape {(self.num_envs, self.action_dim)}, got {a.shape}")
-        self._act.copy_(torch.from_numpy(np.ascontiguousarray(a)), non_blocking=False)
+        if self._pending:                                         # step_async twice without step_wait: the staging array may still be read by the previous copy
+            self._head_event.synchronize()
+        np.copyto(self._act_host_np, a)
+        # (a copy between host and device goes to the current stream of its device: the stream the library's launches are given)
+        self._act.copy_(self._act_host, non_blocking=True)
         self.step_tensor(self._act)
+        self._check(self.lib.usim_pack_step(C.byref(self._io), self.num_envs, self._packed.data_ptr(), self._stream()))
+        self._mirror_head.copy_(self._packed_head, non_blocking=True)
+        self._head_event.record(torch.cuda.current_stream(self.device))
+        self._d2h_transfers += 1
         self._pending = True
 
     def step_wait(self):
         if not self._pending:
             raise RuntimeError("step_wait called without step_async")
         self._pending = False
-        obs = self._obs.cpu().numpy().copy()
-        rew = self._rew.cpu().numpy().copy()
-        done = self._done.cpu().numpy().astype(bool)
+        self._head_event.synchronize()                            # the head has arrived (and the actions have left the staging array)
+        obs = self._head_np[:, :_lib.OBS_DIM].copy()              # fresh arrays: SB3 keeps references across steps, the mirror is overwritten by the next one
+        rew = self._head_np[:, _lib.OBS_DIM].copy()
+        done = self._head_np[:, _lib.OBS_DIM + 1] != 0
         infos = [{} for _ in range(self.num_envs)]
-        if done.any():
-            idx = np.nonzero(done)[0]
-            term = self._term.cpu().numpy()
-            ep_r = self._ep_ret.cpu().numpy()
-            ep_l = self._ep_len.cpu().numpy()
+        count = int(self._count_np[0])
+        if count:
+            w = count * _lib.PACK_EPISODE_WORDS
+            self._mirror_rows[:w].copy_(self._packed_rows[:w], non_blocking=False)
+            self._d2h_transfers += 1
+            rows = self._rows_np[:count]                          # ascending environment index
+            idx, ep_l = rows[:, 0], rows[:, 1]
+            ep_r, term = rows[:, 2].view(np.float32), rows[:, 4:].view(np.float32)
             now = round(time.time() - self._t_start, 6)
-            for i in idx:
-                infos[i]["terminal_observation"] = term[i].copy()
+            for k in range(count):
+                info = infos[idx[k]]
+                info["terminal_observation"] = term[k].copy()
                 if self._monitor:                                # SB3 Monitor (src/rl.py:39)
-                    infos[i]["episode"] = {"r": float(ep_r[i]), "l": int(ep_l[i]), "t": now}
+                    info["episode"] = {"r": float(ep_r[k]), "l": int(ep_l[k]), "t": now}
                 if self._report_truncation:
-                    infos[i]["TimeLimit.truncated"] = bool(ep_l[i] >= self.horizon)
+                    info["TimeLimit.truncated"] = bool(ep_l[k] >= self.horizon)
         return obs, rew, done, infos
 
     def step(self, actions):

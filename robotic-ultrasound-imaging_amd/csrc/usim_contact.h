@@ -1,7 +1,7 @@
 // usim_contact.h -- the contact solve of the soft torso's top face: the rows of the contacts, their Delassus blocks, the warm start, the block Jacobi iteration
 // with its line search, the wrench on the site and the impulses on the elements (DESIGN.md sections 4.1, 4.2).  contact_rows / contact_solve are what the 16-lane step
 // kernels of usim_step16.h call; cone_local is also the visit of the full torso (usim_full.h).
-// (included by usim_kernels.hip inside namespace usim, after the LDS layout, group_sync and group_bcast / half_bcast, before usim_episode.h)
+// (included by usim_kernels.hip inside namespace usim, after the LDS layout, group_sync and group_bcast / half_bcast / quad_bcast, before usim_episode.h)
 #pragma once
 
 #define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
@@ -10,6 +10,10 @@
 DI float row_ror8(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, true)); }
 // value of lane l - D of the DPP row, zero in the first D lanes (row_shr:D)
 template <int D> DI float row_shr(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x110 + D, 0xf, 0xf, true)); }
+// Quad layout of a 16-lane group whose halves hold the same eight values (x of lane k and of lane 8 + k is X_k): quads 0 and 1 get X_0..3, quads 2 and 3 get X_4..7, so
+// that quad_bcast serves both halves at once.  Lanes 4-11 take the value four lanes away (row_ror:4 under bank mask 0110; X has period eight, so the direction does not
+// matter), lanes 0-3 and 12-15 keep their own: one move, and only copies -- the bits of X_k are those of the lane that formed it.
+DI float quad_layout(float x) { const int ix = __float_as_int(x); return __int_as_float(__builtin_amdgcn_update_dpp(ix, ix, 0x124, 0xf, 0x6, false)); }
 
 // sum over the lanes of a group, delivered to every lane (three or four DPP steps; lane k + 8 first, so that a 16-lane group whose halves carry the two contacts
 // of a pair adds in the order of an 8-lane group that holds both in one lane: the same bits)
@@ -108,6 +112,54 @@ DI typename LaneVec<T>::mask cone_local(const T b00, const T b01, const T b02, c
     const T aa = V::fma(a1, a1, a2 * a2);
     const T sc = -V::min(lim * V::rsq(aa), V::rcp(det));                           // (v_min keeps the number when aa = 0 makes the product inf or NaN)
     h0 = n0; h1 = V::sel(haslim, a1 * sc, V::splat(0.f)); h2 = V::sel(haslim, a2 * sc, V::splat(0.f));
+    return haslim;
+}
+
+// The same visit for ONE contact per lane (the 16-lane groups that CLONE), with the quantities of its two tangent rows carried as one two-float value from the start:
+// bt = (b01, b02), bA = (b11, b12), bB = (b12, b22), bD = (b11, b22); rt, ft, ht = rows 1 and 2 of r, f, h.  Every component is the operation of cone_local<float> on
+// the same operands in the same order (one IEEE fma, mul or add per half of a v_pk_*; the dot products, the rays and the multiplier stay scalar chains): the same bits.
+// Stated on its own because the vectoriser packs cone_local<float> only after moving registers together and leaves half of these pairs scalar, and because
+// cone_local<float> is also the full torso's visit, whose kernels keep their code.
+DI bool cone_local_rows12(const float b00, const v2f bt, const v2f bA, const v2f bB, const v2f bD, float r0, v2f rt, const float f0, const v2f ft, const float mu,
+                          float& lam, float& h0, v2f& ht) {
+    typedef LaneVec<float> S;
+    typedef LaneVec<v2f> P;
+    const float b12 = bA.y;
+    const float Bf0 = fmaf(bt.y, ft.y, fmaf(bt.x, ft.x, b00 * f0));
+    const v2f Bft = P::fma(bB, P::splat(ft.y), P::fma(bA, P::splat(ft.x), bt * f0));
+    const float vr = fmaf(ft.y, rt.y, fmaf(ft.x, rt.x, f0 * r0)), vBv = fmaf(ft.y, Bft.y, fmaf(ft.x, Bft.x, f0 * Bf0));
+    const float x = S::sel(S::gt(f0, 1e-10f), S::max(-vr * S::rcp(vBv), -1.f), 0.f);
+    r0 = fmaf(x, Bf0, r0); rt = P::fma(P::splat(x), Bft, rt);
+    float n0 = fmaf(x, f0, f0);
+    v2f nt = P::fma(P::splat(x), ft, ft);
+    const float rt2 = fmaf(rt.x, rt.x, rt.y * rt.y);
+    const float irt = S::rsq(S::max(rt2, 1e-30f)), rtn = rt2 * irt;
+    const float sl = S::sel(S::both(S::gt(rt2, 0.f), S::lt(r0, mu * rtn)), -mu * irt, 0.f);
+    const v2f u = sl * rt;                                                         // second direction (1, u)
+    const float Bu0 = fmaf(bt.y, u.y, fmaf(bt.x, u.x, b00));
+    const v2f But = P::fma(bB, P::splat(u.y), P::fma(bA, P::splat(u.x), bt));
+    const float ur = fmaf(u.y, rt.y, fmaf(u.x, rt.x, r0)), uBu = fmaf(u.y, But.y, fmaf(u.x, But.x, Bu0));
+    const float x2 = S::max(-ur * S::rcp(uBu), 0.f);
+    n0 += x2; nt = P::fma(P::splat(x2), u, nt);
+    rt = P::fma(P::splat(x2), But, rt);
+    const float lim = mu * n0;
+    const bool haslim = S::gt(lim, 1e-7f);
+    const v2f qt = rt - P::fma(bB, P::splat(nt.y), bA * nt.x);
+    v2f mt = bD + lam;                                                             // (m11, m22); the adjugate takes them swapped: an op_sel of the same register pair
+    float det = fmaf(mt.x, mt.y, -(b12 * b12));
+    v2f at = P::fma(mt.yx, qt, -(b12 * qt.yx));
+    {
+        const float aa = fmaf(at.x, at.x, at.y * at.y);
+        const v2f ma = mt.yx * at;                                                 // (m22 a1, m11 a2)
+        const float aAa = fmaf(ma.y, at.y, fmaf(ma.x, at.x, -2.f * b12 * at.x * at.y));
+        const float an = aa * S::rsq(S::max(aa, 1e-30f));
+        lam = S::max(fmaf(fmaf(-det, lim, an) * aa, S::rcp(S::max(lim * aAa, 1e-30f)), lam), 0.f);
+    }
+    mt = bD + lam; det = fmaf(mt.x, mt.y, -(b12 * b12));
+    at = P::fma(mt.yx, qt, -(b12 * qt.yx));
+    const float aa = fmaf(at.x, at.x, at.y * at.y);
+    const float sc = -S::min(lim * S::rsq(aa), S::rcp(det));
+    h0 = n0; ht = haslim ? at * sc : P::splat(0.f);
     return haslim;
 }
 
@@ -346,10 +398,11 @@ DI void delassus_blocks(const float* lds, const int eb, const int gl, const int 
 // q = A D for the pairs' summed directions D (one per lane, D_k in lane k).  Up to four contacts: one running sum over them.  More: the sum over contacts 0-3 plus the
 // sum over contacts 4-7 -- in that association in EVERY mapping (an environment's bits must not depend on its wave's neighbours: for one with at most four contacts
 // the second sum is exact zeros) -- which a 16-lane group evaluates in its two halves at once: lanes 0-7 take D_j, lanes 8-15 D_(4+j) from the same row (two bank-masked
-// broadcasts per word), each half multiplies with the four blocks it formed, one rotation by eight lanes adds the halves.  Eight contacts: 63 instructions instead of
-// 96 (round 5), six: 63 / 72.  Used by every iteration and, with a warm start, once before them (A s0): one statement of the association for both
+// broadcasts per word; QUAD: the row goes to the quad layout once per word, then one quad_perm per word and block serves both halves -- 15 moves instead of 24), each half
+// multiplies with the four blocks it formed, one rotation by eight lanes adds the halves.  Eight contacts: 63 instructions (QUAD: 54) instead of 96 (round 5), six:
+// 63 / 72.  Used by every iteration and, with a warm start, once before them (A s0): one statement of the association for both
 // (a function template; as a lambda inside contact_solve the 8-lane split kernel of a cold handle spilled one more register).
-template <int G, bool CLONE, int NCM, int NB>
+template <int G, bool CLONE, bool QUAD, int NCM, int NB>
 DI void delassus_product(const float (&B)[NB][3][3], const float D0, const float D1, const float D2, float& q0, float& q1, float& q2) {
     q0 = 0.f; q1 = 0.f; q2 = 0.f;
     if constexpr (NCM <= 4) {
@@ -361,9 +414,10 @@ DI void delassus_product(const float (&B)[NB][3][3], const float D0, const float
             q2 = fmaf(B[k][2][2], e2, fmaf(B[k][2][1], e1, fmaf(B[k][2][0], e0, q2)));
         }
     } else if constexpr (CLONE) {
+        const float Q0 = QUAD ? quad_layout(D0) : D0, Q1 = QUAD ? quad_layout(D1) : D1, Q2 = QUAD ? quad_layout(D2) : D2;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float e0 = half_bcast(D0, j), e1 = half_bcast(D1, j), e2 = half_bcast(D2, j);
+            const float e0 = QUAD ? quad_bcast(Q0, j) : half_bcast(D0, j), e1 = QUAD ? quad_bcast(Q1, j) : half_bcast(D1, j), e2 = QUAD ? quad_bcast(Q2, j) : half_bcast(D2, j);
             q0 = fmaf(B[j][0][2], e2, fmaf(B[j][0][1], e1, fmaf(B[j][0][0], e0, q0)));
             q1 = fmaf(B[j][1][2], e2, fmaf(B[j][1][1], e1, fmaf(B[j][1][0], e0, q1)));
             q2 = fmaf(B[j][2][2], e2, fmaf(B[j][2][1], e1, fmaf(B[j][2][0], e0, q2)));
@@ -397,7 +451,7 @@ template <bool CLONE> using ContactLane = typename std::conditional<CLONE, float
 //      t = (sum_v d_v'B_v d_v) / (d'Qd) <= 1 (the exact minimiser of the quadratic when every block is solved exactly, never longer) -- a convex combination of feasible points, no projection --; the shared residual moves by t A D,
 //      D_k = d_Ak + d_Bk (three row broadcasts and nine multiply-adds per pair: the only part that grows with the contact count).  `iters` iterations from the forces
 //      fv and multipliers lamv (zero: cold start; WARM: the kept ones, and the shared residual cres first moves to them).  NCM: the wave's largest contact count ----
-template <int G, bool CLONE, bool WARM, int NCM, int NB>
+template <int G, bool CLONE, bool WARM, bool QUAD, bool PAIR, int NCM, int NB>
 DI void jacobi_iterations(const int iters, const float (&B)[NB][3][3], const Sym3& bd, const float (&Rd)[3], const typename LaneVec<ContactLane<CLONE>>::mask ownv,
                           const ContactLane<CLONE> muv, ContactLane<CLONE> (&fv)[3], ContactLane<CLONE>& lamv, float (&cres)[3]) {
     typedef ContactLane<CLONE> VT;
@@ -409,10 +463,38 @@ DI void jacobi_iterations(const int iters, const float (&B)[NB][3][3], const Sym
         float D0 = V::hsum(fv[0]), D1 = V::hsum(fv[1]), D2 = V::hsum(fv[2]);
         if constexpr (CLONE) { D0 += row_ror8(D0); D1 += row_ror8(D1); D2 += row_ror8(D2); }
         float q0, q1, q2;
-        delassus_product<G, CLONE, NCM>(B, D0, D1, D2, q0, q1, q2);
+        delassus_product<G, CLONE, QUAD, NCM>(B, D0, D1, D2, q0, q1, q2);
         cres[0] += q0; cres[1] += q1; cres[2] += q2;
     }
-    for (int it = 0; it < iters; ++it) {
+    if constexpr (PAIR) {
+        static_assert(CLONE, "cone_local_rows12 visits one contact per lane");
+        // one contact per lane: rows 1 and 2 as a pair (cone_local_rows12); the arithmetic of the general statement below, component by component
+        typedef LaneVec<v2f> P;
+        const v2f bt = {bd.b01, bd.b02}, bA = {bd.b11, bd.b12}, bB = {bd.b12, bd.b22}, bD = {bd.b11, bd.b22}, vRt = {Rd[1], Rd[2]};
+        float f0 = fv[0], c0 = cres[0];
+        v2f ft = {fv[1], fv[2]}, ct = {cres[1], cres[2]};
+        for (int it = 0; it < iters; ++it) {
+            float h0, lam = lamv;
+            v2f ht;
+            const bool haslim = cone_local_rows12(bd.b00, bt, bA, bB, bD, fmaf(Rd[0], f0, c0), P::fma(vRt, ft, ct), f0, ft, muv, lam, h0, ht);
+            lamv = V::sel(V::both(ownv, haslim), lam, lamv);
+            const float e0 = V::sel(ownv, h0 - f0, 0.f);
+            const v2f et = ownv ? ht - ft : P::splat(0.f);
+            const float Be0 = fmaf(bt.y, et.y, fmaf(bt.x, et.x, bd.b00 * e0));
+            const v2f Bet = P::fma(bB, P::splat(et.y), P::fma(bA, P::splat(et.x), bt * e0));
+            float num = -fmaf(et.y, Bet.y, fmaf(et.x, Bet.x, e0 * Be0));
+            const float D0 = e0 + row_ror8(e0), D1 = et.x + row_ror8(et.x), D2 = et.y + row_ror8(et.y);
+            float q0, q1, q2;
+            delassus_product<G, CLONE, QUAD, NCM>(B, D0, D1, D2, q0, q1, q2);
+            const v2f qt = {q1, q2}, wt = P::fma(vRt, et, qt);
+            float den = fmaf(et.y, wt.y, fmaf(et.x, wt.x, e0 * fmaf(Rd[0], e0, q0)));
+            num = group_allsum<G>(num); den = group_allsum<G>(den);
+            const float t = (den > 0.f) ? fminf(-num * rcp_(den), 1.f) : 0.f;
+            f0 = fmaf(t, e0, f0); ft = P::fma(P::splat(t), et, ft);
+            c0 = fmaf(t, q0, c0); ct = P::fma(P::splat(t), qt, ct);
+        }
+        fv[0] = f0; fv[1] = ft.x; fv[2] = ft.y; cres[0] = c0; cres[1] = ct.x; cres[2] = ct.y;
+    } else for (int it = 0; it < iters; ++it) {
         VT dv[3];
         float num, D0, D1, D2;
         {
@@ -430,7 +512,7 @@ DI void jacobi_iterations(const int iters, const float (&B)[NB][3][3], const Sym
         }
         if constexpr (CLONE) { D0 += row_ror8(D0); D1 += row_ror8(D1); D2 += row_ror8(D2); }       // D_k = d_Ak + d_Bk in both halves
         float q0, q1, q2;
-        delassus_product<G, CLONE, NCM>(B, D0, D1, D2, q0, q1, q2);
+        delassus_product<G, CLONE, QUAD, NCM>(B, D0, D1, D2, q0, q1, q2);
         float den = V::hsum(V::fma(dv[2], V::fma(vR2, dv[2], V::splat(q2)), V::fma(dv[1], V::fma(vR1, dv[1], V::splat(q1)), dv[0] * V::fma(vR0, dv[0], V::splat(q0)))));
         num = group_allsum<G>(num); den = group_allsum<G>(den);
         const float t = (den > 0.f) ? fminf(-num * rcp_(den), 1.f) : 0.f;
@@ -481,13 +563,18 @@ DI void contact_wrench(const int gl, const float (&w)[3][6], const float (&g)[3]
 // PRE: the arm-independent half of the rows comes from contact_rows (P); otherwise it is formed here (vz and the records; P is not read), into locals: handing the
 // rows through the struct cost the 16-lane split kernel 0.5 us per step.
 // WR = WarmRec: the solve starts from the kept record `wr` of the lane (matched by element against this pass's contact list) and leaves the new one in it.
-template <int G, bool PRE, class WR>
+// SHORT: the shortened Jacobi pass of groups that CLONE -- three pieces, each switched by its own constant below (same bits with or without any of them; DESIGN.md
+// section 10).  The split kernel asks for it; the single-wave 16-lane kernels, which run at the register limit and spill more with any of the three, do not.
+template <int G, bool PRE, bool SHORT, class WR>
 DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M, const DevCfg& C, const int nc, const int ncmax, const int* cel,
                       const float* Li, const float* alpha, const float* vs, const float mu, const float vz, const ContactRows& P, float* W, float* gf,
                       unsigned long long* dbg, WR& wr) {
     constexpr bool WARM = !std::is_same<WR, NoWarm>::value;
     constexpr bool CLONE = (G == 16) && !PRE;                            // lanes 8-15 of a 16-lane group clone lanes 0-7: delassus_blocks
     constexpr int NB = CLONE ? 4 : MAXC;
+    constexpr bool QUAD = CLONE && SHORT;                                // the summed directions in the quad layout: one DPP move per broadcast word (delassus_product)
+    constexpr bool PAIR = CLONE && SHORT;                                // the tangent rows of a contact as one two-float value (cone_local_rows12)
+    constexpr bool ONE = CLONE && SHORT;                                 // five to eight contacts: one instantiation of the iterations
     typedef ContactLane<CLONE> VT;
     typedef LaneVec<VT> V;
     const int cl = CLONE ? (gl & 7) : gl;
@@ -522,17 +609,18 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
     VT fv[3] = {V::splat(0.f), V::splat(0.f), V::splat(0.f)}, lamv = V::splat(0.f);
     int myel = -1;
     warm_match(lds, eb, gl, cl, own, ownv, wr, myel, fv, lamv);
-    // (one straight-line instantiation per wave-uniform contact count)
-    auto iterations = [&](auto NCM) { jacobi_iterations<G, CLONE, WARM, decltype(NCM)::value>(C.pgs_iters, B, bd, Rd, ownv, muv, fv, lamv, cres); };
-    switch (ncmax) {
+    // (one straight-line instantiation per wave-uniform contact count; groups that CLONE run the same code for five to eight contacts -- four blocks per half,
+    //  whatever the count -- and with ONE they share one)
+    auto iterations = [&](auto NCM) { jacobi_iterations<G, CLONE, WARM, QUAD, PAIR, decltype(NCM)::value>(C.pgs_iters, B, bd, Rd, ownv, muv, fv, lamv, cres); };
+    switch ((ONE && ncmax > 4) ? MAXC : ncmax) {
         case 1: iterations(std::integral_constant<int, 1>{}); break;
         case 2: iterations(std::integral_constant<int, 2>{}); break;
         case 3: iterations(std::integral_constant<int, 3>{}); break;
         case 4: iterations(std::integral_constant<int, 4>{}); break;
-        case 5: iterations(std::integral_constant<int, 5>{}); break;
-        case 6: iterations(std::integral_constant<int, 6>{}); break;
-        case 7: iterations(std::integral_constant<int, 7>{}); break;
-        default: iterations(std::integral_constant<int, 8>{}); break;
+        case 5: if constexpr (!ONE) iterations(std::integral_constant<int, 5>{}); break;
+        case 6: if constexpr (!ONE) iterations(std::integral_constant<int, 6>{}); break;
+        case 7: if constexpr (!ONE) iterations(std::integral_constant<int, 7>{}); break;
+        default: iterations(std::integral_constant<int, MAXC>{}); break;
     }
     warm_keep(wr, myel, fv, lamv);
     USIM_STAMP(dbg, 10);

@@ -108,6 +108,20 @@ DI float half_bcast(float v, int J) {
     }
     return __int_as_float(r);
 }
+// 16-lane groups, quad layout: a row whose quads 0 and 1 hold X_0..3 and whose quads 2 and 3 hold X_4..7 (quad_layout of usim_contact.h) delivers X_J to lanes 0-7 and
+// X_(4 + J) to lanes 8-15 with ONE quad_perm:[J,J,J,J] (J = 0..3, a compile-time constant after unrolling) where half_bcast takes two: a row broadcast has one source lane
+DI float quad_bcast(float v, int J) {
+    const int iv = __float_as_int(v);
+    int r = iv;
+    switch (J) {
+        case 0: r = __builtin_amdgcn_mov_dpp(iv, 0x00, 0xf, 0xf, true); break;
+        case 1: r = __builtin_amdgcn_mov_dpp(iv, 0x55, 0xf, 0xf, true); break;
+        case 2: r = __builtin_amdgcn_mov_dpp(iv, 0xAA, 0xf, 0xf, true); break;
+        case 3: r = __builtin_amdgcn_mov_dpp(iv, 0xFF, 0xf, 0xf, true); break;
+        default: break;
+    }
+    return __int_as_float(r);
+}
 
 // Phase timeline probe (diagnostics only): wave 0 of workgroup 0 stamps the shader clock when a buffer is given.  The stamps exist only in the profiling
 // build (make prof -> libusim_prof.so): each one is a branch, and sixteen of them cost the production kernel 2 % (25.6 vs 25.1 us/step).  -DUSIM_TSTAMP_NOWAIT (what

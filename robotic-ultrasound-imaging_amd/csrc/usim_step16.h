@@ -536,7 +536,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
                 for (int b = 0; b <= a; ++b) Lp[PK(a, b)] = mb[MB_OP + a * 8 + b];
             }
             XSTAMP(2);
-            contact_solve<G, EARLY>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, P, W, gf, dbg, cy.wr);
+            contact_solve<G, EARLY, true>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, P, W, gf, dbg, cy.wr);
             XSTAMP(3);
         } else warm_clear(cy.wr);                                        // (no contact in the wave: nothing kept)
         if (gl == 0) {
@@ -1012,8 +1012,8 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
                 for (int b = 0; b <= a; ++b) Lp[PK(a, b)] = rbc<G, TASK_LANE[a]>(Li[b]);
             });
             USIM_STAMP(dbg, 8);
-            if constexpr (MODE == 0) contact_solve<G, false>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, ContactRows{}, W, gf, dbg, cy.wr);
-            else { NoWarm cold; contact_solve<G, false>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, ContactRows{}, W, gf, dbg, cold); }
+            if constexpr (MODE == 0) contact_solve<G, false, false>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, ContactRows{}, W, gf, dbg, cy.wr);
+            else { NoWarm cold; contact_solve<G, false, false>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, ContactRows{}, W, gf, dbg, cold); }
         } else warm_clear(cy.wr);                                        // (no contact in the wave: nothing kept)
         USIM_STAMP(dbg, 11);
         // ---- element accelerations a = a~ + Linv[:, e_c] gf_c, semi-implicit Euler, write back (a reset leaves the lattice at rest) ----

@@ -1,6 +1,8 @@
 """Static census of one kernel's gfx950 ISA: instruction mix, spill traffic (v_readlane / v_writelane of spilled SGPRs, scratch), and the same per loop
 (backward branches), so that what sits inside the 256-step loop can be told from what runs once per launch.
-usage: hipcc ... -S --cuda-device-only -o usim.s usim_api.hip ; python tools/isa_census.py usim.s '<mangled-name prefix>'"""
+usage: hipcc ... -S --cuda-device-only -o usim.s usim_api.hip ; python tools/isa_census.py usim.s '<mangled-name prefix>' [LO HI]
+With LO HI every loop of LO..HI instructions is listed too, in program order, with its mix of packed, DPP and move instructions (the Jacobi passes of the contact solve:
+150 250; in the split kernel they stand in the order >= 5 contacts, 4, 3, 2, 1)."""
 import collections, re, sys
 path, key = sys.argv[1], sys.argv[2]
 lines = open(path).read().split("\n")
@@ -26,3 +28,13 @@ loops.sort(key=lambda x: x[0] - x[1])
 for a, b in loops[:8]:
     cc = census(body[a:b + 1])
     print(f"  loop lines {a}-{b}: {sum(cc.values())} instructions;", ", ".join(f"{k} {cc[k]}" for k in WATCH))
+if len(sys.argv) > 4:
+    lo, hi = int(sys.argv[3]), int(sys.argv[4])
+    for a, b in sorted(loops):
+        seg = [l.strip() for l in body[a:b + 1] if is_inst(l)]
+        if lo <= len(seg) <= hi:
+            n = lambda f: sum(1 for x in seg if f(x))
+            dpp = lambda x: "dpp" in x.split()[0] or " row_" in x or "quad_perm" in x
+            print(f"  loop lines {a}-{b}: {len(seg)} instructions; v_pk_* {n(lambda x: x.startswith('v_pk_'))}, dpp {n(dpp)} (v_mov_b32_dpp {n(lambda x: x.startswith('v_mov') and dpp(x))}),"
+                  f" v_mov* {n(lambda x: x.startswith('v_mov'))}, v_cndmask {n(lambda x: x.startswith('v_cndmask'))}, s_nop {n(lambda x: x.startswith('s_nop'))},"
+                  f" other SALU {n(lambda x: x.startswith('s_') and not x.startswith('s_nop'))}")

@@ -253,6 +253,41 @@ int usim_set_body_state(usim_handle* h, const double* body);
 int usim_get_warm_start(usim_handle* h, float* w);
 int usim_set_warm_start(usim_handle* h, const float* w);
 
+/* ---- snapshots: save, load and fork the state of environments ON THE DEVICE (robosuite's sim.get_state() / sim.set_state(), batched and indexed).  usim_get_state /
+ * usim_set_state above go through the host, synchronise and rebuild every reset-bank ring: a checkpoint file.  These two stay inside a rollout loop: a shooting planner
+ * that evaluates K action sequences from one state, two policies compared from identical states, a restart from stored states, a rewind after a probe step.
+ *
+ * A snapshot is a caller-owned device buffer snap_dev [m][W] of float32 rows, W = usim_snapshot_words(h), 16-byte aligned (every W is a multiple of 4 words; everything
+ * moves as 16-byte accesses).  The library allocates nothing.  A row is an OPAQUE device format -- not usim_get_state's:
+ *     words [0, 40)        the scalar state words in the order of usim_get_state's block, as the device holds them: words 0 - 6 are q - q0, the integer fields
+ *                          (t, has_touched, episode, status) are int32 bit patterns
+ *     words [40, 40 + L)   the lattice words: L = 0 (USIM_TORSO_NONE), 200 (USIM_TORSO_TOP: s and sdot of the 99 elements), 1712 (USIM_TORSO_FULL: the 270 sliders, the
+ *                          free torso body and the warm start of its contact solve)
+ *     then                 USIM_TORSO_TOP with warm_start = 1: the USIM_WARM_WORDS words of the solver's kept contact list (the elements as int32 bit patterns)
+ * It is valid for the library version that wrote it, not a file format.
+ *
+ * usim_save_envs: row r receives the state of environment env_index_dev[r] (int32 [m]; NULL: environments 0 .. m - 1, which needs m <= n).  An index outside [0, n) leaves
+ * its row as it is.  The handle is not modified.
+ * usim_load_envs: environment i takes row row_of_env_dev[i] (int32 [n], required); a negative value, or one >= m, keeps the environment bit for bit.  Every word of the row is
+ * written EXCEPT THE EPISODE COUNTER: the destination continues the saved episode -- trajectory, stiffness / damping / friction, t, has_touched, ep_return, status bits, lattice,
+ * body, solver warm start -- under its own counter, and when that episode ends it goes on with ITS OWN next episode (counter + 1).  The reset bank of an environment is a ring
+ * of the episodes that follow its own counter, and the refill orders it has outstanding name that counter; with the counter left alone both stay valid, so a load needs no bank
+ * fill and touches no host counter.  (A load that restores the counter as well is usim_set_state, at the price of a reset.)  Stepping draws nothing per environment -- the only
+ * per-environment streams are the reset draws, keyed (seed, env_offset + env, episode), and the synthetic actions of usim_rollout_random --, so environments that hold the same
+ * row and are given the same actions compute the same bits until that episode ends.
+ * Both: kernel launches on `stream` and nothing else -- no synchronisation, no event, no allocation; capture-safe like usim_refill_bank.  A NULL handle or buffer, m <= 0 or a
+ * snap_dev off the 16-byte grid: USIM_ERR_INVALID, nothing enqueued.  There is no in-place fork: an environment read as a source while another launch lane writes it as a
+ * destination would race; save, then load (vec_env.py fork).
+ * Rows may be loaded into ANOTHER handle.  The caller's responsibility: equal usim_snapshot_words and an equal configuration -- torso, torso_shape, robot, mode, substeps, the
+ * probe_* and solver fields (pgs_iters, pair_model, probe_geoms, warm_start), the physical constants.  The number of environments, env_offset, seed and the kernel mapping may differ. */
+#define USIM_SNAPSHOT_WORDS_RIGID     40
+#define USIM_SNAPSHOT_WORDS_TOP       240      /* 40 + 200 */
+#define USIM_SNAPSHOT_WORDS_TOP_WARM  312      /* + USIM_WARM_WORDS */
+#define USIM_SNAPSHOT_WORDS_FULL      1752     /* 40 + 1712 */
+int usim_snapshot_words(const usim_handle* h);           /* one of the four; < 0: error code */
+int usim_save_envs(usim_handle* h, const int32_t* env_index_dev, int m, float* snap_dev, void* stream);
+int usim_load_envs(usim_handle* h, const float* snap_dev, int m, const int32_t* row_of_env_dev, void* stream);
+
 /* Diagnostics: runs one step (in-kernel synthetic actions of `step`, auto-reset on) on the default stream, blocks, and returns
  * shader-clock stamps taken in workgroup 0: ticks[0..16] by wave 0 at the phase boundaries of the single-wave step
  * kernels, ticks[20..29] / ticks[30..38] by the arm wave / the lattice wave of the split kernel at their barriers (min(max_ticks, 64) words

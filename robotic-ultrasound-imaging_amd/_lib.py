@@ -30,6 +30,22 @@ MODE = {"tracking": 0, "fixed": 1, "variable_z": 2, "wrench": 3}
 TORSO = {"none": 0, "rigid": 0, "top": 1, "soft": 1, "full": 2}
 ROBOT = {"Panda": 0, "UR5e": 1}             # ultrasound.py:137
 
+# usim_save_envs / usim_load_envs: 32-bit words of a snapshot row (USIM_SNAPSHOT_WORDS_*)
+SNAPSHOT_WORDS_RIGID = 40          # the scalar state words
+SNAPSHOT_WORDS_TOP = 240           # + the 200 lattice words of the top-face torso
+SNAPSHOT_WORDS_TOP_WARM = 312      # + WARM_WORDS, the solver's kept contact list (warm_start = 1)
+SNAPSHOT_WORDS_FULL = 1752         # scalar words + the 1712 lattice / body / solver words of the full torso
+
+
+def snapshot_words(torso, warm=False):
+    """usim_snapshot_words of a handle with this torso (a key of TORSO, or its number) and warm_start setting; the warm start adds words to the top-face row only"""
+    t = TORSO[torso] if isinstance(torso, str) else int(torso)
+    if t not in (0, 1, 2):
+        raise ValueError(f"torso must be one of {sorted(TORSO)} or 0 .. 2, got {torso!r}")
+    if t == 1:
+        return SNAPSHOT_WORDS_TOP_WARM if warm else SNAPSHOT_WORDS_TOP
+    return SNAPSHOT_WORDS_FULL if t == 2 else SNAPSHOT_WORDS_RIGID
+
 
 class UsimConfig(C.Structure):
     """struct usim_config (include/usim.h)"""
@@ -107,6 +123,9 @@ SYMBOLS = {
     "usim_set_body_state": (C.c_int, [C.c_void_p, C.c_void_p]),
     "usim_get_warm_start": (C.c_int, [C.c_void_p, C.c_void_p]),
     "usim_set_warm_start": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "usim_snapshot_words": (C.c_int, [C.c_void_p]),
+    "usim_save_envs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "usim_load_envs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "usim_profile_step": (C.c_int, [C.c_void_p, C.POINTER(UsimStepIO), C.c_int64, C.POINTER(C.c_uint64), C.c_int]),
     "usim_strerror": (C.c_char_p, [C.c_int]),
     "usim_last_hip_error": (C.c_char_p, [C.c_void_p]),

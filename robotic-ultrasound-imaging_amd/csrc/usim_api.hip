@@ -17,6 +17,7 @@
 #include "usim_device.h"
 #include "usim_robot.h"
 #include "usim_kernels.hip"      // single translation unit: kernels + host launcher (no relocatable device code)
+#include "usim_snapshot.h"       // usim_save_envs / usim_load_envs (behind the step kernels)
 
 
 using namespace usim;
@@ -772,6 +773,39 @@ int usim_set_state(usim_handle* h, const float* scalars, const float* lattice) {
         if (rc) return rc;
     }
     HIPCHK(h, hipDeviceSynchronize());
+    return USIM_OK;
+}
+
+// ---- snapshots: whole environments copied between the state block and a caller-owned device buffer of rows (usim_snapshot.h), one launch on the caller's stream and
+// nothing else -- no synchronisation, no event, no allocation, no host counter: capture-safe like usim_refill_bank
+static_assert(USIM_SNAPSHOT_WORDS_RIGID == F_NSCALAR && USIM_SNAPSHOT_WORDS_TOP == F_NSCALAR + LAT_ENV_WORDS && USIM_SNAPSHOT_WORDS_TOP_WARM == F_NSCALAR + LAT_ENV_WORDS + WARM_WORDS &&
+              USIM_SNAPSHOT_WORDS_FULL == F_NSCALAR + LATF_ENV_WORDS, "include/usim.h");
+static SnapLayout snap_layout(const usim_handle* h) {
+    return {h->cfg.torso == USIM_TORSO_FULL ? LATF_ENV_WORDS : (h->n_el ? LAT_ENV_WORDS : 0), h->warm ? WARM_WORDS : 0, h->bank_row0};
+}
+static unsigned snap_grid(int rows, int lanes) { return (unsigned)(((size_t)rows * lanes + SNAP_WG - 1) / SNAP_WG); }
+
+int usim_snapshot_words(const usim_handle* h) { return h ? snap_row_words(snap_layout(h)) : USIM_ERR_INVALID; }
+
+int usim_save_envs(usim_handle* h, const int32_t* env_index_dev, int m, float* snap_dev, void* stream) {
+    if (!h || !snap_dev || m <= 0 || (reinterpret_cast<uintptr_t>(snap_dev) & 15) || (!env_index_dev && m > h->n)) return USIM_ERR_INVALID;
+    DeviceGuard guard(h->device);
+    const SnapLayout L = snap_layout(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (h->map == Mapping::FULL) hipLaunchKernelGGL(usim_save_envs_kernel<64>, dim3(snap_grid(m, 64)), dim3(SNAP_WG), 0, s, h->state, h->n, h->npad, L, env_index_dev, m, snap_dev);
+    else hipLaunchKernelGGL(usim_save_envs_kernel<16>, dim3(snap_grid(m, 16)), dim3(SNAP_WG), 0, s, h->state, h->n, h->npad, L, env_index_dev, m, snap_dev);
+    HIPCHK(h, hipGetLastError());
+    return USIM_OK;
+}
+
+int usim_load_envs(usim_handle* h, const float* snap_dev, int m, const int32_t* row_of_env_dev, void* stream) {
+    if (!h || !snap_dev || !row_of_env_dev || m <= 0 || (reinterpret_cast<uintptr_t>(snap_dev) & 15)) return USIM_ERR_INVALID;
+    DeviceGuard guard(h->device);
+    const SnapLayout L = snap_layout(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (h->map == Mapping::FULL) hipLaunchKernelGGL(usim_load_envs_kernel<64>, dim3(snap_grid(h->n, 64)), dim3(SNAP_WG), 0, s, h->state, h->n, h->npad, L, snap_dev, m, row_of_env_dev);
+    else hipLaunchKernelGGL(usim_load_envs_kernel<16>, dim3(snap_grid(h->n, 16)), dim3(SNAP_WG), 0, s, h->state, h->n, h->npad, L, snap_dev, m, row_of_env_dev);
+    HIPCHK(h, hipGetLastError());
     return USIM_OK;
 }
 

@@ -195,6 +195,64 @@ class UltrasoundVecEnv:
         self._check(self.lib.usim_random_actions(self._handle, int(step), out.data_ptr(), self._stream()))
         return out
 
+    # ---- snapshots: save / load / fork environment states on the device (include/usim.h usim_save_envs, usim_load_envs) ------
+    @property
+    def snapshot_words(self):
+        """float32 words of one snapshot row of this env (usim_snapshot_words)"""
+        w = int(self.lib.usim_snapshot_words(self._handle))
+        if w < 0:
+            self._check(w)
+        return w
+
+    def _index_tensor(self, x, length, name):
+        t = torch.as_tensor(x, device=self.device)
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            t = t.to(torch.int32).contiguous()
+        if tuple(t.shape) != (length,):
+            raise ValueError(f"{name} must have shape {(length,)}, got {tuple(t.shape)}")
+        return t
+
+    def save_envs(self, indices=None, out=None):
+        """Copy the state of the environments `indices` (int tensor [m]; None: all) into rows of a float32 device tensor [m, snapshot_words] and return it.  `out`: a
+        contiguous float32 tensor of this device with at least m rows to write into; its first m rows are returned (rows beyond m, and the row of an index outside
+        [0, n), keep what they hold).
+        One kernel launch on the current stream; the env is not modified.  A row is an opaque device format (include/usim.h), valid for load_envs of this env or of
+        another one with the same configuration."""
+        w = self.snapshot_words
+        idx = None if indices is None else self._index_tensor(indices, len(indices), "indices")
+        m = self.num_envs if idx is None else int(idx.shape[0])
+        if out is None:
+            out = torch.empty((m, w), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != w or out.shape[0] < m:
+            raise ValueError(f"out must be a contiguous float32 tensor [>= {m}, {w}] on {self.device}")
+        self._check(self.lib.usim_save_envs(self._handle, None if idx is None else idx.data_ptr(), m, out.data_ptr(), self._stream()))
+        self._last_snap_args = (idx, out)     # keep the tensors alive until the kernel has run
+        return out[:m]
+
+    def load_envs(self, snap, rows):
+        """Environment i continues from row rows[i] of `snap` (float32 [m, snapshot_words], from save_envs); rows[i] < 0 (or >= m) keeps it.  Everything is restored but the
+        episode counter: the environment finishes the saved episode and then goes on with its own next one (include/usim.h usim_load_envs).  One kernel launch on the
+        current stream.  The observation buffer is not touched: fork() gathers it, or step once."""
+        if snap.dtype != torch.float32 or snap.device != self.device or not snap.is_contiguous() or snap.dim() != 2 or snap.shape[1] != self.snapshot_words:
+            raise ValueError(f"snap must be a contiguous float32 tensor [m, {self.snapshot_words}] on {self.device}")
+        r = self._index_tensor(rows, self.num_envs, "rows")
+        self._check(self.lib.usim_load_envs(self._handle, snap.data_ptr(), int(snap.shape[0]), r.data_ptr(), self._stream()))
+        self._last_snap_args = (r, snap)
+
+    def fork(self, src):
+        """Environment i continues from the present state of environment src[i] (int tensor [n]; src[i] == i keeps it): save_envs + load_envs, and the rows of the
+        observation buffer gathered the same way, so that the next policy call sees the forked observations.  Returns the observation tensor.  Nothing touches the host."""
+        s = self._index_tensor(src, self.num_envs, "src")
+        if getattr(self, "_fork_snap", None) is None:
+            self._fork_snap = torch.empty((self.num_envs, self.snapshot_words), dtype=torch.float32, device=self.device)
+            self._fork_self = torch.arange(self.num_envs, dtype=torch.int64, device=self.device)
+        snap = self.save_envs(out=self._fork_snap)
+        self.load_envs(snap, s)
+        s64 = s.long()
+        gather = torch.where((s64 >= 0) & (s64 < self.num_envs), s64, self._fork_self)      # (an index outside [0, n) keeps the environment, as load_envs does)
+        self._obs.copy_(self._obs.index_select(0, gather))
+        return self._obs
+
     def _block_io(self, block):
         """usim_step_io over a rollout block (dict of [T, n, ...] device tensors: obs, rew, done and optionally act)."""
         act = block.get("act")

@@ -204,6 +204,20 @@ int usim_random_actions(usim_handle* h, int64_t step, float* act_dev, void* stre
  * slice k (SB3 RolloutBuffer layout, the unit that is all-gathered across GPUs). */
 int usim_rollout_random(usim_handle* h, int64_t first_step, int nsteps, const usim_step_io* io, int block_advance, void* stream);
 
+/* Enqueues nsteps consecutive steps whose actions are the CALLER's: io->act_dev (required) is an action block [nsteps][n][A] and step k plays slice k -- a planner's
+ * candidate sequences, a recorded trajectory to replay, an open-loop identification input, the zero actions of src/main.py.  Auto-reset is on.  The call equals nsteps
+ * calls of usim_step(h, io_k, 1, stream) with act_dev = slice k, bit for bit: every output and the whole state afterwards, for every mapping, every steps_per_launch,
+ * across the 256-step refill period of the reset bank, with warm_start, and with substeps > 1 (the action of a control step holds for all its physics substeps).  A
+ * non-finite action component counts as 0, as in usim_step.  What it saves is the launch path: the steps run in the multi-step launches of usim_rollout_random (up to
+ * usim_set_steps_per_launch steps each, never across the refill period; the full torso always launches step by step), which keep the state in registers and the
+ * tables in LDS between steps and pay launch latency once.
+ * block_advance governs the OUTPUT buffers only, exactly as in usim_rollout_random: 0 = every step writes the same buffers (they hold the last step's results
+ * afterwards), != 0 = the non-NULL output buffers of io are rollout blocks [nsteps][n][...] and step k writes slice k.  The action block is indexed by step either
+ * way.  act_out_dev is ignored (nothing is drawn).
+ * nsteps == 0: USIM_OK, nothing enqueued.  A NULL handle, io, act_dev or required output buffer, or nsteps < 0: USIM_ERR_INVALID, nothing enqueued.  Capture: the
+ * rules of usim_rollout_random and usim_step -- the refill counter lives on the host, so a recorded sequence starts and ends with usim_refill_bank. */
+int usim_rollout_actions(usim_handle* h, int nsteps, const usim_step_io* io, int block_advance, void* stream);
+
 /* Refill the reset bank now (the launch usim_step issues by itself every 256 steps: the initial states of the episodes that will reuse the ring slots
  * consumed since the last refill) and restart the 256-step period.  For callers that record a FIXED sequence of steps once and replay it -- a HIP
  * graph captured around T x usim_step (policy.GraphedCollector): the period counter lives on the host and does not advance at replay, so such a
@@ -319,6 +333,17 @@ int usim_profile_step(usim_handle* h, const usim_step_io* io, int64_t step, uint
 #define USIM_PACK_EPISODE_WORDS 23         /* env index (int32 bits), ep_length (int32 bits), ep_return, status (int32 bits; 0 when io->status_dev is NULL), terminal_observation[19] */
 #define USIM_PACK_WORDS(n) (4 + (size_t)(n) * (USIM_PACK_HEAD_WORDS + USIM_PACK_EPISODE_WORDS))
 int usim_pack_step(const usim_step_io* io, int n, float* packed_dev, void* stream);
+
+/* ---- the score of a rollout block: for every environment the discounted return of its FIRST episode inside the block and that episode's length, in one launch -- the
+ * scoring pass of a shooting planner after usim_rollout_actions, in place of 2 nsteps small tensor kernels (ret += rew * alive;
+ * alive &= ~done).  rew_block_dev [nsteps][n] float32 and done_block_dev [nsteps][n] bytes are the rew / done blocks of a rollout.  For environment i:
+ *     L = 1 + the first k with done[k][i] != 0 (any non-zero byte), or nsteps if there is none
+ *     return_dev[i] = sum over k < L of gamma^k rew[k][i]          length_dev[i] = L  (int32; length_dev may be NULL)
+ * Past its first done an environment of an auto-reset rollout plays an episode of its own: those words do not enter the sum (a NaN there does not reach the result).
+ * The arithmetic is fixed -- float32, in step order, ret = fmaf(disc, r, ret); disc *= gamma; from ret = 0, disc = 1 --, so the result is a function of the inputs
+ * alone; at gamma = 1 it is the float32 sum in step order.  No handle, no allocation, no synchronisation: one kernel launch, capture-safe.  A NULL buffer other than
+ * length_dev, n <= 0 or nsteps <= 0: USIM_ERR_INVALID, nothing is written. */
+int usim_score_block(const float* rew_block_dev, const uint8_t* done_block_dev, int nsteps, int n, float gamma, float* return_dev, int32_t* length_dev, void* stream);
 
 /* ---- the caller's side of env.step() on the device: SB3 VecNormalize + MlpPolicy forward + sampling + rollout-buffer
  * writes + GAE, fused into a few kernels per rollout step (csrc/usim_policy.hip).  Everything is a device pointer into the CALLER's tensors

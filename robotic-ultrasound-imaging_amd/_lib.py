@@ -99,6 +99,7 @@ SYMBOLS = {
     "usim_policy_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
     "usim_pack_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_void_p, C.c_void_p]),
+    "usim_score_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_default_config": (C.c_int, [C.POINTER(UsimConfig)]),
     "usim_create": (C.c_int, [C.POINTER(UsimConfig), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "usim_destroy": (None, [C.c_void_p]),
@@ -116,6 +117,7 @@ SYMBOLS = {
     "usim_step": (C.c_int, [C.c_void_p, C.POINTER(UsimStepIO), C.c_int, C.c_void_p]),
     "usim_random_actions": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "usim_rollout_random": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(UsimStepIO), C.c_int, C.c_void_p]),
+    "usim_rollout_actions": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(UsimStepIO), C.c_int, C.c_void_p]),
     "usim_time_steps": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(UsimStepIO), C.c_int, C.c_void_p, C.POINTER(C.c_float)]),
     "usim_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -54,9 +54,22 @@ static bool multi_step(Mapping m) { return m != Mapping::FULL; }           // se
 // everything else); model and configuration by value, or through pointers for the split kernels
 struct Kernel { void (*step)(const DevModel, const DevCfg, float*, int, int, const DevIO, int, long long); void (*split)(const DevModel*, const DevCfg*, float*, int, int, const DevIO, int, long long);
                 int epb, nt, lds_words; };
-static Kernel kernel_of(Mapping m, int mode, bool multi, bool warm) {
+// acts: the launch plays a caller's action block (usim_rollout_actions, several control steps per launch): the multi-step kernel that moves io.act on between them
+static Kernel kernel_of(Mapping m, int mode, bool multi, bool warm, bool acts = false) {
     if (mode != 0 && soft_torso(m)) m = Mapping::SOFT16_W2;
     const bool r = mode != 0, mu = !r && multi;
+    if (mu && acts && m != Mapping::FULL) {
+        Kernel k = kernel_of(m, mode, multi, warm);            // the launch geometry of the mapping's multi-step kernel
+        const bool w = warm && soft_torso(m);
+        switch (m) {
+            case Mapping::RIGID16: k.step = usim_step16_acts_kernel<0, 2>; break;
+            case Mapping::SOFT16_W1: k.step = w ? usim_step16_acts_kernel<1, 1, true> : usim_step16_acts_kernel<1, 1>; break;
+            case Mapping::SOFT16_W2: k.step = w ? usim_step16_acts_kernel<1, 2, true> : usim_step16_acts_kernel<1, 2>; break;
+            case Mapping::SPLIT16: k.split = w ? usim_step32_acts_kernel<16, true> : usim_step32_acts_kernel<16>; break;
+            default: k.split = w ? usim_step32_acts_kernel<8, true> : usim_step32_acts_kernel<8>; break;
+        }
+        return k;
+    }
     if (warm && soft_torso(m)) {
         constexpr int L16 = arm_lds_base<1, 0, 16>() + ARM_LDS_WORDS;
         if (r) return {usim_step16_kernel<1, 2, 1, false, true>, nullptr, 16, 256, L16};
@@ -351,8 +364,8 @@ static int build_model(usim_handle* h) {
 static int set_lds_limits(usim_handle* h) {
     for (int m = 0; m <= (int)Mapping::SPLIT8; ++m)
         if ((Mapping)m == h->map || (soft_torso((Mapping)m) && soft_torso(h->map)))
-            for (int i = 0; i < 4; ++i) {
-                const Kernel k = kernel_of((Mapping)m, i & 1, i >> 1, h->warm);
+            for (int i = 0; i < 5; ++i) {                        // (step, reset) x (single, multi-step), then the multi-step kernel of usim_rollout_actions
+                const Kernel k = i < 4 ? kernel_of((Mapping)m, i & 1, i >> 1, h->warm) : kernel_of((Mapping)m, 0, true, h->warm, true);
                 HIPCHK(h, hipFuncSetAttribute(k.step ? (const void*)k.step : (const void*)k.split, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_words * (int)sizeof(float)));
             }
     return USIM_OK;
@@ -370,7 +383,7 @@ static int warm_rows_reset(usim_handle* h) {
 template <int MODE>
 static int launch(usim_handle* h, DevIO io, int flags, long long rstep, hipStream_t s) {
     io.bank_row0 = h->bank_row0;
-    const Kernel k = kernel_of(h->map, MODE, io.nsub > 1 || h->C.substeps > 1, h->warm);
+    const Kernel k = kernel_of(h->map, MODE, io.nsub > 1 || h->C.substeps > 1, h->warm, io.nsub > 1 && io.act);
     const dim3 grid((h->n + k.epb - 1) / k.epb), block(k.nt);
     const size_t lds = (size_t)k.lds_words * sizeof(float);
     if (k.step) hipLaunchKernelGGL(k.step, grid, block, lds, s, h->M, h->C, h->state, h->n, h->npad, io, flags, rstep);
@@ -614,26 +627,43 @@ int usim_random_actions(usim_handle* h, int64_t step, float* act_dev, void* stre
     return USIM_OK;
 }
 
-int usim_rollout_random(usim_handle* h, int64_t first_step, int nsteps, const usim_step_io* s, int block_advance, void* stream) {
-    if (!h || nsteps < 0) return USIM_ERR_INVALID;
-    DeviceGuard guard(h->device);
-    DevIO io; int rc = fill_io(s, io, false);
-    if (rc) return rc;
-    io.act = nullptr;
-    // the 16-lane kernels run up to h->steps_per_launch consecutive steps per launch (usim_step16.h step16_body); a launch never crosses the
-    // refill period of the reset bank (an environment consumes at most one ring slot per step)
+// nsteps consecutive auto-reset steps in multi-step launches (usim_rollout_random, usim_rollout_actions; `flags` and io.act are all that differs between them).
+// The 16-lane kernels run up to h->steps_per_launch consecutive steps per launch (usim_step16.h step16_body); a launch never crosses the refill period of the
+// reset bank (an environment consumes at most one ring slot per step).  io.act, where there is one, is an action block [nsteps][n][A]: inside a launch the kernel
+// moves it on from control step to control step (kernel_of acts), between launches this loop does -- whether or not the outputs are blocks (block_advance).
+static int rollout_common(usim_handle* h, DevIO io, int flags, long long first_step, int nsteps, int block_advance, void* stream) {
     const int kmax = multi_step(h->map) ? h->steps_per_launch : 1;
     for (int k = 0; k < nsteps;) {
         int kk = nsteps - k < kmax ? nsteps - k : kmax;
         if (kk > BANK_DEPTH - (int)h->steps_since_refill) kk = BANK_DEPTH - (int)h->steps_since_refill;
         io.nsub = kk; io.block = block_advance ? 1 : 0;
         h->steps_since_refill += kk - 1;                      // (step_common counts the launch as one step)
-        rc = step_common(h, io, LF_AUTO_RESET | LF_RANDOM_ACT, (long long)(first_step + k), stream);
+        const int rc = step_common(h, io, flags, first_step + k, stream);
         if (rc) return rc;
         k += kk;
         if (block_advance) advance_rollout_block(io, (size_t)h->n * kk, h->adim);
+        if (io.act) io.act += (size_t)h->n * kk * h->adim;
     }
     return USIM_OK;
+}
+
+int usim_rollout_random(usim_handle* h, int64_t first_step, int nsteps, const usim_step_io* s, int block_advance, void* stream) {
+    if (!h || nsteps < 0) return USIM_ERR_INVALID;
+    DeviceGuard guard(h->device);
+    DevIO io; int rc = fill_io(s, io, false);
+    if (rc) return rc;
+    io.act = nullptr;
+    return rollout_common(h, io, LF_AUTO_RESET | LF_RANDOM_ACT, (long long)first_step, nsteps, block_advance, stream);
+}
+
+int usim_rollout_actions(usim_handle* h, int nsteps, const usim_step_io* s, int block_advance, void* stream) {
+    if (!h || nsteps < 0) return USIM_ERR_INVALID;
+    DevIO io; int rc = fill_io(s, io, true);                  // (io->act_dev required; nothing is enqueued on a refusal)
+    if (rc) return rc;
+    if (nsteps == 0) return USIM_OK;
+    DeviceGuard guard(h->device);
+    io.act_out = nullptr;                                     // nothing is drawn: the block's own action entry, if any, is not written
+    return rollout_common(h, io, LF_AUTO_RESET, 0, nsteps, block_advance, stream);
 }
 
 int usim_time_steps(usim_handle* h, int64_t first_step, int nsteps, const usim_step_io* s, int block_advance, void* stream, float* elapsed_ms) {

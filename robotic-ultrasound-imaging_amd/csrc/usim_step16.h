@@ -1257,7 +1257,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 // One launch = io.nsub consecutive steps (usim_rollout_random: the actions are drawn in-kernel, so step k + 1 needs nothing from the host).
 // The lattice tables stay in LDS, launch latency and the kernel-argument / first-load round trip are paid once; every step still reads its
 // state from HBM and writes it back together with its slice of the transition block, so the algorithmic traffic per step is unchanged.
-template <int TORSO, int MODE, int ROLE, int NT, bool MULTI = false, int G = 16, class WR = NoWarm>
+template <int TORSO, int MODE, int ROLE, int NT, bool MULTI = false, int G = 16, class WR = NoWarm, bool ACTS = false>
 DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __restrict__ st, const int n, const int npad, const DevIO& io0, const int flags, const long long rstep) {
     // (MULTI is a template parameter: the single-step instantiation -- usim_step, a policy in the loop -- keeps the register allocation of a
     // straight-line kernel; the loop costs it 2 us per step)
@@ -1284,6 +1284,10 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
             __threadfence_block();
             if constexpr (ROLE != 0) USIM_BAR();
             if (io0.block && ctrl_done) advance_rollout_block(io, (size_t)n, C.adim);
+            // usim_rollout_actions (ACTS): the next control step plays the next slice of the caller's action block [nsub][n][A], whether or not the outputs move --
+            // a scalar add on a kernel argument, the same in both roles.  Instantiations of their own (usim_step16_acts_kernel, usim_step32_acts_kernel): in
+            // the kernels of usim_rollout_random the add costs the single-wave soft-torso ones 6 - 8 more spilled VGPRs (profiles/rollout_actions/resource_usage.txt)
+            if constexpr (ACTS) { if (ctrl_done) io.act += (size_t)n * C.adim; }
         }
     }
 #if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
@@ -1296,6 +1300,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
                                                                                                           const DevIO io, int flags, long long rstep) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     step16_body<TORSO, MODE, 0, 256, MULTI, 16, typename std::conditional<WARM, WarmOf<16>::type, NoWarm>::type>(lds, M, C, st, n, npad, io, flags, rstep);
+}
+
+// the multi-step launch of usim_rollout_actions: step k of the launch reads slice k of io.act (step16_body ACTS); otherwise usim_step16_kernel<TORSO, OCC, 0, true, WARM>
+template <int TORSO, int OCC, bool WARM = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void usim_step16_acts_kernel(const DevModel M, const DevCfg C, float* __restrict__ st, int n, int npad,
+                                                                                                               const DevIO io, int flags, long long rstep) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    step16_body<TORSO, 0, 0, 256, true, 16, typename std::conditional<WARM, WarmOf<16>::type, NoWarm>::type, true>(lds, M, C, st, n, npad, io, flags, rstep);
 }
 
 // soft-torso step with two waves per quad of environments: waves 0-3 of the workgroup run the arm side, waves 4-7 the lattice / contact side
@@ -1320,6 +1332,19 @@ __global__ __launch_bounds__(128 * wpr<G>()) __attribute__((amdgpu_waves_per_eu(
     typedef typename std::conditional<WARM, typename WarmOf<G>::type, NoWarm>::type WR;
     if (threadIdx.x < NT / 2) step16_body<1, 0, 1, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
     else step16_body<1, 0, 2, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
+}
+
+// the multi-step launch of usim_rollout_actions with the split kernel: usim_step32_kernel<true, G, WARM> whose two roles move io.act on between control steps (step16_body
+// ACTS: no barrier, no branch that differs between the roles -- the BARRIER INVARIANT above holds as it does there)
+template <int G = 16, bool WARM = false>
+__global__ __launch_bounds__(128 * wpr<G>()) __attribute__((amdgpu_waves_per_eu(2, 2))) void usim_step32_acts_kernel(const DevModel* __restrict__ Mp, const DevCfg* __restrict__ Cp, float* __restrict__ st, int n, int npad,
+                                                                                                                       const DevIO io, int flags, long long rstep) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const DevModel& M = *Mp; const DevCfg& C = *Cp;
+    constexpr int NT = 128 * wpr<G>();
+    typedef typename std::conditional<WARM, typename WarmOf<G>::type, NoWarm>::type WR;
+    if (threadIdx.x < NT / 2) step16_body<1, 0, 1, NT, true, G, WR, true>(lds, M, C, st, n, npad, io, flags, rstep);
+    else step16_body<1, 0, 2, NT, true, G, WR, true>(lds, M, C, st, n, npad, io, flags, rstep);
 }
 
 }  // namespace usim

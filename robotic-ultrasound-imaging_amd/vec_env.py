@@ -271,6 +271,55 @@ class UltrasoundVecEnv:
             io = self._io if block is None else self._block_io(block)
         self._check(self.lib.usim_rollout_random(self._handle, int(first_step), int(nsteps), C.byref(io), int(advance), self._stream()))
 
+    def rollout_actions(self, actions, block=None, io=None):
+        """Enqueue T steps that play the caller's actions: `actions` is a contiguous float32 tensor [T, n, A] on this device and step k plays actions[k] (anything
+        else raises ValueError before the library is called).  The same bits as T step_tensor(actions[k]) calls -- outputs and state --, in the multi-step launches
+        of rollout_random (include/usim.h usim_rollout_actions).  With `block` (or its prepared `io`), step k writes slice k of the [T, n, ...] tensors; the
+        block's own "act" entry, if any, is not written; a block of fewer than T steps raises ValueError.  A prepared `io` (block_io) is taken as it is: its blocks
+        must hold T steps, nothing here can check that.  Without either, every step writes the env's own buffers (the results of the last step remain).  Auto-reset
+        is on.  The launches go to the current stream and read `actions` there: the caching allocator keeps its memory in that stream's order, no reference is held."""
+        a = actions
+        want = (self.num_envs, self.action_dim)
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.device != self.device or a.dim() != 3 or tuple(a.shape[1:]) != want or not a.is_contiguous():
+            what = f"{tuple(a.shape)} {a.dtype} on {a.device}, contiguous {a.is_contiguous()}" if isinstance(a, torch.Tensor) else type(a).__name__
+            raise ValueError(f"actions must be a contiguous float32 tensor [T, {want[0]}, {want[1]}] on {self.device}, got {what}")
+        T = int(a.shape[0])
+        if T == 0:
+            return
+        if block is not None and any(int(block[k].shape[0]) < T for k in ("obs", "rew", "done")):
+            raise ValueError(f"block holds fewer than {T} steps")
+        advance = block is not None or io is not None
+        if io is None:
+            io = self._io if block is None else self._block_io(block)
+        keep = io.act_dev
+        io.act_dev = a.data_ptr()
+        try:
+            self._check(self.lib.usim_rollout_actions(self._handle, T, C.byref(io), int(advance), self._stream()))
+        finally:
+            io.act_dev = keep
+
+    def score_block(self, rew, done=None, gamma=1.0, out=None):
+        """Score a rollout block in one launch (include/usim.h usim_score_block): for every environment the discounted return of its first episode inside the block
+        -- sum of gamma^k rew[k] up to and including its first done -- and that episode's length in steps (T where it did not end).  `rew` / `done`: contiguous
+        [T, n] device tensors, float32 / uint8; or a block dict (alloc_block) as the only positional argument.  `out`: a (float32 [n], int32 [n]) pair of device
+        tensors to write into.  Returns (returns, lengths).  What the rew * alive loop of a shooting planner computes; bit for bit at gamma = 1."""
+        if isinstance(rew, dict):
+            if done is not None:
+                raise ValueError("score_block(block, gamma=...) or score_block(rew, done, gamma=...)")
+            rew, done = rew["rew"], rew["done"]
+        ok = lambda t, dt: isinstance(t, torch.Tensor) and t.dtype == dt and t.device == self.device and t.dim() == 2 and t.is_contiguous()
+        if not ok(rew, torch.float32) or not ok(done, torch.uint8) or rew.shape != done.shape or rew.shape[0] < 1 or rew.shape[1] < 1:
+            raise ValueError(f"rew / done must be contiguous [T, n] tensors on {self.device}, float32 / uint8, of one shape")
+        T, n = int(rew.shape[0]), int(rew.shape[1])
+        if out is None:
+            out = (torch.empty(n, dtype=torch.float32, device=self.device), torch.empty(n, dtype=torch.int32, device=self.device))
+        ret, length = out
+        for t, dt in ((ret, torch.float32), (length, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or tuple(t.shape) != (n,) or not t.is_contiguous():
+                raise ValueError(f"out must be (float32 [{n}], int32 [{n}]) contiguous tensors on {self.device}")
+        self._check(self.lib.usim_score_block(rew.data_ptr(), done.data_ptr(), T, n, float(gamma), ret.data_ptr(), length.data_ptr(), self._stream()))
+        return ret, length
+
     def time_steps(self, first_step, nsteps, block=None):
         """Same as rollout_random but bracketed by HIP events on the current stream; returns elapsed ms."""
         ms = C.c_float(0)

@@ -87,7 +87,7 @@ typedef struct usim_config {
                                                 * kernel, arm side and lattice / contact side in two waves that share a SIMD; automatic up to 4096 envs); 64 (soft torso: the
                                                 * same with 8-lane groups, 32 environments per workgroup; automatic beyond 4096 envs).  Rigid torso: 0 or 16; soft torso: 0, 16,
                                                 * 32 or 64; full torso: 0, 16, 32 or 64, ignored (one wave per environment); anything else is USIM_ERR_INVALID.  The table of
-                                                * mappings and of the kernels they run: resolve_mapping in csrc/usim_api.hip */
+                                                * mappings: resolve_mapping in csrc/usim_setup.h; of the kernels they run: the launch table of csrc/usim_api.hip */
     int32_t torso_shape;                       /* use_box_torso (rl_config.yaml:57): 0 box (soft_box.xml), 1 cylinder (soft_human_torso.xml) */
     int32_t waves_per_simd;                    /* soft torso, 16-lane step kernel: register budget for 1 or 2 waves per SIMD; 0 auto (1 up to 4096 envs, 2 beyond).  Nonzero with
                                                 * lanes_per_env 0: lanes_per_env 16.  Rigid and full torso: 0, 1 or 2, ignored */

@@ -17,6 +17,7 @@ POLICY_PACKED = 2 * 128 * 256      # USIM_POLICY_PACKED
 RESET_PARAMS = 13
 LOG_WIDTH = 53
 WARM_WORDS = 8 + 16 * 4            # USIM_WARM_WORDS
+FULL_BODY_WORDS = 13 + 4 * 270 + 8 + 64      # USIM_FULL_BODY_WORDS: the free body (13), then the warm start of the full torso's contact solve
 PACK_HEAD_WORDS = 21               # USIM_PACK_HEAD_WORDS: obs[19], rew, done
 PACK_EPISODE_WORDS = 23            # USIM_PACK_EPISODE_WORDS: env index, ep_length, ep_return, status, terminal_observation[19]
 

@@ -1,5 +1,5 @@
 // usim_device.h -- data layout shared by the HIP kernels (usim_kernels.hip) and the host side of the C ABI
-// (usim_api.hip).  gfx950 only.
+// (usim_api.hip, usim_setup.h).  gfx950 only.
 //
 // HBM layout: one float32 block per handle (ints as bit patterns), n_pad = n rounded up to the workgroup
 // width.  The per-environment state is environment-major: 40 scalar words per environment (scalar_index()), then -- soft torso --
@@ -7,6 +7,7 @@
 // (soft torso) with 16-byte accesses off a single address.  The reset bank behind the state is environment-major as well.
 #pragma once
 #include <stdint.h>
+#include <hip/hip_vector_types.h>      // int2 (DevIO::items); types only
 
 namespace usim {
 
@@ -45,6 +46,32 @@ constexpr int A16_LANES = 16;
 enum ArmTable : int { AT_RFIX = 0 /* 9: columns x, y, z of the fixed rotation */, AT_LPOS = 9 /* 3 */, AT_LCOM = 12 /* 3 */, AT_MASS = 15,
                       AT_INERTIA = 16 /* 6: xx xy xz yy yz zz about the COM, link frame */, AT_QMIN = 22, AT_QMAX = 23, AT_TAUMAX = 24,
                       AT_INITQ = 25, AT_JOINT = 26 /* 1: the lane owns a joint, 0: padding / site / idle lane */, AT_ARMATURE = 27 /* rotor inertia on the joint's diagonal entry of the mass matrix */, AT_STRIDE = 28 };
+
+// lattice tables, laid out exactly as their workgroup-resident LDS copy.  One device buffer per handle (DevModel::tables, built and
+// uploaded by usim_create): handles with different torso shapes can live side by side on one GPU
+constexpr int LROW = 100;                             // row stride of the lattice inverse (pad word zero)
+constexpr int TB_LINV = 0;                            // float [99][100]
+constexpr int TB_POS = N_TOP * LROW;                  // float [99][3] nominal surface point rel. torso centre (padded to 300)
+constexpr int TB_AXIS = TB_POS + 300;                 // float [99][3] slide axis
+constexpr int TB_SHELL = TB_AXIS + 300;               // int   [99]    shell id (contact-pair index convention)
+constexpr int TB_WORDS = TB_SHELL + 100;              // 10600 words (the lattice topology itself is implicit: 9 x 11 grid stencil)
+constexpr int TB_ARM = TB_WORDS;                      // behind the lattice block (not copied to LDS): the arm table of the 16-lane step kernel
+constexpr int TB_TOTAL = TB_ARM + A16_LANES * AT_STRIDE;
+
+// full torso (usim_full.h)
+constexpr int NSH = 270;                      // shell elements (soft_box.xml:9 count="9 4 11")
+constexpr int FE = 5;                         // elements per lane: element e = FE * lane + i  (64 * 5 = 320 >= 270; elements >= 270 do not exist: mass-less, zero everywhere)
+constexpr int FNE = 64 * FE;
+// table block of a full-torso handle (DevModel::tables), words
+constexpr int FT_POS = 0;                     // float [270][3] element surface point, body frame
+constexpr int FT_AXIS = 816;                  // float [270][3] slide axis (radial)
+constexpr int FT_NBR = 1632;                  // int   [320][4] shell neighbours (FNE - 1 = a word that is always zero: no neighbour)
+constexpr int FT_P = 2912;                    // float [270][3] P = L^-1 N'
+constexpr int FT_DIAG = 3728;                 // float [320]    diagonal of L (1 for elements that do not exist)
+constexpr int FT_CONST = 4048;                // float [32]     S^-1 (9), I_b^-1 (9), M_tot, contact regulariser scale of an element-table contact
+constexpr int FT_LINV = 4080;                 // float [270][272] L^-1
+constexpr int FT_LROW = 272;
+constexpr int FT_WORDS = FT_LINV + NSH * FT_LROW;
 
 // model constants (host-built in fp64, narrowed once; passed to the kernels by value -> kernarg/SGPRs)
 struct DevModel {

@@ -22,20 +22,8 @@
 #pragma once
 // (included by usim_kernels.hip inside namespace usim, after probe_sdf / group_sync, cone_local of usim_contact.h and usim_episode.h)
 
-constexpr int NSH = 270;                      // shell elements (soft_box.xml:9 count="9 4 11")
-constexpr int FE = 5;                         // elements per lane: element e = FE * lane + i  (64 * 5 = 320 >= 270; elements >= 270 do not exist: mass-less, zero everywhere)
-constexpr int FNE = 64 * FE;
+// (NSH, FE, FNE and the layout FT_* of a full-torso handle's table block: usim_device.h -- the host writes it)
 constexpr int FULL_CG_ITERS = 20;
-// table block of a full-torso handle (DevModel::tables), words
-constexpr int FT_POS = 0;                     // float [270][3] element surface point, body frame
-constexpr int FT_AXIS = 816;                  // float [270][3] slide axis (radial)
-constexpr int FT_NBR = 1632;                  // int   [320][4] shell neighbours (FNE - 1 = a word that is always zero: no neighbour)
-constexpr int FT_P = 2912;                    // float [270][3] P = L^-1 N'
-constexpr int FT_DIAG = 3728;                 // float [320]    diagonal of L (1 for elements that do not exist)
-constexpr int FT_CONST = 4048;                // float [32]     S^-1 (9), I_b^-1 (9), M_tot, contact regulariser scale of an element-table contact
-constexpr int FT_LINV = 4080;                 // float [270][272] L^-1
-constexpr int FT_LROW = 272;
-constexpr int FT_WORDS = FT_LINV + NSH * FT_LROW;
 // state of the lattice region (environment-major, LATF_ENV_WORDS words per environment)
 constexpr int LATF_S = 0, LATF_SD = 272, LATF_BODY = 544;     // s[270], sdot[270], body: position (3, base-centred world axes), quaternion w x y z, linear velocity (world), angular velocity (body frame)
 // warm start of the contact solve (the forces of the previous physics step: element-table contacts by element, probe contacts by element and geom):
@@ -586,7 +574,7 @@ DI void full_forward(float* lds, const int lane, const DevModel& M, const DevCfg
 //         for the (env, episode) items of the refill work list (written to the reset bank: bank_park).
 // full_item is the body of one environment / work item: a sequence of the phases below.  The arm mathematics is the serial chain of usim_devmath.h, replicated in the lanes.
 // ======================================================================================================================================================================
-constexpr int FULL_NT = 64, FULL_EPB = 1, FULL_LDS_WORDS = FL_WORDS;     // threads and environments per workgroup, dynamic LDS words (kernel_of, usim_api.hip)
+constexpr int FULL_NT = 64, FULL_EPB = 1, FULL_LDS_WORDS = FL_WORDS;     // threads and environments per workgroup, dynamic LDS words (full_row, usim_api.hip)
 
 // site Jacobian J = [Jv; Jw]
 DI void site_jacobian(const Kin& K, float (&J)[6][NJ]) {

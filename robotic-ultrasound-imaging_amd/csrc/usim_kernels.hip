@@ -37,16 +37,7 @@
 
 namespace usim {
 
-// lattice tables, laid out exactly as their workgroup-resident LDS copy.  One device buffer per handle (DevModel::tables, built and
-// uploaded by usim_create): handles with different torso shapes can live side by side on one GPU
-constexpr int LROW = 100;                             // row stride of the lattice inverse (pad word zero)
-constexpr int TB_LINV = 0;                            // float [99][100]
-constexpr int TB_POS = N_TOP * LROW;                  // float [99][3] nominal surface point rel. torso centre (padded to 300)
-constexpr int TB_AXIS = TB_POS + 300;                 // float [99][3] slide axis
-constexpr int TB_SHELL = TB_AXIS + 300;               // int   [99]    shell id (contact-pair index convention)
-constexpr int TB_WORDS = TB_SHELL + 100;              // 10600 words (the lattice topology itself is implicit: 9 x 11 grid stencil)
-constexpr int TB_ARM = TB_WORDS;                      // behind the lattice block (not copied to LDS): the arm table of the 16-lane step kernel
-constexpr int TB_TOTAL = TB_ARM + A16_LANES * AT_STRIDE;
+// (the lattice tables' layout, LROW and TB_*: usim_device.h -- the host writes them)
 
 // per-environment LDS block (word offsets); GE_X must stay 16-byte aligned
 constexpr int GE_X = 0;                               // rhs[100] of the lattice solve

@@ -187,7 +187,7 @@ class UltrasoundVecEnv:
     def set_mapping(self, lanes_per_env, waves_per_simd=0):
         """Switch a live soft-torso env between the split kernel (lanes_per_env 32: 16-lane groups, 64: 8-lane groups) and the single-wave 16-lane kernel (waves_per_simd
         0 / 1 / 2).  The mappings compute the same bits; the choice only matters for speed (include/usim.h usim_set_mapping; the table of mappings:
-        resolve_mapping in csrc/usim_api.hip)."""
+        resolve_mapping in csrc/usim_setup.h, the kernels they launch: kernel_of in csrc/usim_api.hip)."""
         self._check(self.lib.usim_set_mapping(self._handle, int(lanes_per_env), int(waves_per_simd)))
 
     def random_actions_tensor(self, step, out=None):
@@ -500,7 +500,7 @@ class UltrasoundVecEnv:
         st["s"] = lat[:, : self.num_elements, 0].copy()
         st["sd"] = lat[:, : self.num_elements, 1].copy()
         if self.num_elements == 270:                                  # full torso: the free body (position world, quaternion w x y z, velocity world, angular velocity body frame)
-            body = np.zeros((self.num_envs, 13 + 4 * 270 + 8 + 64), dtype=np.float64)             # USIM_FULL_BODY_WORDS
+            body = np.zeros((self.num_envs, _lib.FULL_BODY_WORDS), dtype=np.float64)
             self._check(self.lib.usim_get_body_state(self._handle, body.ctypes.data))
             st["body"] = body[:, :13].copy()
             st["solver_warm_start"] = body[:, 13:].copy()                                          # the contact forces of the previous physics step (the solve's initial guess)

@@ -40,7 +40,7 @@ def _add_body(m_a, c_a, I_a, m_b, c_b, I_b):
 
 
 def panda_chain():
-    """Panda + hand + ultrasound probe (the model of usim_api.hip build_model / usim_devmath.h): 7 links, link 7 carries the composite of
+    """Panda + hand + ultrasound probe (the model of usim_setup.h build_model / usim_devmath.h): 7 links, link 7 carries the composite of
     link7 + hand + probe.  Returns dict with per-link arrays and the end-effector constants in the link-7 frame."""
     lpos = np.array([[0, 0, 0.333], [0, 0, 0], [0, -0.316, 0], [0.0825, 0, 0], [-0.0825, 0.384, 0], [0, 0, 0], [0.088, 0, 0]], dtype=float)
     rotx = [0, -1, 1, 1, -1, 1, 1]

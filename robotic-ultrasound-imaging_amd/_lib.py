@@ -14,6 +14,8 @@ OBS_DIM = 19
 MAXC = 8
 NSCALAR = 40
 POLICY_PACKED = 2 * 128 * 256      # USIM_POLICY_PACKED
+POLICY_SCRATCH = 1280              # USIM_POLICY_SCRATCH
+POLICY_FUSED_ROW = 48              # doubles per row of usim_policy_fused.work_dev (one row of partial sums per 32 environments)
 RESET_PARAMS = 13
 LOG_WIDTH = 53
 WARM_WORDS = 8 + 16 * 4            # USIM_WARM_WORDS
@@ -25,6 +27,16 @@ PACK_EPISODE_WORDS = 23            # USIM_PACK_EPISODE_WORDS: env index, ep_leng
 def pack_words(n):
     """USIM_PACK_WORDS(n): 32-bit words of the block usim_pack_step fills for n environments"""
     return 4 + int(n) * (PACK_HEAD_WORDS + PACK_EPISODE_WORDS)
+
+
+def policy_fused_rows(n):
+    """USIM_POLICY_FUSED_ROWS(n)"""
+    return (int(n) + 31) // 32
+
+
+def policy_fused_work(n):
+    """USIM_POLICY_FUSED_WORK(n): doubles of usim_policy_fused.work_dev -- the rows, then two 32-bit arrival flags per row and a status word"""
+    return policy_fused_rows(n) * (POLICY_FUSED_ROW + 1) + 2
 
 
 MODE = {"tracking": 0, "fixed": 1, "variable_z": 2, "wrench": 3}

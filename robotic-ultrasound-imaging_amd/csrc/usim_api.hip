@@ -2,6 +2,7 @@
 //
 // Owns the SoA state block in HBM and enqueues the kernels of usim_kernels.hip (and of usim_full.h, usim_step16.h, which it includes) on the caller's HIP stream.
 // What usim_create decides before it touches the device -- the model constants in double precision, the DevCfg translation, the mapping -- is usim_setup.h.
+// The entry points that take no handle are translation units of their own: usim_policy.hip (usim_policy_*), usim_pack.hip, usim_score.hip.
 // No torch types, no exceptions across the boundary.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -10,13 +11,12 @@
 #include <string>
 #include <vector>
 #include <new>
-#include <atomic>
 
 #include "../../include/usim.h"
 #include "usim_device.h"
 #include "usim_robot.h"
 #include "usim_setup.h"          // what usim_create decides before it touches the device: Mapping, check_config, build_model, translate_config
-#include "usim_kernels.hip"      // single translation unit: kernels + host launcher (no relocatable device code)
+#include "usim_kernels.hip"      // the step, reset, bank and snapshot kernels share this translation unit with their host launcher (no relocatable device code)
 #include "usim_snapshot.h"       // usim_save_envs / usim_load_envs (behind the step kernels)
 
 
@@ -647,5 +647,3 @@ const char* usim_last_hip_error(const usim_handle* h) { return h ? h->hip_err.c_
 const char* usim_version(void) { return "usim 0.5 (gfx950) src " USIM_SRC_HASH; }
 
 }  // extern "C"
-
-#include "usim_policy.hip"

@@ -1,4 +1,5 @@
-// usim_kernels.hip -- CDNA4 (gfx950) device code of the batched Ultrasound simulator; the translation unit is usim_api.hip, which includes it.
+// usim_kernels.hip -- CDNA4 (gfx950) device code of the batched Ultrasound simulator's step kernels; their translation unit is usim_api.hip, which includes it
+// (the policy, pack and score kernels are translation units of their own: usim_policy.hip, usim_pack.hip, usim_score.hip).
 //
 // This file holds
 //   - the LDS layout and the group primitives (group_sync, group_bcast) of the soft torso's top face, its lattice phases (lattice_rhs, lattice_solve) and its collision

@@ -1,6 +1,6 @@
 // usim_policy.hip -- the CALLER's side of env.step() on the device: SB3's VecNormalize + MlpPolicy forward + action sampling + rollout-buffer
 // writes + GAE as four kernels per rollout step (src/rl.py:140 VecNormalize, :143 PPO("MlpPolicy"), :157 / :177-184
-// checkpoints).  Included by usim_api.hip (single translation unit).
+// checkpoints).  A translation unit of its own: it takes no usim_handle and shares nothing with the step kernels but usim_devmath.h (DI, philox, u4, PI_F).
 //
 // Why: with a policy in the loop a rollout step in PyTorch is ~100 launches of a few microseconds (float64 running statistics, two 3-layer MLPs,
 // sampling, clipping, buffer copies) around a 15 us simulator kernel -- 300 us per step even when replayed as a graph.  Here:
@@ -18,7 +18,14 @@
 // The weights are read from the caller's tensors (torch parameters: an optimiser step is seen by the next call); nothing is copied.
 // Numerics: same formulas as policy.DeviceVecNormalize / MlpActorCritic; sums are ordered differently from PyTorch's kernels, so results agree to
 // rounding (tests/test_gpu_policy_replay.py: 1e-5 on means / values / log-probs, 1e-12 relative on the float64 statistics), not bit for bit.
-#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <atomic>
+
+#include "../../include/usim.h"
+#include "usim_devmath.h"
+
+using namespace usim;
 
 namespace usim {
 
@@ -39,6 +46,16 @@ struct NormStats {                                       // policy.DeviceVecNorm
 
 DI double ld_agent(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 DI void st_agent(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// RunningMeanStd.update_from_moments: merges a batch of n samples (sum x, sum x^2) into a running mean / variance over `count` samples (parallel-variance
+// update); returns the new count.  (-ffp-contract=on fuses per statement: the statements are part of the result)
+DI double merge_moments(double& mean, double& var, double count, double sum, double sum_sq, int n) {
+    const double bm = sum / n, bv = fmax(sum_sq / n - bm * bm, 0.0);
+    const double tot = count + n, delta = bm - mean;
+    const double m2 = var * count + bv * n + delta * delta * count * n / tot;
+    mean += delta * n / tot; var = m2 / tot;
+    return tot;
+}
 
 // RunningMeanStd.update(obs).  PL_SB workgroups read their slice of the [n][19] batch once, coalesced (thread t takes words t, t + 128, ...: the
 // channel of a word is its index mod 19, and since 128 * 19 words form a block, slot j of a thread always holds channel (first + t + 128 j) mod 19 --
@@ -92,10 +109,7 @@ DI void obs_stats_body(ObsStatsLds& L, const float* __restrict__ obs, int n, con
         double a = 0.0, b = 0.0;
 #pragma unroll
         for (int k = 0; k < PL_SB; ++k) { a += pp[k].x; b += pp[k].y; }
-        const double bm = a / n, bv = fmax(b / n - bm * bm, 0.0);
-        const double cnt = *S.obs_count, tot = cnt + n, delta = bm - S.obs_mean[t];
-        const double m2 = S.obs_var[t] * cnt + bv * n + delta * delta * cnt * n / tot;
-        S.obs_mean[t] += delta * n / tot; S.obs_var[t] = m2 / tot;
+        merge_moments(S.obs_mean[t], S.obs_var[t], *S.obs_count, a, b, n);
     }
     __syncthreads();
     if (t == 0) { *S.obs_count += n; *arrived = 0u; }
@@ -310,10 +324,7 @@ __global__ __launch_bounds__(256, 2) void usim_policy_act_kernel(PolicyNet P, No
                 double a = 0.0, b = 0.0;
 #pragma unroll
                 for (int g = 0; g < PL_SG; ++g) { a += FT.tab[0][g][tid]; b += FT.tab[1][g][tid]; }
-                const double bm = a / n, bv = fmax(b / n - bm * bm, 0.0);
-                const double tot = ocnt + n, delta = bm - om;
-                const double m2 = ov * ocnt + bv * n + delta * delta * ocnt * n / tot;
-                om += delta * n / tot; ov = m2 / tot;
+                const double tot = merge_moments(om, ov, ocnt, a, b, n);
                 if (writer && stats_ok) { S.obs_mean[tid] = om; S.obs_var[tid] = ov; if (tid == 0) *S.obs_count = tot; }
             }
             FL.mean[tid] = om; FL.var[tid] = ov; FL.inv[tid] = 1.0 / sqrt(ov + S.epsilon);
@@ -322,10 +333,7 @@ __global__ __launch_bounds__(256, 2) void usim_policy_act_kernel(PolicyNet P, No
             if (F.have_prev) {
                 const double a = (FT.red[0][0] + FT.red[0][1]) + (FT.red[0][2] + FT.red[0][3]), b = (FT.red[1][0] + FT.red[1][1]) + (FT.red[1][2] + FT.red[1][3]),
                              c = (FT.red[2][0] + FT.red[2][1]) + (FT.red[2][2] + FT.red[2][3]);
-                const double bm = b / n, bv = fmax(c / n - bm * bm, 0.0);
-                const double tot = rcnt + n, delta = bm - rmean;
-                const double m2 = rvar * rcnt + bv * n + delta * delta * rcnt * n / tot;
-                rmean += delta * n / tot; rvar = m2 / tot; rcnt = tot;
+                rcnt = merge_moments(rmean, rvar, rcnt, b, c, n);
                 if (writer && stats_ok) { *S.ret_mean = rmean; *S.ret_var = rvar; *S.ret_count = rcnt; if (F.raw_sum) *F.raw_sum += a; }
             }
             FL.scale = 1.0 / sqrt(rvar + S.epsilon);
@@ -502,12 +510,7 @@ DI void reward_body(RewardLds& L, const float* __restrict__ rew, const uint8_t* 
         double a = 0.0, b = 0.0, c = 0.0;
         for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { a += red[0][i]; b += red[1][i]; c += red[2][i]; }
         if (raw_sum) *raw_sum += a;
-        if (training) {
-            const double bm = b / n, bv = fmax(c / n - bm * bm, 0.0);
-            const double cnt = *S.ret_count, tot = cnt + n, delta = bm - *S.ret_mean;
-            const double m2 = *S.ret_var * cnt + bv * n + delta * delta * cnt * n / tot;
-            *S.ret_mean += delta * n / tot; *S.ret_var = m2 / tot; *S.ret_count = tot;
-        }
+        if (training) *S.ret_count = merge_moments(*S.ret_mean, *S.ret_var, *S.ret_count, b, c, n);
         scale = 1.0 / sqrt(*S.ret_var + S.epsilon);
     }
     __syncthreads();
@@ -557,6 +560,16 @@ static NormStats norm_stats(const usim_norm_stats& s) { return {s.obs_mean, s.ob
 static bool step_args_ok(const usim_policy_net* net, const usim_norm_stats* st, const float* obs_dev, int n, int act_dim, const float* lo, const float* hi, const usim_policy_out* out) {
     return net && st && obs_dev && out && out->act_env_dev && n > 0 && act_dim >= 1 && act_dim <= 7 && lo && hi && net->w2_packed;
 }
+// the policy launch of usim_policy_step (FUSED = false, F unused) and usim_policy_step_fused
+template <bool FUSED>
+static int launch_act(const usim_policy_net* net, const usim_norm_stats* st, const FusedArgs& F, const float* obs_dev, const uint8_t* prev_done_dev, int n, int act_dim,
+                      const float* act_low_dev, const float* act_high_dev, uint64_t seed, uint32_t counter, const uint32_t* counter_base_dev, int env_offset,
+                      int deterministic, const usim_policy_out* out, void* stream) {
+    hipLaunchKernelGGL(usim_policy_act_kernel<FUSED>, dim3((n + PL_TM - 1) / PL_TM, 2), dim3(256), 0, (hipStream_t)stream, policy_net(*net), norm_stats(*st), obs_dev, prev_done_dev, n,
+                       act_dim, act_low_dev, act_high_dev, (uint32_t)seed, (uint32_t)(seed >> 32), counter, counter_base_dev, env_offset, deterministic, out->nobs_dev, out->act_dev,
+                       out->act_env_dev, out->value_dev, out->logp_dev, out->episode_start_dev, F);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
 
 }  // namespace usim
 
@@ -571,26 +584,19 @@ int usim_policy_pack(const usim_policy_net* net, float* packed_dev, void* stream
 int usim_policy_step(const usim_policy_net* net, const usim_norm_stats* st, const float* obs_dev, const uint8_t* prev_done_dev, int n, int act_dim,
                      const float* act_low_dev, const float* act_high_dev, uint64_t seed, uint32_t counter, const uint32_t* counter_base_dev, int env_offset,
                      int training, int deterministic, const usim_policy_out* out, void* stream) {
-    using namespace usim;
     if (!step_args_ok(net, st, obs_dev, n, act_dim, act_low_dev, act_high_dev, out)) return USIM_ERR_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    const PolicyNet P = policy_net(*net);
-    const NormStats S = norm_stats(*st);
     if (training == 1) {
         if (!st->scratch) return USIM_ERR_INVALID;
         // scratch: PL_SB x 19 x 2 partial sums, then the arrival counter (zero on entry, left zero)
-        hipLaunchKernelGGL(usim_policy_obs_stats_kernel, dim3(PL_SB), dim3(PL_ST), 0, s, obs_dev, n, S, st->scratch, reinterpret_cast<unsigned int*>(st->scratch + PL_SB * PL_OBS * 2));
+        hipLaunchKernelGGL(usim_policy_obs_stats_kernel, dim3(PL_SB), dim3(PL_ST), 0, (hipStream_t)stream, obs_dev, n, norm_stats(*st), st->scratch,
+                           reinterpret_cast<unsigned int*>(st->scratch + PL_SB * PL_OBS * 2));
     }
-    hipLaunchKernelGGL(usim_policy_act_kernel<false>, dim3((n + PL_TM - 1) / PL_TM, 2), dim3(256), 0, s, P, S, obs_dev, prev_done_dev, n,
-                       act_dim, act_low_dev, act_high_dev, (uint32_t)seed, (uint32_t)(seed >> 32), counter, counter_base_dev, env_offset, deterministic, out->nobs_dev, out->act_dev,
-                       out->act_env_dev, out->value_dev, out->logp_dev, out->episode_start_dev, FusedArgs{});
-    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+    return launch_act<false>(net, st, FusedArgs{}, obs_dev, prev_done_dev, n, act_dim, act_low_dev, act_high_dev, seed, counter, counter_base_dev, env_offset, deterministic, out, stream);
 }
 
 int usim_policy_step_fused(const usim_policy_net* net, const usim_norm_stats* st, const usim_policy_fused* f, const float* obs_dev, const uint8_t* prev_done_dev, int n,
                            int act_dim, const float* act_low_dev, const float* act_high_dev, uint64_t seed, uint32_t counter, const uint32_t* counter_base_dev,
                            int env_offset, int deterministic, const usim_policy_out* out, void* stream) {
-    using namespace usim;
     if (!f || !step_args_ok(net, st, obs_dev, n, act_dim, act_low_dev, act_high_dev, out)) return USIM_ERR_INVALID;
     if (!f->work_dev || (f->have_prev && (!f->rew_prev_dev || !f->done_prev_dev || !f->nrew_prev_dev))) return USIM_ERR_INVALID;
     if (n > USIM_POLICY_FUSED_MAX_ENVS) return USIM_ERR_UNSUPPORTED;          // every workgroup must be resident (see the kernel)
@@ -610,18 +616,12 @@ int usim_policy_step_fused(const usim_policy_net* net, const usim_norm_stats* st
         }
         if (2 * ((n + PL_TM - 1) / PL_TM) > cap) return USIM_ERR_UNSUPPORTED;
     }
-    const PolicyNet P = policy_net(*net);
-    const NormStats S = norm_stats(*st);
-    FusedArgs F{f->rew_prev_dev, f->done_prev_dev, f->nrew_prev_dev, f->raw_sum_dev, f->work_dev, f->update_obs, f->have_prev, f->norm_reward};
-    hipLaunchKernelGGL(usim_policy_act_kernel<true>, dim3((n + PL_TM - 1) / PL_TM, 2), dim3(256), 0, (hipStream_t)stream, P, S, obs_dev, prev_done_dev, n,
-                       act_dim, act_low_dev, act_high_dev, (uint32_t)seed, (uint32_t)(seed >> 32), counter, counter_base_dev, env_offset, deterministic, out->nobs_dev, out->act_dev,
-                       out->act_env_dev, out->value_dev, out->logp_dev, out->episode_start_dev, F);
-    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+    const FusedArgs F{f->rew_prev_dev, f->done_prev_dev, f->nrew_prev_dev, f->raw_sum_dev, f->work_dev, f->update_obs, f->have_prev, f->norm_reward};
+    return launch_act<true>(net, st, F, obs_dev, prev_done_dev, n, act_dim, act_low_dev, act_high_dev, seed, counter, counter_base_dev, env_offset, deterministic, out, stream);
 }
 
 int usim_policy_reward(const usim_norm_stats* st, const float* rew_dev, const uint8_t* done_dev, int n, int training, int norm_reward, float* nrew_dev,
                        double* raw_sum_dev, const float* next_obs_dev, void* stream) {
-    using namespace usim;
     if (!st || !rew_dev || !done_dev || !nrew_dev || n <= 0) return USIM_ERR_INVALID;
     const NormStats S = norm_stats(*st);
     if (next_obs_dev && training) {
@@ -635,7 +635,6 @@ int usim_policy_reward(const usim_norm_stats* st, const float* rew_dev, const ui
 
 int usim_policy_gae(const float* rewards_dev, const float* values_dev, const float* episode_starts_dev, const float* last_values_dev, const uint8_t* last_done_dev,
                     int T, int n, float gamma, float gae_lambda, float* advantages_dev, float* returns_dev, void* stream) {
-    using namespace usim;
     if (!rewards_dev || !values_dev || !episode_starts_dev || !last_values_dev || !last_done_dev || !advantages_dev || !returns_dev || T <= 0 || n <= 0) return USIM_ERR_INVALID;
     hipLaunchKernelGGL(usim_policy_gae_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, rewards_dev, values_dev, episode_starts_dev, last_values_dev,
                        last_done_dev, T, n, gamma, gae_lambda, advantages_dev, returns_dev);

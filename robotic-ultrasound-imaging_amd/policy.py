@@ -9,6 +9,7 @@ torch.load(weights_only=True), the pickle with a restricted unpickler that maps 
 (sys.modules is never touched).  save_sb3_zip / save_vecnormalize_pkl write the same formats (the model.save / env.save step at the
 end of src/rl.py's training branch, :157-158)."""
 import ctypes as C
+import functools
 import io
 import json
 import pickle
@@ -16,6 +17,8 @@ import zipfile
 
 import numpy as np
 import torch
+
+from . import _lib
 
 # the four classes a VecNormalize pickle of stable-baselines3 refers to (besides numpy's array reconstructors)
 _SB3_CLASSES = (("gym.spaces.box", "Box"), ("gym.spaces.space", "Space"),
@@ -336,12 +339,15 @@ class DeviceRolloutBuffer:
     def reset(self):
         self.pos, self.full = 0, False
 
+    def write(self, t, obs, action, reward, episode_start, value, log_prob):
+        """the six slices of step t (no bookkeeping: a recorded rollout writes the same slices at every replay)"""
+        self.observations[t].copy_(obs); self.actions[t].copy_(action); self.rewards[t].copy_(reward)
+        self.episode_starts[t].copy_(episode_start.to(torch.float32)); self.values[t].copy_(value); self.log_probs[t].copy_(log_prob)
+
     def add(self, obs, action, reward, episode_start, value, log_prob):
         if self.pos >= self.buffer_size:
             raise RuntimeError("rollout buffer is full")
-        t = self.pos
-        self.observations[t].copy_(obs); self.actions[t].copy_(action); self.rewards[t].copy_(reward)
-        self.episode_starts[t].copy_(episode_start.to(torch.float32)); self.values[t].copy_(value); self.log_probs[t].copy_(log_prob)
+        self.write(self.pos, obs, action, reward, episode_start, value, log_prob)
         self.pos += 1
         self.full = self.pos == self.buffer_size
 
@@ -373,6 +379,52 @@ class DeviceRolloutBuffer:
 
 
 @torch.no_grad()
+def _rollout_step(env, policy, vecnorm, low, high, obs, episode_start, generator=None, store=None, raw_reward_sum=None):
+    """One step of the rollout loop, for collect_rollouts and GraphedCollector alike: normalise the observation, sample, clip the action to the box
+    for the env, step, normalise the reward; store(normalised obs, unclipped action, normalised reward, episode_start, value, log-prob) where a store is
+    given.  Returns (next raw obs, next episode_start, done flags of this step); the first two are copies: the env rewrites its buffers."""
+    nobs = vecnorm.normalize_obs(obs)
+    act, value, logp = policy.sample(nobs, generator)
+    obs, rew, done = env.step_tensor(torch.max(torch.min(act, high), low))
+    if raw_reward_sum is not None:
+        raw_reward_sum.add_(rew.sum())
+    nrew = vecnorm.normalize_reward(rew, done)
+    if store is not None:
+        store(nobs, act, nrew, episode_start, value, logp)
+    return obs.clone(), done.bool().clone(), done
+
+
+@torch.no_grad()
+def _bootstrap_value(policy, vecnorm, obs):
+    """SB3 bootstraps with the value of the stored, already normalised `_last_obs`: the statistics are not updated a second time"""
+    was_training, vecnorm.training = vecnorm.training, False
+    try:
+        return policy.forward(vecnorm.normalize_obs(obs))[1]
+    finally:
+        vecnorm.training = was_training
+
+
+def _capture(env, record, prologue=None, generator=None):
+    """record() as a HIP graph (torch.cuda.CUDAGraph), captured on a side stream.  Library handles, lazy initialisation and the allocator's warm-up must
+    happen outside the capture: `prologue` runs eagerly on the side stream first.  The reset bank is refilled before the capture (env.refill_bank)."""
+    dev = env.device
+    graph = torch.cuda.CUDAGraph()
+    if generator is not None:
+        graph.register_generator_state(generator)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        if prologue is not None:
+            prologue()
+        env.refill_bank()
+        torch.cuda.current_stream(dev).synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            record()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    return graph
+
+
+@torch.no_grad()
 def collect_rollouts(env, policy, vecnorm, buffer, obs=None, episode_start=None, generator=None):
     """OnPolicyAlgorithm.collect_rollouts for one buffer: sample actions from the policy on normalised observations, clip them to
     the action box for the env, store the unclipped sample, normalise rewards, bootstrap with the value of the last observation.
@@ -387,20 +439,8 @@ def collect_rollouts(env, policy, vecnorm, buffer, obs=None, episode_start=None,
     buffer.reset()
     done = episode_start
     for _ in range(buffer.buffer_size):
-        nobs = vecnorm.normalize_obs(obs)
-        act, value, logp = policy.sample(nobs, generator)
-        obs, rew, done = env.step_tensor(torch.max(torch.min(act, high), low))
-        nrew = vecnorm.normalize_reward(rew, done)
-        buffer.add(nobs, act, nrew, episode_start, value, logp)
-        episode_start = done.bool().clone()
-        obs = obs.clone()
-    # SB3 bootstraps with the value of the stored, already normalised `_last_obs`: the statistics are not updated a second time
-    was_training, vecnorm.training = vecnorm.training, False
-    try:
-        _, last_value = policy.forward(vecnorm.normalize_obs(obs))
-    finally:
-        vecnorm.training = was_training
-    buffer.compute_returns_and_advantage(last_value, done.bool())
+        obs, episode_start, done = _rollout_step(env, policy, vecnorm, low, high, obs, episode_start, generator, buffer.add)
+    buffer.compute_returns_and_advantage(_bootstrap_value(policy, vecnorm, obs), done.bool())
     return obs, episode_start
 
 
@@ -428,54 +468,30 @@ class GraphedCollector:
         self.episode_start = torch.ones(env.num_envs, dtype=torch.bool, device=dev)
         self.last_done = torch.zeros(env.num_envs, dtype=torch.bool, device=dev)
         self.raw_reward_sum = torch.zeros((), dtype=torch.float64, device=dev)  # sum of the raw rewards of the last rollout (diagnostics)
-        self.graph = torch.cuda.CUDAGraph()
-        if generator is not None:
-            self.graph.register_generator_state(generator)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            # library handles, lazy initialisation and the allocator's warm-up happen outside the capture: a few eager steps on the side stream.
-            # They are real steps (the statistics and the environments advance), exactly like the first steps of an eager collect_rollouts.
+        def warm_up():
+            # a few eager steps: real ones (the statistics and the environments advance), exactly like the first steps of an eager collect_rollouts
             obs, start = self.obs, self.episode_start
             for _ in range(warmup_steps):
                 obs, start, _ = self._step(obs, start, None)
             self.obs.copy_(obs); self.episode_start.copy_(start)
-            env.refill_bank()
-            torch.cuda.current_stream(dev).synchronize()
-            with torch.cuda.graph(self.graph, stream=side):
-                self._record()
-        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = _capture(env, self._record, warm_up, generator)
         buffer.pos, buffer.full = buffer.buffer_size, True
 
-    @torch.no_grad()
     def _step(self, obs, episode_start, t):
-        vn, env = self.vecnorm, self.env
-        nobs = vn.normalize_obs(obs)
-        act, value, logp = self.policy.sample(nobs, self.generator)
-        o, rew, done = env.step_tensor(torch.max(torch.min(act, self._high), self._low))
-        if t is not None:
-            self.raw_reward_sum.add_(rew.sum())
-        nrew = vn.normalize_reward(rew, done)
-        if t is not None:
-            b = self.buffer
-            b.observations[t].copy_(nobs); b.actions[t].copy_(act); b.rewards[t].copy_(nrew)
-            b.episode_starts[t].copy_(episode_start.to(torch.float32)); b.values[t].copy_(value); b.log_probs[t].copy_(logp)
-        return o.clone(), done.bool().clone(), done
+        """_rollout_step; with t, into the buffer slices of step t and the reward sum"""
+        store, raw_sum = (None, None) if t is None else (functools.partial(self.buffer.write, t), self.raw_reward_sum)
+        return _rollout_step(self.env, self.policy, self.vecnorm, self._low, self._high, obs, episode_start, self.generator, store, raw_sum)
 
     @torch.no_grad()
     def _record(self):
-        vn, b = self.vecnorm, self.buffer
+        b = self.buffer
         obs, start = self.obs, self.episode_start
         self.env.refill_bank()                 # first node of the recorded sequence as well as the last: a replay does not depend on what ran before it
         self.raw_reward_sum.zero_()
         done = None
         for t in range(b.buffer_size):
             obs, start, done = self._step(obs, start, t)
-        was_training, vn.training = vn.training, False
-        try:
-            _, last_value = self.policy.forward(vn.normalize_obs(obs))
-        finally:
-            vn.training = was_training
+        last_value = _bootstrap_value(self.policy, self.vecnorm, obs)
         self.last_done.copy_(done.bool())
         b.compute_returns_and_advantage(last_value, self.last_done)
         self.obs.copy_(obs); self.episode_start.copy_(start)
@@ -498,7 +514,6 @@ class FusedRollout:
     Gaussian noise comes from the library's counter-based stream (seed, environment, step), not from a torch generator."""
 
     def __init__(self, env, policy, vecnorm, buffer, seed=0, graph=True, fused_stats=None, init_stats=True):
-        from . import _lib
         # fused_stats: VecNormalize's two updates inside the policy launch (usim_policy_step_fused: two launches per step instead of three).  Its workgroups wait
         # for one another, so all of them must be resident: by default only up to 4096 environments (256 workgroups, half of what the device holds -- room
         # for a collective's kernels beside them); fused_stats=True asks for it up to the library's limit of 8192 (a device to itself)
@@ -523,7 +538,7 @@ class FusedRollout:
         self._w2_packed = torch.zeros(_lib.POLICY_PACKED, dtype=torch.float32, device=dev)
         self._net.w2_packed = self._w2_packed.data_ptr()
         vn = vecnorm
-        self._scratch = torch.zeros(1280, dtype=torch.float64, device=dev)                  # USIM_POLICY_SCRATCH (include/usim.h)
+        self._scratch = torch.zeros(_lib.POLICY_SCRATCH, dtype=torch.float64, device=dev)
         self._stats = _lib.UsimNormStats(ptr(vn.obs_mean), ptr(vn.obs_var), ptr(vn._obs_count), ptr(vn.ret_mean), ptr(vn.ret_var), ptr(vn._ret_count), ptr(vn.returns),
                                          ptr(self._scratch), float(vn.clip_obs), float(vn.clip_reward), float(vn.gamma), float(vn.epsilon))
         self._low = torch.as_tensor(env.action_space.low, dtype=torch.float32, device=dev).contiguous()
@@ -533,50 +548,43 @@ class FusedRollout:
         self.raw_reward_sum = torch.zeros((), dtype=torch.float64, device=dev)
         self.counter = 0                                                                    # rollouts collected
         self._ctr = torch.zeros(1, dtype=torch.int32, device=dev)                           # device part of the noise counter: advanced by every rollout
-        self._rows = (env.num_envs + 31) // 32
-        self._work = torch.zeros(self._rows * 49 + 2, dtype=torch.float64, device=dev)                    # USIM_POLICY_FUSED_WORK(n)
+        self._work = torch.zeros(_lib.policy_fused_work(env.num_envs), dtype=torch.float64, device=dev)
         self.obs = env.reset_tensor()                                                       # the env's own observation buffer: rewritten by every step
         self._prev_done = env._done                                                         # ... and its done flags: read by the policy kernel BEFORE the next step rewrites them
         self._prev_done.fill_(1)                                                            # every environment starts an episode
         if vecnorm.training and init_stats:                                                 # VecNormalize.reset(): the statistics see the reset observation (init_stats=False: the caller's first act(training=1) does)
             self.act(self.obs, self._prev_done, counter=0, training=1, deterministic=True)
-        self.graph = None
-        if graph:
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                env.refill_bank()
-                torch.cuda.current_stream(dev).synchronize()
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, stream=side):
-                    self._record()
-            torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = _capture(env, self._record) if graph else None
 
     def _check(self, rc):
-        from . import _lib
         _lib.check(self.lib, rc, None)
 
     def pack(self):
         """usim_policy_pack: the layer-2 weights as they are now, in operand order (a launch of 64 workgroups)"""
         self._check(self.lib.usim_policy_pack(C.byref(self._net), self._w2_packed.data_ptr(), self.env._stream()))
 
+    def _out(self, t):
+        """usim_policy_out: the env's action; with t, the buffer slices of step t; without, only the value (into a tensor of its own)"""
+        b = self.buffer
+        if t is None:
+            return _lib.UsimPolicyOut(self._act_env.data_ptr(), None, None, self._value.data_ptr(), None, None)
+        return _lib.UsimPolicyOut(self._act_env.data_ptr(), b.observations[t].data_ptr(), b.actions[t].data_ptr(), b.values[t].data_ptr(), b.log_probs[t].data_ptr(),
+                                  b.episode_starts[t].data_ptr())
+
     def act(self, obs, prev_done, counter, training=None, deterministic=False, t=None, pack=True):
         """usim_policy_step on raw observations [n, 19]: returns (clipped action for the env, value); with t, the buffer slices of step t are written"""
-        from . import _lib
         env, b = self.env, self.buffer
         if pack:
             self.pack()
         training = self.vecnorm.training if training is None else training
         ptr = lambda x: None if x is None else x.data_ptr()
-        out = _lib.UsimPolicyOut(ptr(self._act_env), None if t is None else ptr(b.observations[t]), None if t is None else ptr(b.actions[t]),
-                                 ptr(self._value) if t is None else ptr(b.values[t]), None if t is None else ptr(b.log_probs[t]), None if t is None else ptr(b.episode_starts[t]))
+        out = self._out(t)
         self._check(self.lib.usim_policy_step(C.byref(self._net), C.byref(self._stats), ptr(obs), ptr(prev_done), env.num_envs, env.action_dim, ptr(self._low), ptr(self._high),
                                               self.seed, int(counter) & 0xffffffff, ptr(self._ctr), int(env.env_offset), int(training),
                                               int(bool(deterministic)), C.byref(out), env._stream()))
         return self._act_env, (self._value if t is None else b.values[t])
 
     def _fused(self, t, rewards_out):
-        from . import _lib
         env, vn = self.env, self.vecnorm
         prev = t > 0
         return _lib.UsimPolicyFused(self._work.data_ptr(), env._rew.data_ptr() if prev else None, env._done.data_ptr() if prev else None,
@@ -585,14 +593,11 @@ class FusedRollout:
     def act_fused(self, obs, prev_done, counter, rewards_out=None, deterministic=False, t=None, pack=True):
         """usim_policy_step_fused: as act(), with RunningMeanStd.update(obs) and the reward side of the step before (normalised into rewards_out) in the same
         launch when counter > 0"""
-        from . import _lib
-        env, b = self.env, self.buffer
+        env = self.env
         if pack:
             self.pack()
         ptr = lambda x: None if x is None else x.data_ptr()
-        out = _lib.UsimPolicyOut(ptr(self._act_env), None if t is None else ptr(b.observations[t]), None if t is None else ptr(b.actions[t]),
-                                 ptr(self._value) if t is None else ptr(b.values[t]), None if t is None else ptr(b.log_probs[t]), None if t is None else ptr(b.episode_starts[t]))
-        f = self._fused(counter, rewards_out)
+        out, f = self._out(t), self._fused(counter, rewards_out)
         self._check(self.lib.usim_policy_step_fused(C.byref(self._net), C.byref(self._stats), C.byref(f), ptr(obs), ptr(prev_done), env.num_envs, env.action_dim,
                                                     ptr(self._low), ptr(self._high), self.seed, int(counter) & 0xffffffff, ptr(self._ctr),
                                                     int(env.env_offset), int(bool(deterministic)), C.byref(out), env._stream()))
@@ -600,43 +605,35 @@ class FusedRollout:
     @property
     def wait_ran_out(self):
         """True if a workgroup of usim_policy_step_fused ever gave up waiting for the others' partial sums (the device was shared; statistics are then wrong)"""
-        return bool(self._work[self._rows * 48:].view(torch.int32)[2 * self._rows].item())
-
-    def _record_fused(self):
-        """one rollout with two launches per step: policy (+ the statistics of the observation it reads + the reward side of the step before), env"""
-        env, b = self.env, self.buffer
-        T, n = b.buffer_size, env.num_envs
-        env.refill_bank()                      # first node of the recorded sequence as well: a replay is valid whatever ran on the env since the last one
-        self.raw_reward_sum.zero_()
-        self.pack()                            # the weights of this rollout (they do not change inside it)
-        for t in range(T):
-            self.act_fused(self.obs, self._prev_done, counter=t, rewards_out=b.rewards[t - 1] if t else None, t=t, pack=False)
-            env.step_tensor(self._act_env)
-        self.act_fused(self.obs, self._prev_done, counter=T, rewards_out=b.rewards[T - 1], deterministic=True, pack=False)      # bootstrap value + the last step's reward side
-        self._check(self.lib.usim_policy_gae(b.rewards.data_ptr(), b.values.data_ptr(), b.episode_starts.data_ptr(), self._value.data_ptr(), self._prev_done.data_ptr(),
-                                             T, n, b.gamma, b.gae_lambda, b.advantages.data_ptr(), b.returns.data_ptr(), env._stream()))
-        self._ctr.add_(T + 1)
-        env.refill_bank()
+        rows = _lib.policy_fused_rows(self.env.num_envs)
+        flags = self._work[rows * _lib.POLICY_FUSED_ROW:].view(torch.int32)                 # two arrival flags per row, then the status word
+        return bool(flags[2 * rows].item())
 
     def _record(self):
-        """one rollout: T x (policy, env, reward) + bootstrap value + GAE.  The noise of step t is keyed on (seed, environment, t + device counter); the
-        recorded sequence advances the device counter by T + 1 at its end, so a replay draws fresh noise"""
-        if self.fused_stats:
-            return self._record_fused()
+        """one rollout: T x (policy, env[, reward]) + bootstrap value + GAE.  The noise of step t is keyed on (seed, environment, t + device counter); the
+        recorded sequence advances the device counter by T + 1 at its end, so a replay draws fresh noise.
+        fused_stats: two launches per step -- the policy launch also takes the statistics of the observation it reads and the reward side of the step before.
+        Otherwise three, and the observation statistics follow VecNormalize's timing: RunningMeanStd.update(obs) when the environment RETURNS the observation
+        (reset: once, in __init__; step: in the launch that also does the reward side), so the policy kernel only normalises (training = 2) and the bootstrap
+        value sees statistics that include the last observation, as SB3's `_last_obs` does."""
         env, b, vn = self.env, self.buffer, self.vecnorm
         T, n = b.buffer_size, env.num_envs
-        env.refill_bank()                      # first node of the recorded sequence as well (usim.h: "the sequence starts and ends with it")
+        env.refill_bank()                      # first node of the recorded sequence as well as the last: a replay is valid whatever ran on the env since the last one
         self.raw_reward_sum.zero_()
-        # The observation statistics follow VecNormalize's timing: RunningMeanStd.update(obs) when the environment RETURNS the observation (reset: once, in
-        # __init__; step: in the launch that also does the reward side), so the policy kernel only normalises (training = 2) and the bootstrap value sees
-        # statistics that include the last observation, as SB3's `_last_obs` does.
         self.pack()                            # the weights of this rollout (they do not change inside it)
         for t in range(T):
-            self.act(self.obs, self._prev_done, counter=t, training=2 if vn.training else 0, t=t, pack=False)
-            o, rew, done = env.step_tensor(self._act_env)
-            self._check(self.lib.usim_policy_reward(C.byref(self._stats), rew.data_ptr(), done.data_ptr(), n, int(bool(vn.training)), int(bool(vn.norm_reward)),
-                                                    b.rewards[t].data_ptr(), self.raw_reward_sum.data_ptr(), o.data_ptr() if vn.training else None, env._stream()))
-        self.act(self.obs, self._prev_done, counter=T, training=0, deterministic=True, pack=False)
+            if self.fused_stats:
+                self.act_fused(self.obs, self._prev_done, counter=t, rewards_out=b.rewards[t - 1] if t else None, t=t, pack=False)
+                env.step_tensor(self._act_env)
+            else:
+                self.act(self.obs, self._prev_done, counter=t, training=2 if vn.training else 0, t=t, pack=False)
+                o, rew, done = env.step_tensor(self._act_env)
+                self._check(self.lib.usim_policy_reward(C.byref(self._stats), rew.data_ptr(), done.data_ptr(), n, int(bool(vn.training)), int(bool(vn.norm_reward)),
+                                                        b.rewards[t].data_ptr(), self.raw_reward_sum.data_ptr(), o.data_ptr() if vn.training else None, env._stream()))
+        if self.fused_stats:                   # bootstrap value (+ the last step's reward side)
+            self.act_fused(self.obs, self._prev_done, counter=T, rewards_out=b.rewards[T - 1], deterministic=True, pack=False)
+        else:
+            self.act(self.obs, self._prev_done, counter=T, training=0, deterministic=True, pack=False)
         self._check(self.lib.usim_policy_gae(b.rewards.data_ptr(), b.values.data_ptr(), b.episode_starts.data_ptr(), self._value.data_ptr(), self._prev_done.data_ptr(),
                                              T, n, b.gamma, b.gae_lambda, b.advantages.data_ptr(), b.returns.data_ptr(), env._stream()))
         self._ctr.add_(T + 1)

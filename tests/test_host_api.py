@@ -38,7 +38,7 @@ def test_struct_layouts_match_header(usim):
            'offsetof(usim_config, seed), offsetof(usim_config, control_dt), offsetof(usim_config, probe_height));'
            'printf("%zu %zu %zu %zu %zu %zu %zu %d ", sizeof(usim_policy_net), sizeof(usim_norm_stats), offsetof(usim_norm_stats, clip_obs), sizeof(usim_policy_out), '
            'sizeof(usim_policy_fused), offsetof(usim_policy_fused, raw_sum_dev), offsetof(usim_policy_fused, update_obs), (int)USIM_POLICY_FUSED_WORK(1000));'
-           'printf("%d\\n", (int)USIM_FULL_BODY_WORDS);return 0;}')
+           'printf("%d %d %d\\n", (int)USIM_FULL_BODY_WORDS, (int)USIM_POLICY_SCRATCH, (int)USIM_POLICY_PACKED);return 0;}')
     import tempfile
     with tempfile.TemporaryDirectory() as d:
         (Path(d) / "p.c").write_text(src)
@@ -48,7 +48,8 @@ def test_struct_layouts_match_header(usim):
     cfg, io = L.UsimConfig, L.UsimStepIO
     assert [int(v) for v in out] == [C.sizeof(cfg), C.sizeof(io), cfg.seed.offset, cfg.control_dt.offset, cfg.probe_height.offset,
                                      C.sizeof(L.UsimPolicyNet), C.sizeof(L.UsimNormStats), L.UsimNormStats.clip_obs.offset, C.sizeof(L.UsimPolicyOut),
-                                     C.sizeof(L.UsimPolicyFused), L.UsimPolicyFused.raw_sum_dev.offset, L.UsimPolicyFused.update_obs.offset, 32 * 49 + 2, L.FULL_BODY_WORDS]
+                                     C.sizeof(L.UsimPolicyFused), L.UsimPolicyFused.raw_sum_dev.offset, L.UsimPolicyFused.update_obs.offset, 32 * 49 + 2, L.FULL_BODY_WORDS, L.POLICY_SCRATCH, L.POLICY_PACKED]
+    assert L.policy_fused_work(1000) == 32 * 49 + 2
 
 
 def test_default_config_is_the_shipped_rl_config(usim, tmp_path):

@@ -345,6 +345,40 @@ int usim_pack_step(const usim_step_io* io, int n, float* packed_dev, void* strea
  * length_dev, n <= 0 or nsteps <= 0: USIM_ERR_INVALID, nothing is written. */
 int usim_score_block(const float* rew_block_dev, const uint8_t* done_block_dev, int nsteps, int n, float gamma, float* return_dev, int32_t* length_dev, void* stream);
 
+/* ---- a batched MPPI shooting planner: the sampler before usim_rollout_actions and the update after usim_score_block (csrc/usim_plan.hip; planner.py MPPIPlanner;
+ * INTEGRATION.md section 4c).  `groups` = G controlled environments, `per_group` = K candidates each, n = G K simulated environments: environments [g K, (g + 1) K)
+ * play the candidates of group g, and candidate k = 0 of every group is the unperturbed nominal.  Caller-owned float32 device buffers: the nominal mean [G][H][A]
+ * (H = horizon, A = act_dim), the candidate block cand [H][n][A] -- the layout usim_rollout_actions consumes --, the returns ret [n].  Both calls take no handle and
+ * are kernel launches on `stream` and nothing else -- no allocation, no synchronisation, no event; capture-safe like usim_score_block.  Both answer USIM_ERR_INVALID
+ * before anything is enqueued for a NULL required pointer, groups / per_group / horizon <= 0 (or G K, G H beyond INT_MAX), act_dim outside 1 .. 8, smoothing outside
+ * [0, 1), a temperature that is negative or not finite.
+ *
+ * usim_plan_sample:   cand[t][g K + k][a] = clip(m[g][t][a] + sigma[a] e[k][t][a], low[a], high[a])
+ *   m is mean_dev; a non-finite word counts as 0, as an action does in usim_step.  Where restart_dev[g] != 0 (uint8 [G], may be NULL: no restart) m is taken as 0
+ *   AND 0 IS WRITTEN INTO mean_dev[g]: an environment that has just started an episode starts from a fresh nominal.  Nothing else writes mean_dev.
+ *   e = 0 for k = 0.  For k >= 1 the noise is first-order smoothed over the horizon: e[0] = xi[0], e[t] = smoothing e[t - 1] + sqrt(1 - smoothing^2) xi[t]
+ *   (float32: fmaf(smoothing, e[t - 1], c xi[t]) with c rounded once from float64); the sample is fmaf(sigma, e, m), then the clip.
+ *   xi is N(0, 1) by the Box-Muller recipe of usim_policy_step -- one Philox4x32-10 block per pair of components, u1 = ((word 0 >> 8) + 1) / 2^24, u2 = (word 1 >> 8)
+ *   / 2^24, radius sqrt(-2 ln u1), cosine for even components and sine for odd ones, hardware log / sine / cosine -- keyed by the counter words
+ *   (g K + k, (counter + *counter_base_dev) mod 2^32, 4 t + (a >> 1), 0x504c414e "PLAN") under the key (seed low, seed high).  counter_base_dev (may be NULL) is a device
+ *   word that a recorded sequence advances between replays.  A draw depends on (seed, counter, candidate g K + k, t, a) alone -- not on G, K, H or the launch shape.
+ *
+ * usim_plan_update, per group g:
+ *   best = the candidate with the largest FINITE return, ties to the lowest index; a candidate with a non-finite return has weight 0; if no return of the group is
+ *   finite, best = 0 and the weight is 1 on candidate 0.
+ *   temperature == 0 is a SELECTION, not a product: the weight is exactly 1 on best and plan[g][t] is that candidate's words bit for bit (no clip).
+ *   temperature > 0: w_k = exp((ret_k - ret_best) / temperature) / sum_j exp((ret_j - ret_best) / temperature),  plan[g][t][a] = clip(sum_k w_k cand[t][g K + k][a], low, high).
+ *   act[g] = plan[g][0];  next_mean[g][t] = plan[g][t + 1] for t < H - 1 and next_mean[g][H - 1] = plan[g][H - 1] (the receding horizon keeps the last action).
+ *   Outputs: plan_dev [G][H][A], next_mean_dev [G][H][A], best_dev [G] int32 and weight_dev [n] may be NULL; act_dev [G][A] is required.  next_mean_dev may be the
+ *   mean_dev of the next usim_plan_sample (this call does not read the nominal); the outputs must not overlap each other or the inputs.
+ *   The result is a function of the inputs alone: float32 in a fixed order -- thread j of 256 takes candidates j, j + 256, ... ascending (s += term; acc = fmaf(w, cand,
+ *   acc)), a butterfly over lane distances 32 .. 1 inside each wave of 64, then ((w0 + w1) + w2) + w3 over the four waves; no atomics, nothing ordered by arrival.  The
+ *   result of a group does not depend on the other groups. */
+int usim_plan_sample(float* mean_dev, const float* sigma_dev, const float* act_low_dev, const float* act_high_dev, const uint8_t* restart_dev, int groups, int per_group,
+                     int horizon, int act_dim, float smoothing, uint64_t seed, uint32_t counter, const uint32_t* counter_base_dev, float* cand_dev, void* stream);
+int usim_plan_update(const float* cand_dev, const float* ret_dev, const float* act_low_dev, const float* act_high_dev, int groups, int per_group, int horizon, int act_dim,
+                     float temperature, float* plan_dev, float* next_mean_dev, float* act_dev, int32_t* best_dev, float* weight_dev, void* stream);
+
 /* ---- the caller's side of env.step() on the device: SB3 VecNormalize + MlpPolicy forward + sampling + rollout-buffer
  * writes + GAE, fused into a few kernels per rollout step (csrc/usim_policy.hip).  Everything is a device pointer into the CALLER's tensors
  * (torch parameters, policy.DeviceVecNormalize statistics, policy.DeviceRolloutBuffer slices); the library keeps no copy. ---- */

@@ -113,6 +113,10 @@ SYMBOLS = {
                                   C.c_void_p]),
     "usim_pack_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_void_p, C.c_void_p]),
     "usim_score_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_plan_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_plan_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_default_config": (C.c_int, [C.POINTER(UsimConfig)]),
     "usim_create": (C.c_int, [C.POINTER(UsimConfig), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "usim_destroy": (None, [C.c_void_p]),

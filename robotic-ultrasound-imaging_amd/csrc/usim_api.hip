@@ -2,7 +2,7 @@
 //
 // Owns the SoA state block in HBM and enqueues the kernels of usim_kernels.hip (and of usim_full.h, usim_step16.h, which it includes) on the caller's HIP stream.
 // What usim_create decides before it touches the device -- the model constants in double precision, the DevCfg translation, the mapping -- is usim_setup.h.
-// The entry points that take no handle are translation units of their own: usim_policy.hip (usim_policy_*), usim_pack.hip, usim_score.hip.
+// The entry points that take no handle are translation units of their own: usim_policy.hip (usim_policy_*), usim_pack.hip, usim_score.hip, usim_plan.hip (usim_plan_*).
 // No torch types, no exceptions across the boundary.
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -2,6 +2,7 @@
 //
 // Owns the SoA state block in HBM and enqueues the kernels of usim_kernels.hip (and of usim_full.h, usim_step16.h, which it includes) on the caller's HIP stream.
 // What usim_create decides before it touches the device -- the model constants in double precision, the DevCfg translation, the mapping -- is usim_setup.h.
+// The layout of the state block is stated once (StateLayout, usim_checkpoint.h); the checkpoint conversions over host copies of the block are that header's too.
 // The entry points that take no handle are translation units of their own: usim_policy.hip (usim_policy_*), usim_pack.hip, usim_score.hip, usim_plan.hip (usim_plan_*).
 // No torch types, no exceptions across the boundary.
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include "usim_device.h"
 #include "usim_robot.h"
 #include "usim_setup.h"          // what usim_create decides before it touches the device: Mapping, check_config, build_model, translate_config
+#include "usim_checkpoint.h"     // the layout of the state block (StateLayout) and the checkpoint conversions over host copies of it
 #include "usim_kernels.hip"      // the step, reset, bank and snapshot kernels share this translation unit with their host launcher (no relocatable device code)
 #include "usim_snapshot.h"       // usim_save_envs / usim_load_envs (behind the step kernels)
 
@@ -110,7 +112,8 @@ static const Kernel& kernel_of(Mapping m, bool warm, Launch l) { return kRows[fi
 struct usim_handle {
     usim_config cfg;
     Mapping map = Mapping::RIGID16;   // resolved by usim_create (resolve_mapping)
-    int n = 0, npad = 0, device = 0, adim = 6, n_el = 0, nfields = 0;
+    StateLayout L{};                  // the state block: environments, regions, size (usim_checkpoint.h)
+    int device = 0, adim = 6;
     DevModel M;
     DevCfg C;
     float* state = nullptr;
@@ -130,7 +133,6 @@ struct usim_handle {
     int* d_count = nullptr;           // [0] items, [1] finished workgroups of the running refill
     long long steps_since_refill = 0;
     int steps_per_launch = 256;      // usim_rollout_random: consecutive steps per launch of the 16-lane kernels (USIM_STEPS_PER_LAUNCH overrides, 1 .. MAX_STEPS_PER_LAUNCH)
-    int bank_row0 = 0;
     bool warm = false;                // warm start of the top-face contact solve: warm rows behind the reset bank, the step / reset kernels that use them (kernel_of)
     std::string hip_err;
 };
@@ -172,20 +174,19 @@ static int set_lds_limits(usim_handle* h) {
 
 // every environment's warm rows to "nothing kept" (synchronous)
 static int warm_rows_reset(usim_handle* h) {
-    std::vector<float> w((size_t)WARM_WORDS * h->npad, 0.f);
-    const int none = -1;
-    for (int i = 0; i < h->npad; ++i) for (int k = 0; k < MAXC; ++k) std::memcpy(&w[(size_t)i * WARM_WORDS + WARM_EL + k], &none, 4);
-    HIPCHK(h, hipMemcpy(h->state + warm_index(h->bank_row0, h->npad, 0), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+    std::vector<float> w((size_t)h->L.warm_words * h->L.npad);
+    empty_warm(h->L.npad, w.data());
+    HIPCHK(h, hipMemcpy(h->state + h->L.warm(0), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
     return USIM_OK;
 }
 
 static int launch(usim_handle* h, DevIO io, Launch l, int flags, long long rstep, hipStream_t s) {
-    io.bank_row0 = h->bank_row0;
+    io.bank_row0 = h->L.bank_row0;
     const Kernel& k = kernel_of(h->map, h->warm, l);
-    const dim3 grid((h->n + k.epb - 1) / k.epb), block(k.nt);
+    const dim3 grid((h->L.n + k.epb - 1) / k.epb), block(k.nt);
     const size_t lds = (size_t)k.lds_words * sizeof(float);
-    if (k.step) hipLaunchKernelGGL(k.step, grid, block, lds, s, h->M, h->C, h->state, h->n, h->npad, io, flags, rstep);
-    else hipLaunchKernelGGL(k.split, grid, block, lds, s, h->d_M, h->d_C, h->state, h->n, h->npad, io, flags, rstep);
+    if (k.step) hipLaunchKernelGGL(k.step, grid, block, lds, s, h->M, h->C, h->state, h->L.n, h->L.npad, io, flags, rstep);
+    else hipLaunchKernelGGL(k.split, grid, block, lds, s, h->d_M, h->d_C, h->state, h->L.n, h->L.npad, io, flags, rstep);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->hip_err = std::string("usim_step_kernel launch: ") + hipGetErrorString(e); return USIM_ERR_HIP; }
     return USIM_OK;
@@ -209,18 +210,19 @@ int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** ou
     usim_handle* h = new (std::nothrow) usim_handle();
     if (!h) return USIM_ERR_ALLOC;
     *out = h;                       // returned even on failure so that usim_last_hip_error can be read; caller destroys
-    h->cfg = *cfg; h->n = n_envs; h->npad = (n_envs + WG - 1) / WG * WG; h->device = device;
+    h->cfg = *cfg; h->device = device;
     DeviceGuard guard(device);
-    ModelTables model;
-    int rc = build_model(*cfg, &model);
-    if (rc != USIM_OK) return rc;
-    h->M = model.M; h->n_el = model.n_el;
-    h->C = translate_config(*cfg);
-    h->adim = h->C.adim;
     // warm start of the top-face contact solve (the rigid torso has no contact solve, the full torso is always warm: accepted, no effect).  USIM_WARM_START = 0 / 1
     // replaces the field, so that a fixed command line (bench.py) can time both; the handle's recorded configuration follows it
     if (const char* ws = std::getenv("USIM_WARM_START")) { if ((ws[0] == '0' || ws[0] == '1') && ws[1] == 0) h->cfg.warm_start = ws[0] - '0'; }
     h->warm = h->cfg.warm_start != 0 && cfg->torso == USIM_TORSO_TOP;
+    ModelTables model;
+    int rc = build_model(*cfg, &model);
+    h->L = state_layout(cfg->torso, model.n_el, n_envs, h->warm);             // the one description of the state block: allocation, checkpoints, snapshots
+    if (rc != USIM_OK) return rc;
+    h->M = model.M;
+    h->C = translate_config(*cfg);
+    h->adim = h->C.adim;
     if (const char* spl = std::getenv("USIM_STEPS_PER_LAUNCH")) { const int v = std::atoi(spl); if (v >= 1 && v <= MAX_STEPS_PER_LAUNCH) h->steps_per_launch = v; }
     rc = upload_tables(h, model.words);
     if (rc != USIM_OK) return rc;
@@ -232,14 +234,10 @@ int usim_create(const usim_config* cfg, int n_envs, int device, usim_handle** ou
         HIPCHK(h, hipMemcpy(static_cast<char*>(h->d_consts) + offC, &h->C, sizeof(DevCfg), hipMemcpyHostToDevice));
         h->d_M = static_cast<const DevModel*>(h->d_consts); h->d_C = reinterpret_cast<const DevCfg*>(static_cast<const char*>(h->d_consts) + offC);
     }
-    h->nfields = (cfg->torso == USIM_TORSO_FULL) ? F_TOTAL_FULL : (h->n_el ? F_TOTAL_TOP : F_NSCALAR);
-    h->bank_row0 = h->nfields;                                  // two reset-bank slots follow the live state rows
-    size_t bytes = (size_t)(h->nfields + BANK_ROWS) * h->npad * sizeof(float);
-    const size_t warm_bytes = h->warm ? (size_t)WARM_WORDS * h->npad * sizeof(float) : 0;      // warm rows behind the bank (usim_device.h warm_index)
-    HIPCHK(h, hipMalloc(&h->state, bytes + warm_bytes));
-    HIPCHK(h, hipMemset(h->state, 0, bytes + warm_bytes));
+    HIPCHK(h, hipMalloc(&h->state, h->L.words * sizeof(float)));                // live rows, reset bank, warm rows (StateLayout)
+    HIPCHK(h, hipMemset(h->state, 0, h->L.words * sizeof(float)));
     if (h->warm) { int rc2 = warm_rows_reset(h); if (rc2) return rc2; }
-    HIPCHK(h, hipMalloc(&h->d_items, 2 * (size_t)h->n * BANK_DEPTH * sizeof(int2)));
+    HIPCHK(h, hipMalloc(&h->d_items, 2 * (size_t)h->L.n * BANK_DEPTH * sizeof(int2)));
     HIPCHK(h, hipMalloc(&h->d_count, 2 * sizeof(int)));
     HIPCHK(h, hipMemset(h->d_count, 0, 2 * sizeof(int)));
     HIPCHK(h, hipEventCreate(&h->ev0));
@@ -269,7 +267,7 @@ void usim_destroy(usim_handle* h) {
 
 int usim_set_mapping(usim_handle* h, int lanes_per_env, int waves_per_simd) {
     if (!h || !soft_torso(h->map) || lanes_per_env == 0) return USIM_ERR_INVALID;
-    return resolve_mapping(h->cfg.torso, lanes_per_env, waves_per_simd, h->n, &h->map) ? USIM_OK : USIM_ERR_INVALID;
+    return resolve_mapping(h->cfg.torso, lanes_per_env, waves_per_simd, h->L.n, &h->map) ? USIM_OK : USIM_ERR_INVALID;
 }
 
 int usim_set_steps_per_launch(usim_handle* h, int steps) {
@@ -290,9 +288,9 @@ int usim_refill_time(usim_handle* h, double* total_ms, long long* launches) {
     return USIM_OK;
 }
 
-int usim_num_envs(const usim_handle* h) { return h ? h->n : USIM_ERR_INVALID; }
+int usim_num_envs(const usim_handle* h) { return h ? h->L.n : USIM_ERR_INVALID; }
 int usim_action_dim(const usim_handle* h) { return h ? h->adim : USIM_ERR_INVALID; }
-int usim_num_elements(const usim_handle* h) { return h ? h->n_el : USIM_ERR_INVALID; }
+int usim_num_elements(const usim_handle* h) { return h ? h->L.n_el : USIM_ERR_INVALID; }
 int usim_has_warm_start(const usim_handle* h) { return h ? (h->warm ? 1 : 0) : USIM_ERR_INVALID; }
 
 // compute every episode on the refill work list into the reset bank (grid-stride over the list, one launch)
@@ -320,8 +318,8 @@ static int bank_refill(usim_handle* h, hipStream_t s) {
 
 // order episodes +1..+BANK_DEPTH for the selected environments and compute them
 static int bank_fill(usim_handle* h, const uint8_t* mask_dev, hipStream_t s) {
-    const int total = h->n * BANK_DEPTH;
-    hipLaunchKernelGGL(usim_bank_items_kernel, dim3((total + 255) / 256), dim3(256), 0, s, h->state, h->n, mask_dev, h->d_items, h->d_count);
+    const int total = h->L.n * BANK_DEPTH;
+    hipLaunchKernelGGL(usim_bank_items_kernel, dim3((total + 255) / 256), dim3(256), 0, s, h->state, h->L.n, mask_dev, h->d_items, h->d_count);
     HIPCHK(h, hipGetLastError());
     return bank_refill(h, s);
 }
@@ -386,7 +384,7 @@ int usim_refill_bank(usim_handle* h, void* stream) {
 int usim_random_actions(usim_handle* h, int64_t step, float* act_dev, void* stream) {
     if (!h || !act_dev) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
-    hipLaunchKernelGGL(usim_random_actions_kernel, dim3((h->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->C, h->n, (long long)step, act_dev);
+    hipLaunchKernelGGL(usim_random_actions_kernel, dim3((h->L.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->C, h->L.n, (long long)step, act_dev);
     HIPCHK(h, hipGetLastError());
     return USIM_OK;
 }
@@ -398,15 +396,14 @@ int usim_random_actions(usim_handle* h, int64_t step, float* act_dev, void* stre
 static int rollout_common(usim_handle* h, DevIO io, int flags, long long first_step, int nsteps, int block_advance, void* stream) {
     const int kmax = multi_step(h->map) ? h->steps_per_launch : 1;
     for (int k = 0; k < nsteps;) {
-        int kk = nsteps - k < kmax ? nsteps - k : kmax;
-        if (kk > BANK_DEPTH - (int)h->steps_since_refill) kk = BANK_DEPTH - (int)h->steps_since_refill;
+        const int kk = launch_steps(nsteps - k, kmax, BANK_DEPTH - (int)h->steps_since_refill);
         io.nsub = kk; io.block = block_advance ? 1 : 0;
         h->steps_since_refill += kk - 1;                      // (step_common counts the launch as one step)
         const int rc = step_common(h, io, flags, first_step + k, stream);
         if (rc) return rc;
         k += kk;
-        if (block_advance) advance_rollout_block(io, (size_t)h->n * kk, h->adim);
-        if (io.act) io.act += (size_t)h->n * kk * h->adim;
+        if (block_advance) advance_rollout_block(io, (size_t)h->L.n * kk, h->adim);
+        if (io.act) io.act += (size_t)h->L.n * kk * h->adim;
     }
     return USIM_OK;
 }
@@ -443,122 +440,69 @@ int usim_time_steps(usim_handle* h, int64_t first_step, int nsteps, const usim_s
     return USIM_OK;
 }
 
-static inline size_t lat_words(const usim_handle* h) { return h->cfg.torso == USIM_TORSO_FULL ? LATF_ENV_WORDS : LAT_ENV_WORDS; }
-static inline size_t lat_s(const usim_handle* h) { return h->cfg.torso == USIM_TORSO_FULL ? LATF_S : LAT_S; }
-static inline size_t lat_sd(const usim_handle* h) { return h->cfg.torso == USIM_TORSO_FULL ? LATF_SD : LAT_SD; }
+// ---- checkpoints: synchronise, copy the block down, convert on the host (usim_checkpoint.h), copy it up.  The setters are read-modify-writes: words that a conversion
+// does not own (the padding environments, lattice words between the regions) keep what they hold.
+static int download(usim_handle* h, std::vector<float>& buf, size_t first, size_t words) {
+    buf.resize(words);
+    HIPCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipMemcpy(buf.data(), h->state + first, words * sizeof(float), hipMemcpyDeviceToHost));
+    return USIM_OK;
+}
+static int upload(usim_handle* h, const std::vector<float>& buf, size_t first) {
+    HIPCHK(h, hipMemcpy(h->state + first, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
+    return USIM_OK;
+}
 
-// full torso: per environment USIM_FULL_BODY_WORDS float64 -- pose and velocity of the free body (13: position (world), quaternion w x y z, linear velocity (world), angular
-// velocity (body frame)), then the warm start of the contact solve (LATF_WARM_WORDS: every element's table-contact force and multiplier, the probe slots' elements as numbers and
-// forces).  float64 because the device holds the position relative to the robot base in float32: base + position is exact in float64, so get -> set restores the bits.
-constexpr int FULL_BODY_WORDS = 13 + LATF_WARM_WORDS;
-static_assert(FULL_BODY_WORDS == USIM_FULL_BODY_WORDS, "include/usim.h");
-static constexpr bool probe_slot_element(int w) { return w >= 4 * NSH && w < 4 * NSH + 8; }      // warm-start word w holds the element number of a probe contact slot: an int on the device
 int usim_get_body_state(usim_handle* h, double* body) {
     if (!h || !body || h->cfg.torso != USIM_TORSO_FULL) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
-    HIPCHK(h, hipDeviceSynchronize());
-    std::vector<float> buf((size_t)LATF_ENV_WORDS * h->npad);
-    HIPCHK(h, hipMemcpy(buf.data(), h->state + (size_t)F_LAT * h->npad, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (int i = 0; i < h->n; ++i) {
-        const float* e = &buf[(size_t)i * LATF_ENV_WORDS];
-        double* o = body + (size_t)i * FULL_BODY_WORDS;
-        for (int a = 0; a < 13; ++a) o[a] = (double)e[LATF_BODY + a] + (a < 3 ? (double)h->M.base[a] : 0.0);
-        for (int w = 0; w < LATF_WARM_WORDS; ++w) {
-            if (probe_slot_element(w)) { int v; std::memcpy(&v, &e[LATF_WTAB + w], 4); o[13 + w] = (double)v; }      // element numbers of the probe slots
-            else o[13 + w] = (double)e[LATF_WTAB + w];
-        }
-    }
+    std::vector<float> lat;
+    if (int rc = download(h, lat, h->L.lattice(0), (size_t)h->L.lat_words * h->L.npad)) return rc;
+    body_words<TO_HOST>(h->L, h->M.base, lat.data(), body);
     return USIM_OK;
 }
 int usim_set_body_state(usim_handle* h, const double* body) {
     if (!h || !body || h->cfg.torso != USIM_TORSO_FULL) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
-    HIPCHK(h, hipDeviceSynchronize());
-    std::vector<float> bw(13 + LATF_WARM_WORDS);
-    for (int i = 0; i < h->n; ++i) {
-        const double* o = body + (size_t)i * FULL_BODY_WORDS;
-        for (int a = 0; a < 13; ++a) bw[a] = (float)(o[a] - (a < 3 ? (double)h->M.base[a] : 0.0));
-        for (int w = 0; w < LATF_WARM_WORDS; ++w) {
-            if (probe_slot_element(w)) { const int v = (int)o[13 + w]; std::memcpy(&bw[13 + w], &v, 4); }
-            else bw[13 + w] = (float)o[13 + w];
-        }
-        float* dst = h->state + (size_t)F_LAT * h->npad + (size_t)i * LATF_ENV_WORDS;
-        HIPCHK(h, hipMemcpy(dst + LATF_BODY, bw.data(), 13 * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy(dst + LATF_WTAB, bw.data() + 13, (size_t)LATF_WARM_WORDS * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return USIM_OK;
+    std::vector<float> lat;
+    if (int rc = download(h, lat, h->L.lattice(0), (size_t)h->L.lat_words * h->L.npad)) return rc;
+    body_words<TO_DEVICE>(h->L, h->M.base, lat.data(), body);
+    return upload(h, lat, h->L.lattice(0));
 }
 
-// soft top-face torso with usim_config.warm_start: the kept contact list of the solver, [n][USIM_WARM_WORDS] float32 (the device's warm rows with the elements as numbers)
-static_assert(WARM_WORDS == USIM_WARM_WORDS, "include/usim.h");
 int usim_get_warm_start(usim_handle* h, float* w) {
     if (!h || !w || !h->warm) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
-    HIPCHK(h, hipDeviceSynchronize());
-    HIPCHK(h, hipMemcpy(w, h->state + warm_index(h->bank_row0, h->npad, 0), (size_t)WARM_WORDS * h->n * sizeof(float), hipMemcpyDeviceToHost));
-    for (int i = 0; i < h->n; ++i) for (int k = 0; k < MAXC; ++k) {
-        float* p = &w[(size_t)i * WARM_WORDS + WARM_EL + k];
-        int v; std::memcpy(&v, p, 4); *p = (float)v;
-    }
+    std::vector<float> rows;
+    if (int rc = download(h, rows, h->L.warm(0), (size_t)h->L.warm_words * h->L.n)) return rc;
+    warm_words<TO_HOST>(h->L.n, rows.data(), w);
     return USIM_OK;
 }
 int usim_set_warm_start(usim_handle* h, const float* w) {
     if (!h || !w || !h->warm) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
     HIPCHK(h, hipDeviceSynchronize());
-    std::vector<float> buf(w, w + (size_t)WARM_WORDS * h->n);
-    for (int i = 0; i < h->n; ++i) for (int k = 0; k < MAXC; ++k) {
-        float* p = &buf[(size_t)i * WARM_WORDS + WARM_EL + k];
-        const int v = (*p >= 0.f && *p < (float)N_TOP) ? (int)*p : -1;       // (an element number the kernels can compare; anything else: empty slot)
-        std::memcpy(p, &v, 4);
-    }
-    HIPCHK(h, hipMemcpy(h->state + warm_index(h->bank_row0, h->npad, 0), buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
-    return USIM_OK;
+    std::vector<float> rows((size_t)h->L.warm_words * h->L.n);
+    warm_words<TO_DEVICE>(h->L.n, rows.data(), w);
+    return upload(h, rows, h->L.warm(0));
 }
 
-static constexpr int kIntFields[4] = {F_T, F_TOUCH, F_EPISODE, F_STATUS};       // scalar words that the device holds as ints: float numbers on the host side
 int usim_get_state(usim_handle* h, float* scalars, float* lattice) {
     if (!h || !scalars) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
-    HIPCHK(h, hipDeviceSynchronize());
-    std::vector<float> buf((size_t)h->nfields * h->npad);
-    HIPCHK(h, hipMemcpy(buf.data(), h->state, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (int i = 0; i < h->n; ++i) {
-        for (int f = 0; f < F_NSCALAR; ++f) scalars[(size_t)i * USIM_NSCALAR + f] = buf[scalar_index(f, i)];
-        for (int j = 0; j < NJ; ++j) scalars[(size_t)i * USIM_NSCALAR + F_Q + j] = buf[scalar_index(F_Q0 + j, i)] + buf[scalar_index(F_Q + j, i)];   // device holds dq = q - q0
-        for (int k = 0; k < 4; ++k) {
-            int v; std::memcpy(&v, &buf[scalar_index(kIntFields[k], i)], 4);
-            scalars[(size_t)i * USIM_NSCALAR + kIntFields[k]] = (float)v;
-        }
-        if (lattice && h->n_el)
-            for (int e = 0; e < h->n_el; ++e) {
-                lattice[((size_t)i * h->n_el + e) * 2] = buf[(size_t)F_LAT * h->npad + (size_t)i * lat_words(h) + lat_s(h) + e];
-                lattice[((size_t)i * h->n_el + e) * 2 + 1] = buf[(size_t)F_LAT * h->npad + (size_t)i * lat_words(h) + lat_sd(h) + e];
-            }
-    }
+    std::vector<float> buf;
+    if (int rc = download(h, buf, 0, h->L.live_words())) return rc;
+    state_words<TO_HOST>(h->L, buf.data(), scalars, lattice);
     return USIM_OK;
 }
 
 int usim_set_state(usim_handle* h, const float* scalars, const float* lattice) {
     if (!h || !scalars) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
-    HIPCHK(h, hipDeviceSynchronize());
-    std::vector<float> buf((size_t)h->nfields * h->npad);
-    HIPCHK(h, hipMemcpy(buf.data(), h->state, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (int i = 0; i < h->n; ++i) {
-        for (int f = 0; f < F_NSCALAR; ++f) buf[scalar_index(f, i)] = scalars[(size_t)i * USIM_NSCALAR + f];
-        for (int j = 0; j < NJ; ++j) buf[scalar_index(F_Q + j, i)] = scalars[(size_t)i * USIM_NSCALAR + F_Q + j] - scalars[(size_t)i * USIM_NSCALAR + F_Q0 + j];   // device holds dq = q - q0
-        for (int k = 0; k < 4; ++k) {
-            int v = (int)scalars[(size_t)i * USIM_NSCALAR + kIntFields[k]];
-            std::memcpy(&buf[scalar_index(kIntFields[k], i)], &v, 4);
-        }
-        if (lattice && h->n_el)
-            for (int e = 0; e < h->n_el; ++e) {
-                buf[(size_t)F_LAT * h->npad + (size_t)i * lat_words(h) + lat_s(h) + e] = lattice[((size_t)i * h->n_el + e) * 2];
-                buf[(size_t)F_LAT * h->npad + (size_t)i * lat_words(h) + lat_sd(h) + e] = lattice[((size_t)i * h->n_el + e) * 2 + 1];
-            }
-    }
-    HIPCHK(h, hipMemcpy(h->state, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
+    std::vector<float> buf;
+    if (int rc = download(h, buf, 0, h->L.live_words())) return rc;
+    state_words<TO_DEVICE>(h->L, buf.data(), scalars, lattice);
+    if (int rc = upload(h, buf, 0)) return rc;
     if (h->warm) { int rc = warm_rows_reset(h); if (rc) return rc; }          // a state set from outside starts cold (usim_set_warm_start after this call restores the list)
     // the bank is a pure function of (seed, env, episode): rebuild every ring for the restored episode counters
     HIPCHK(h, hipMemset(h->d_count, 0, 2 * sizeof(int)));
@@ -572,22 +516,18 @@ int usim_set_state(usim_handle* h, const float* scalars, const float* lattice) {
 
 // ---- snapshots: whole environments copied between the state block and a caller-owned device buffer of rows (usim_snapshot.h), one launch on the caller's stream and
 // nothing else -- no synchronisation, no event, no allocation, no host counter: capture-safe like usim_refill_bank
-static_assert(USIM_SNAPSHOT_WORDS_RIGID == F_NSCALAR && USIM_SNAPSHOT_WORDS_TOP == F_NSCALAR + LAT_ENV_WORDS && USIM_SNAPSHOT_WORDS_TOP_WARM == F_NSCALAR + LAT_ENV_WORDS + WARM_WORDS &&
-              USIM_SNAPSHOT_WORDS_FULL == F_NSCALAR + LATF_ENV_WORDS, "include/usim.h");
-static SnapLayout snap_layout(const usim_handle* h) {
-    return {h->cfg.torso == USIM_TORSO_FULL ? LATF_ENV_WORDS : (h->n_el ? LAT_ENV_WORDS : 0), h->warm ? WARM_WORDS : 0, h->bank_row0};
-}
+static SnapLayout snap_layout(const usim_handle* h) { return {h->L.lat_words, h->L.warm_words, h->L.bank_row0}; }
 static unsigned snap_grid(int rows, int lanes) { return (unsigned)(((size_t)rows * lanes + SNAP_WG - 1) / SNAP_WG); }
 
-int usim_snapshot_words(const usim_handle* h) { return h ? snap_row_words(snap_layout(h)) : USIM_ERR_INVALID; }
+int usim_snapshot_words(const usim_handle* h) { return h ? h->L.snapshot_words() : USIM_ERR_INVALID; }      // (= snap_row_words(snap_layout(h)), what the kernels move)
 
 int usim_save_envs(usim_handle* h, const int32_t* env_index_dev, int m, float* snap_dev, void* stream) {
-    if (!h || !snap_dev || m <= 0 || (reinterpret_cast<uintptr_t>(snap_dev) & 15) || (!env_index_dev && m > h->n)) return USIM_ERR_INVALID;
+    if (!h || !snap_dev || m <= 0 || (reinterpret_cast<uintptr_t>(snap_dev) & 15) || (!env_index_dev && m > h->L.n)) return USIM_ERR_INVALID;
     DeviceGuard guard(h->device);
     const SnapLayout L = snap_layout(h);
     hipStream_t s = (hipStream_t)stream;
-    if (h->map == Mapping::FULL) hipLaunchKernelGGL(usim_save_envs_kernel<64>, dim3(snap_grid(m, 64)), dim3(SNAP_WG), 0, s, h->state, h->n, h->npad, L, env_index_dev, m, snap_dev);
-    else hipLaunchKernelGGL(usim_save_envs_kernel<16>, dim3(snap_grid(m, 16)), dim3(SNAP_WG), 0, s, h->state, h->n, h->npad, L, env_index_dev, m, snap_dev);
+    if (h->map == Mapping::FULL) hipLaunchKernelGGL(usim_save_envs_kernel<64>, dim3(snap_grid(m, 64)), dim3(SNAP_WG), 0, s, h->state, h->L.n, h->L.npad, L, env_index_dev, m, snap_dev);
+    else hipLaunchKernelGGL(usim_save_envs_kernel<16>, dim3(snap_grid(m, 16)), dim3(SNAP_WG), 0, s, h->state, h->L.n, h->L.npad, L, env_index_dev, m, snap_dev);
     HIPCHK(h, hipGetLastError());
     return USIM_OK;
 }
@@ -597,8 +537,8 @@ int usim_load_envs(usim_handle* h, const float* snap_dev, int m, const int32_t* 
     DeviceGuard guard(h->device);
     const SnapLayout L = snap_layout(h);
     hipStream_t s = (hipStream_t)stream;
-    if (h->map == Mapping::FULL) hipLaunchKernelGGL(usim_load_envs_kernel<64>, dim3(snap_grid(h->n, 64)), dim3(SNAP_WG), 0, s, h->state, h->n, h->npad, L, snap_dev, m, row_of_env_dev);
-    else hipLaunchKernelGGL(usim_load_envs_kernel<16>, dim3(snap_grid(h->n, 16)), dim3(SNAP_WG), 0, s, h->state, h->n, h->npad, L, snap_dev, m, row_of_env_dev);
+    if (h->map == Mapping::FULL) hipLaunchKernelGGL(usim_load_envs_kernel<64>, dim3(snap_grid(h->L.n, 64)), dim3(SNAP_WG), 0, s, h->state, h->L.n, h->L.npad, L, snap_dev, m, row_of_env_dev);
+    else hipLaunchKernelGGL(usim_load_envs_kernel<16>, dim3(snap_grid(h->L.n, 16)), dim3(SNAP_WG), 0, s, h->state, h->L.n, h->L.npad, L, snap_dev, m, row_of_env_dev);
     HIPCHK(h, hipGetLastError());
     return USIM_OK;
 }
@@ -616,11 +556,10 @@ int usim_profile_step(usim_handle* h, const usim_step_io* s, int64_t step, uint6
     unsigned long long* d = nullptr;
     HIPCHK(h, hipMalloc(&d, 64 * sizeof(unsigned long long)));
     HIPCHK(h, hipMemset(d, 0, 64 * sizeof(unsigned long long)));
-    io.dbg = d; io.items = h->d_items; io.count = h->d_count;
+    io.dbg = d;
     // USIM_PROFILE_NSUB = k: the stamps of the LAST of k consecutive steps of one launch (multi-step kernels; never across a refill period)
-    if (const char* ns = std::getenv("USIM_PROFILE_NSUB")) { const int v = std::atoi(ns); if (v > 1 && v <= BANK_DEPTH - h->steps_since_refill) { io.nsub = v; h->steps_since_refill += v - 1; } }
-    rc = launch(h, io, step_launch(h, io), LF_AUTO_RESET | LF_RANDOM_ACT, (long long)step, nullptr);
-    if (rc == USIM_OK && ++h->steps_since_refill >= BANK_DEPTH) rc = bank_refill(h, nullptr);
+    if (const char* ns = std::getenv("USIM_PROFILE_NSUB")) { const int v = std::atoi(ns); if (v > 1 && launch_steps(v, MAX_STEPS_PER_LAUNCH, BANK_DEPTH - (int)h->steps_since_refill) == v) { io.nsub = v; h->steps_since_refill += v - 1; } }
+    rc = step_common(h, io, LF_AUTO_RESET | LF_RANDOM_ACT, (long long)step, nullptr);
     HIPCHK(h, hipDeviceSynchronize());
     unsigned long long host[64];
     HIPCHK(h, hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost));

@@ -72,6 +72,15 @@ constexpr int FT_CONST = 4048;                // float [32]     S^-1 (9), I_b^-1
 constexpr int FT_LINV = 4080;                 // float [270][272] L^-1
 constexpr int FT_LROW = 272;
 constexpr int FT_WORDS = FT_LINV + NSH * FT_LROW;
+// state of the lattice region of a full-torso handle (environment-major, LATF_ENV_WORDS words per environment)
+constexpr int LATF_S = 0, LATF_SD = 272, LATF_BODY = 544;     // s[270], sdot[270], body: position (3, base-centred world axes), quaternion w x y z, linear velocity (world), angular velocity (body frame)
+// warm start of the contact solve (the forces of the previous physics step: element-table contacts by element, probe contacts by element and geom):
+constexpr int LATF_WTAB = 560;                // float [270][4] force (normal, t1, t2) and friction multiplier of the element's table contact; zeros: none
+constexpr int LATF_WPROBE = LATF_WTAB + 4 * NSH;   // int [8] elements of the probe contact slots (-1: empty), then float [16][4]: contacts A of slots 0-7, contacts B
+constexpr int LATF_WARM_WORDS = 4 * NSH + 8 + 64;
+constexpr int LATF_ENV_WORDS = LATF_WPROBE + 8 + 64;      // 1712
+static_assert(LATF_ENV_WORDS % 4 == 0 && LATF_WTAB % 4 == 0 && (LATF_WPROBE + 8) % 4 == 0, "16-byte accesses");
+constexpr int F_TOTAL_FULL = F_NSCALAR + LATF_ENV_WORDS;
 
 // model constants (host-built in fp64, narrowed once; passed to the kernels by value -> kernarg/SGPRs)
 struct DevModel {

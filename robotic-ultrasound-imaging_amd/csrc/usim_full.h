@@ -22,17 +22,8 @@
 #pragma once
 // (included by usim_kernels.hip inside namespace usim, after probe_sdf / group_sync, cone_local of usim_contact.h and usim_episode.h)
 
-// (NSH, FE, FNE and the layout FT_* of a full-torso handle's table block: usim_device.h -- the host writes it)
+// (NSH, FE, FNE, the layout FT_* of a full-torso handle's table block and the layout LATF_* of an environment's lattice block: usim_device.h -- the host reads and writes them)
 constexpr int FULL_CG_ITERS = 20;
-// state of the lattice region (environment-major, LATF_ENV_WORDS words per environment)
-constexpr int LATF_S = 0, LATF_SD = 272, LATF_BODY = 544;     // s[270], sdot[270], body: position (3, base-centred world axes), quaternion w x y z, linear velocity (world), angular velocity (body frame)
-// warm start of the contact solve (the forces of the previous physics step: element-table contacts by element, probe contacts by element and geom):
-constexpr int LATF_WTAB = 560;                // float [270][4] force (normal, t1, t2) and friction multiplier of the element's table contact; zeros: none
-constexpr int LATF_WPROBE = LATF_WTAB + 4 * NSH;   // int [8] elements of the probe contact slots (-1: empty), then float [16][4]: contacts A of slots 0-7, contacts B
-constexpr int LATF_WARM_WORDS = 4 * NSH + 8 + 64;
-constexpr int LATF_ENV_WORDS = LATF_WPROBE + 8 + 64;      // 1712
-static_assert(LATF_ENV_WORDS % 4 == 0 && LATF_WTAB % 4 == 0 && (LATF_WPROBE + 8) % 4 == 0, "16-byte accesses");
-constexpr int F_TOTAL_FULL = F_NSCALAR + LATF_ENV_WORDS;
 // contacts
 constexpr int FMAXT = 120;                    // element-table contacts kept (ascending element id; ~54 - 63 while the box rests; beyond: status bit 1)
 constexpr int FREC = 44;                      // probe contact record (slots 0-7 contacts A, 8-15 their coincident contacts B; slot s is built by lane s): a[3][3] b[3][3] c[3] R[3] res0[3] B[6] mu e f[3] lam P[e]

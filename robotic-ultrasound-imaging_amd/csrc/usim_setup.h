@@ -42,6 +42,16 @@ inline bool resolve_mapping(int torso, int lanes_per_env, int waves_per_simd, in
 }
 constexpr bool soft_torso(Mapping m) { return m != Mapping::FULL && m != Mapping::RIGID16; }
 constexpr bool multi_step(Mapping m) { return m != Mapping::FULL; }           // several control steps per launch (usim_rollout_random)
+// control steps of the next launch of a rollout: what remains, at most kmax (the handle's steps per launch; 1 without multi_step), and never across the refill
+// period of the reset bank, of which period_left steps remain (an environment consumes at most one ring slot per step)
+constexpr int launch_steps(int remaining, int kmax, int period_left) {
+    const int k = remaining < kmax ? remaining : kmax;
+    return k < period_left ? k : period_left;
+}
+static_assert(launch_steps(1000, 256, 1) == 1, "a period with one step left");
+static_assert(launch_steps(1000, 256, BANK_DEPTH) == 256 && launch_steps(1000, 64, BANK_DEPTH) == 64, "a period just refilled");
+static_assert(launch_steps(1000, 1, BANK_DEPTH) == 1 && launch_steps(1000, 1, 1) == 1, "kmax = 1: one step per launch");
+static_assert(launch_steps(3, 256, 200) == 3 && launch_steps(1, 256, BANK_DEPTH) == 1, "remaining smaller than everything");
 
 // the defaults of usim_default_config (the caller has checked struct_size: nothing is written to a struct of another layout)
 inline void default_config(usim_config* c) {

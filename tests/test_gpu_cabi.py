@@ -130,3 +130,28 @@ def test_plain_c_client_matches_the_python_host_class(usim, tmp_path):
     assert rec["obs_hash"] == f"{h:016x}"
     assert abs(float(rec["mean_reward"]) - total / (n * steps)) < 1e-5
     env.close()
+
+
+@pytest.mark.parametrize("torso, n, kw", [("rigid", 70, {}), ("soft", 70, {}), ("soft", 70, {"warm_start": 1}), ("full", 8, {})],
+                         ids=["rigid", "soft", "soft-warm", "full"])
+def test_checkpoint_moves_a_state_between_handles(usim, torso, n, kw):
+    """get_state of one handle, set_state on another of the same configuration, for every kind of state block and a number of environments that leaves padding
+    environments in it: the second handle hands out the same state bit for bit in every key (scalars, lattice, the full torso's body, the kept contact lists) and
+    computes the same next step"""
+    opts = dict(usim.default_robosuite_kwargs(), **kw)
+    a, b = (usim.UltrasoundVecEnv(n, device="cuda:0", seed=3, torso=torso, **opts) for _ in range(2))
+    a.reset_tensor(); b.reset_tensor()
+    a.rollout_random(0, 30)
+    st = a.get_state()
+    assert ("solver_warm_start" in st) == (torso == "full" or bool(kw)) and ("body" in st) == (torso == "full")
+    b.set_state(st)
+    st2 = b.get_state()
+    assert set(st2) == set(st)
+    for k in st:
+        assert st[k].dtype == st2[k].dtype and st[k].shape == st2[k].shape and np.ascontiguousarray(st[k]).tobytes() == np.ascontiguousarray(st2[k]).tobytes(), k
+    act = a.random_actions_tensor(30).clone()
+    oa = [t.clone() for t in a.step_tensor(act)]
+    ob = [t.clone() for t in b.step_tensor(act)]
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(oa, ob))
+    a.close(); b.close()

@@ -453,6 +453,47 @@ int usim_policy_reward(const usim_norm_stats* st, const float* rew_dev, const ui
 int usim_policy_gae(const float* rewards_dev, const float* values_dev, const float* episode_starts_dev, const float* last_values_dev, const uint8_t* last_done_dev,
                     int T, int n, float gamma, float gae_lambda, float* advantages_dev, float* returns_dev, void* stream);
 
+/* ---- the learner: one PPO minibatch step on the device (csrc/usim_ppo.hip; ppo.py NativePPO) -- the loss of stable-baselines3's
+ * PPO.train on one minibatch of the rollout buffer with its gradient for every parameter of the usim_policy_net above (A <= 8), and clip_grad_norm_ +
+ * torch.optim.Adam.step on one flat parameter block.  Both calls check their arguments before anything is enqueued (USIM_ERR_INVALID: a NULL required pointer, act_dim
+ * outside 1 .. 8, batch < 1, rows < batch without an index list, a non-finite or negative clip_range / lr / eps, a non-finite coefficient, a beta outside [0, 1), a
+ * work_dev off the 16-byte grid) and are kernel launches on `stream` and nothing else -- no allocation, no synchronisation, no host read of device memory: a grad + adam
+ * pair can be captured into a graph as one chain.  Every sum over samples or workgroups has a fixed order (no floating-point atomics; USIM_PPO_WORKGROUPS partial
+ * blocks, whatever the device), so the same inputs give the same bits on every call.
+ *
+ * usim_ppo_grad, per sample, with Ad the advantage after the optional per-minibatch normalisation (Ad - mean) / (std + 1e-8) (float64, unbiased std as torch.std;
+ * skipped when batch == 1), log-prob the DiagGaussianDistribution.log_prob of act under (mean(obs), log_std), r = exp(log-prob - old_logp), c = clip_range:
+ *   policy term  -min(Ad r, Ad clip(r, 1 - c, 1 + c))      (a gradient passes unless Ad > 0 and r > 1 + c, or Ad < 0 and r < 1 - c)
+ *   value term   (ret - V(obs))^2                          entropy  sum log_std + A / 2 (1 + log 2 pi)
+ *   loss = mean(policy) + vf_coef mean(value) - ent_coef entropy
+ * grad_dev[usim_ppo_params(A)] receives d loss / d parameter in the flat order below; stats_dev[USIM_PPO_STATS]: policy_loss, value_loss, entropy_loss (= -entropy),
+ * approx_kl (mean((r - 1) - log r)), clip_fraction (mean(|r - 1| > c)), loss, the gradient's 2-norm, 0.  w2_packed of the net is ignored.  An index outside
+ * [0, rows) reads the nearest row of the buffer.  work_dev: usim_ppo_work_floats(A) floats on the 16-byte grid; the call rewrites every word it reads, so the
+ * workspace needs no clearing between calls (zero it once for a defined first state).
+ *
+ * usim_ppo_adam: g' = g min(1, max_grad_norm / (|g| + 1e-6)) (max_grad_norm <= 0: no clipping); *step_dev += 1 on the device, t = *step_dev;
+ *   m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;  theta -= lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * in float64 on the float32 words, each result rounded once.  The norm is formed here from grad_dev (the two calls are independent); stats_dev may be NULL, otherwise
+ * slot 6 receives the norm used. ---- */
+#define USIM_PPO_STATS 8
+#define USIM_PPO_WORKGROUPS 128                /* gradient workgroups per network = partial blocks of the workspace: a constant, not the device's CU count */
+/* floats in the flat parameter / gradient block, in the field order of usim_policy_net:
+ * pi_w1 pi_b1 pi_w2 pi_b2 act_w act_b vf_w1 vf_b1 vf_w2 vf_b2 val_w val_b log_std
+ * = 76032 + 130 A + 129;  < 0: error code */
+int     usim_ppo_params(int act_dim);
+int64_t usim_ppo_work_floats(int act_dim);     /* workspace of usim_ppo_grad, zero-initialised by the caller once */
+
+typedef struct usim_ppo_batch {
+    const float *obs_dev, *act_dev, *old_logp_dev, *adv_dev, *ret_dev;  /* RolloutBuffer slices flattened to [rows][19], [rows][A], [rows] x 3 */
+    const int32_t* index_dev;                  /* [batch] rows of this minibatch (repeats allowed); NULL: rows 0 .. batch-1 */
+    int32_t rows, batch, act_dim, normalize_advantage;
+    float clip_range, ent_coef, vf_coef, reserved_;
+} usim_ppo_batch;
+
+int usim_ppo_grad(const usim_policy_net* net, const usim_ppo_batch* b, float* work_dev, float* grad_dev, float* stats_dev, void* stream);
+int usim_ppo_adam(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int params,
+                  float lr, float beta1, float beta2, float eps, float max_grad_norm, float* stats_dev, void* stream);
+
 const char* usim_strerror(int status);
 const char* usim_last_hip_error(const usim_handle* h);
 const char* usim_version(void);

@@ -1,9 +1,11 @@
 """Learnability check: a from-scratch PPO (clip objective, GAE, Adam; SB3's default hyper-parameters where they matter) trained on the
 batched simulator through the device-side collector of policy.py.  Not part of the product path (the reference's training loop is
 stable-baselines3 and stays the caller); it answers one question: does reward per step climb from the random-gain level (5.6) towards
-what the reference's own policy earns on it (8.1)?   usage: python tools/ppo_demo.py [iterations] [n_envs] [n_steps] [impedance_mode] [collector]
+what the reference's own policy earns on it (8.1)?   usage: python tools/ppo_demo.py [iterations] [n_envs] [n_steps] [impedance_mode] [collector] [learner] [seed]
 collector: eager (policy.collect_rollouts, ~100 PyTorch launches per step), graph (the same loop recorded as a HIP graph) or fused (the library's policy
-kernels, usim_policy_step / _reward / _gae, recorded as a HIP graph; the default)"""
+kernels, usim_policy_step / _reward / _gae, recorded as a HIP graph; the default)
+learner: torch (the forty lines below: autograd + torch.optim.Adam; the default) or native (ppo.NativePPO: usim_ppo_grad + usim_ppo_adam per minibatch, the same
+four epochs of eight minibatches); seed: of the initialisation, the exploration noise and the minibatch shuffles (default 0)"""
 import importlib, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -17,7 +19,11 @@ n = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 128
 mode = sys.argv[4] if len(sys.argv) > 4 else "tracking"
 collector = sys.argv[5] if len(sys.argv) > 5 else "fused"
-torch.manual_seed(0)
+learner = sys.argv[6] if len(sys.argv) > 6 else "torch"
+seed = int(sys.argv[7]) if len(sys.argv) > 7 else 0
+if learner not in ("torch", "native"):
+    sys.exit(f"learner must be torch or native, got {learner!r}")
+torch.manual_seed(seed)
 kw = usim.default_robosuite_kwargs(); kw["controller_configs"] = dict(kw["controller_configs"], impedance_mode=mode)
 env = usim.UltrasoundVecEnv(n, device="cuda:0", seed=3, **kw)
 print(f"mode {mode}, {n} envs x {T} steps per iteration", flush=True)
@@ -29,11 +35,14 @@ for m in policy.modules():                                      # SB3: orthogona
 torch.nn.init.orthogonal_(policy.action_net.weight, gain=0.01); torch.nn.init.orthogonal_(policy.value_net.weight, gain=1.0)
 vn = pol.DeviceVecNormalize(n, 19, device=dev, training=True, norm_reward=True)
 buf = pol.DeviceRolloutBuffer(T, n, 19, env.action_dim, device=dev)
-opt = torch.optim.Adam(policy.parameters(), lr=3e-4, eps=1e-5)
-gen = torch.Generator(device=dev); gen.manual_seed(0)
+if learner == "native":
+    usim.ppo.flatten_parameters(policy)                          # before the collector records the parameters' addresses
+opt = torch.optim.Adam(policy.parameters(), lr=3e-4, eps=1e-5) if learner == "torch" else None
+gen = torch.Generator(device=dev); gen.manual_seed(seed)
 obs, start = None, None
-coll = pol.FusedRollout(env, policy, vn, buf, seed=0) if collector == "fused" else (pol.GraphedCollector(env, policy, vn, buf) if collector == "graph" else None)
-print(f"collector: {collector}", flush=True)
+coll = pol.FusedRollout(env, policy, vn, buf, seed=seed) if collector == "fused" else (pol.GraphedCollector(env, policy, vn, buf) if collector == "graph" else None)
+native = usim.ppo.NativePPO(env, policy, vn, buf, coll if collector == "fused" else None, n_epochs=4, seed=seed) if learner == "native" else None
+print(f"collector: {collector}, learner: {learner}, seed {seed}", flush=True)
 torch.cuda.synchronize()
 t0 = time.time()
 t_collect = 0.0
@@ -53,7 +62,9 @@ for it in range(iters):
         env.step_tensor = step_tensor
     torch.cuda.synchronize(); t_collect += time.time() - tc
     adv_all = buf.advantages
-    for epoch in range(4):
+    if native is not None:
+        vf = torch.tensor(native.update()["train/value_loss"])
+    for epoch in range(4 if native is None else 0):
         for ob, ac, val, lp, adv, ret in buf.get(batch_size=n * T // 8, generator=gen):
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
             values, logp, ent = policy.evaluate_actions(ob, ac)

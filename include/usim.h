@@ -449,6 +449,25 @@ int usim_policy_step_fused(const usim_policy_net* net, const usim_norm_stats* st
  * usim_policy_step that consumes that observation is then called with training = 2 ("statistics already updated with this observation"). */
 int usim_policy_reward(const usim_norm_stats* st, const float* rew_dev, const uint8_t* done_dev, int n, int training, int norm_reward, float* nrew_dev,
                        double* raw_sum_dev, const float* next_obs_dev, void* stream);
+/* Time-limit bootstrap of OnPolicyAlgorithm.collect_rollouts (`rewards[idx] += gamma * V(terminal_observation)` where infos[idx]["TimeLimit.truncated"]),
+ * for the step whose usim_step_io buffers are term_obs_dev [n][19], done_dev [n] and ep_length_dev [n].  Environment i is TRUNCATED iff done_dev[i] != 0 &&
+ * ep_length_dev[i] >= horizon (ep_length_dev is stale where not done; an early termination that falls on the horizon step counts as truncated, as in the numpy
+ * path's infos).  For those, rew_dev[i] = fmaf(gamma, V(nobs_i), rew_dev[i]) with
+ *   nobs_i = clip((term_obs_i - obs_mean) * (1 / sqrt(obs_var + epsilon)), +-clip_obs)   in float64, rounded to float32 -- usim_policy_step's arithmetic with
+ *                                                                                       training = 0: the statistics are read, never updated
+ *   V      = value_net(tanh(vf_2(tanh(vf_1(nobs)))))                                     float32 fmaf in a fixed order per environment, tanh as in usim_policy_step
+ * No other word of rew_dev is written, and no row of term_obs_dev of an environment that is not truncated is read (a NaN there has no effect).  An environment's
+ * result depends on its own inputs only -- not on n, on which other environments are truncated or on the device -- and the same inputs give the same bits on every
+ * call (no floating-point atomics).  count_dev (may be NULL): += the number of truncated environments.  Call it after rew_dev holds the (normalised) rewards of the
+ * step and before the next usim_step rewrites the env's buffers; VecNormalize.step_wait normalises the terminal observation with statistics that already contain the
+ * step's new observation, so it goes after the launch that updates them (usim_policy_reward with next_obs_dev, or the usim_policy_step_fused of the next step).
+ * Reads vf_w1 vf_b1 vf_w2 vf_b2 val_w val_b of the net (plain float32, torch.nn.Linear layout) and obs_mean / obs_var / epsilon / clip_obs of the statistics; the
+ * policy-side pointers, log_std and w2_packed are ignored and may be NULL (no usim_policy_pack needed).  One kernel launch on `stream` and nothing else: capture-safe.
+ * A workgroup of 32 environments that has no truncated one -- the common case -- returns after reading its flags.
+ * USIM_ERR_INVALID, before anything is enqueued and with nothing written: a NULL net, st, term_obs_dev, done_dev, ep_length_dev or rew_dev; a NULL vf_* / val_*
+ * pointer, obs_mean or obs_var; n <= 0 or horizon <= 0; a gamma that is not finite or outside [0, 1]. */
+int usim_policy_bootstrap(const usim_policy_net* net, const usim_norm_stats* st, const float* term_obs_dev, const uint8_t* done_dev, const int32_t* ep_length_dev,
+                          int n, int horizon, float gamma, float* rew_dev, int32_t* count_dev, void* stream);
 /* RolloutBuffer.compute_returns_and_advantage over [T][n] buffers (GAE(lambda), SB3's recursion) */
 int usim_policy_gae(const float* rewards_dev, const float* values_dev, const float* episode_starts_dev, const float* last_values_dev, const uint8_t* last_done_dev,
                     int T, int n, float gamma, float gae_lambda, float* advantages_dev, float* returns_dev, void* stream);

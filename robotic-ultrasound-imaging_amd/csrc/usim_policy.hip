@@ -15,6 +15,8 @@
 //   usim_policy_step_fused  the policy launch with both VecNormalize updates inside: its workgroups exchange partial sums through device-scope stores /
 //                           loads and arrival flags (no fences: see the kernel), then normalise and run the MLPs as above
 //   [usim_step]
+// and, where the caller asks for it, one more small launch per step:
+//   usim_policy_bootstrap   += gamma V(terminal observation) on the rewards of the environments that ended at the time limit (see the kernel)
 // The weights are read from the caller's tensors (torch parameters: an optimiser step is seen by the next call); nothing is copied.
 // Numerics: same formulas as policy.DeviceVecNormalize / MlpActorCritic; sums are ordered differently from PyTorch's kernels, so results agree to
 // rounding (tests/test_gpu_policy_replay.py: 1e-5 on means / values / log-probs, 1e-12 relative on the float64 statistics), not bit for bit.
@@ -554,6 +556,111 @@ __global__ void usim_policy_gae_kernel(const float* __restrict__ rewards, const 
     }
 }
 
+// Time-limit bootstrap (SB3 OnPolicyAlgorithm.collect_rollouts: `if done and infos[idx].get("TimeLimit.truncated"): rewards[idx] += gamma * V(terminal_observation)`):
+// environment i is truncated iff done[i] != 0 && ep_length[i] >= horizon (vec_env.py step_wait's rule; ep_length is stale where not done, hence both halves).
+// One workgroup = BT_TM consecutive environments.  Truncations are rare per step, so the common workgroup sees none: it reads its 32 flag pairs, passes one barrier
+// and returns -- no weight or statistics read is issued before that.  A workgroup that has some runs the value network for exactly those, one after the other,
+// on plain float32 multiply-adds (~38 k per environment: no matrix cores, no packed weights): it lists them in environment order (slot j of the list), and every
+// sum below runs over the inputs of ONE environment in an order that is fixed in the code -- not a function of j, of the other slots, of n or of the grid -- so an
+// environment's result has the same bits wherever and with whomever it is computed.
+//   normalise   float64 ((x - mean) * (1 / sqrt(var + eps))), clipped to +-clip_obs, rounded to float32: usim_policy_act_kernel's arithmetic; statistics read only
+//   layer 1     thread f holds row f of vf_w1 [256][19]: fmaf chain k = 0 .. 18 from 0, + bias, tanh_
+//   layer 2     the eight lanes of group g hold rows 4 g .. 4 g + 3 of vf_w2 [128][256] in registers (lane l the words k = 32 c + 4 l .. + 3 of chunk c = 0 .. 7,
+//               loaded once per workgroup; an activation word read from LDS serves four rows): per row one fmaf chain over the lane's 32 words, k ascending,
+//               then the xor-shuffle sums 1, 2, 4 (every lane arrives at the same bits), + bias, tanh_
+//   head        eight lanes per slot as in the policy kernel: sixteen terms each, xor-shuffle sums 1, 2, 4, + bias
+//   reward      rew[i] = fmaf(gamma, V, rew[i]); no other word of rew is touched, and rows of term_obs that are not truncated are never read
+// count (may be null) += the workgroup's number of truncated environments: an integer atomic, exact in any order.
+constexpr int BT_TM = 32;
+__global__ __launch_bounds__(256) void usim_policy_bootstrap_kernel(PolicyNet P, NormStats S, const float* __restrict__ term_obs, const uint8_t* __restrict__ done,
+                                                                    const int32_t* __restrict__ ep_length, int n, int horizon, float gamma, float* __restrict__ rew,
+                                                                    int32_t* __restrict__ count) {
+    __shared__ int list[BT_TM], m_s;
+    __shared__ double mean[PL_OBS], inv[PL_OBS];
+    __shared__ __attribute__((aligned(16))) float xs[BT_TM][PL_KPAD];
+    __shared__ __attribute__((aligned(16))) float h1[BT_TM][PL_H1S];
+    __shared__ __attribute__((aligned(16))) float h2[BT_TM][PL_H2S];
+    const int tid = threadIdx.x, row0 = blockIdx.x * BT_TM;
+    if (tid < 64) {                                                    // wave 0: the flags of this workgroup's environments, and the list of the truncated ones in order
+        const int env = row0 + tid;
+        const bool trunc = tid < BT_TM && env < n && done[env] != 0 && ep_length[env] >= horizon;
+        const unsigned long long mask = __ballot(trunc);
+        if (trunc) list[__popcll(mask & ((1ull << tid) - 1ull))] = tid;
+        if (tid == 0) m_s = __popcll(mask);
+    }
+    __syncthreads();
+    const int m = m_s;
+    if (m == 0) return;                                                // the common case ends here
+    // ---- every weight read is issued up front, in whole cache lines: the eight lanes of group g read 128 contiguous bytes of a row of vf_w2 per instruction (rows
+    //      4 g .. 4 g + 3 stay in registers for all slots: 32 float4 per thread), vf_w1 goes through LDS (h1's space, free until layer 1 writes it) ----
+    const int g = tid >> 3, l = tid & 7;
+    float4 w2[4][PL_H1 / 32];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < PL_H1 / 32; ++c) w2[r][c] = *reinterpret_cast<const float4*>(P.vf_w2 + (size_t)(4 * g + r) * PL_H1 + 32 * c + 4 * l);
+    float* w1s = &h1[0][0];
+    static_assert(PL_H1 * PL_OBS <= BT_TM * PL_H1S, "vf_w1 fits the layer-1 output buffer");
+#pragma unroll
+    for (int i = 0; i < PL_OBS; ++i) w1s[tid + 256 * i] = P.vf_w1[tid + 256 * i];
+    const float b1 = P.vf_b1[tid], b2 = P.vf_b2[4 * g + (l & 3)], vb = P.val_b[0];
+    const int hs = tid >> 3, ho = tid & 7;                              // head: slot, lane of the slot
+    float4 wh[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) wh[q] = *reinterpret_cast<const float4*>(&P.val_w[16 * ho + 4 * q]);
+    if (tid < PL_OBS) { mean[tid] = S.obs_mean[tid]; inv[tid] = 1.0 / sqrt(S.obs_var[tid] + S.epsilon); }
+    __syncthreads();
+    float w1[PL_OBS];
+#pragma unroll
+    for (int k = 0; k < PL_OBS; ++k) w1[k] = w1s[tid * PL_OBS + k];    // (row stride 19 words: no bank is hit twice by 32 lanes)
+    for (int e = tid; e < m * PL_KPAD; e += 256) {
+        const int j = e / PL_KPAD, c = e - j * PL_KPAD;
+        float v = 0.f;
+        if (c < PL_OBS) {
+            double x = ((double)term_obs[(size_t)(row0 + list[j]) * PL_OBS + c] - mean[c]) * inv[c];
+            x = x < -S.clip_obs ? -S.clip_obs : (x > S.clip_obs ? S.clip_obs : x);
+            v = (float)x;
+        }
+        xs[j][c] = v;
+    }
+    __syncthreads();                                                   // (every thread holds its row of vf_w1: h1 may be written)
+    for (int j = 0; j < m; ++j) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < PL_OBS; ++k) acc = fmaf(w1[k], xs[j][k], acc);
+        h1[j][tid] = tanh_(acc + b1);
+    }
+    __syncthreads();
+    for (int j = 0; j < m; ++j) {
+        float4 h[PL_H1 / 32];
+#pragma unroll
+        for (int c = 0; c < PL_H1 / 32; ++c) h[c] = *reinterpret_cast<const float4*>(&h1[j][32 * c + 4 * l]);
+        float s[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float a = 0.f;
+#pragma unroll
+            for (int c = 0; c < PL_H1 / 32; ++c) { a = fmaf(w2[r][c].x, h[c].x, a); a = fmaf(w2[r][c].y, h[c].y, a); a = fmaf(w2[r][c].z, h[c].z, a); a = fmaf(w2[r][c].w, h[c].w, a); }
+            a += __shfl_xor(a, 1); a += __shfl_xor(a, 2); a += __shfl_xor(a, 4);
+            s[r] = a;
+        }
+        const float sl = (l & 2) ? ((l & 1) ? s[3] : s[2]) : ((l & 1) ? s[1] : s[0]);
+        if (l < 4) h2[j][4 * g + l] = tanh_(sl + b2);
+    }
+    __syncthreads();
+    float acc = 0.f;
+    if (hs < m) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 h = *reinterpret_cast<const float4*>(&h2[hs][16 * ho + 4 * q]);
+            acc = fmaf(h.x, wh[q].x, acc); acc = fmaf(h.y, wh[q].y, acc); acc = fmaf(h.z, wh[q].z, acc); acc = fmaf(h.w, wh[q].w, acc);
+        }
+    }
+    acc += __shfl_xor(acc, 1); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 4);
+    if (hs < m && ho == 0) { const int env = row0 + list[hs]; rew[env] = fmaf(gamma, acc + vb, rew[env]); }
+    if (tid == 0 && count) atomicAdd(count, m);
+}
+
 // the C ABI's structs as kernel arguments, and the arguments usim_policy_step and usim_policy_step_fused both require
 static PolicyNet policy_net(const usim_policy_net& n) { return {n.pi_w1, n.pi_b1, n.pi_w2, n.pi_b2, n.act_w, n.act_b, n.vf_w1, n.vf_b1, n.vf_w2, n.vf_b2, n.val_w, n.val_b, n.log_std, reinterpret_cast<const float4*>(n.w2_packed)}; }
 static NormStats norm_stats(const usim_norm_stats& s) { return {s.obs_mean, s.obs_var, s.obs_count, s.ret_mean, s.ret_var, s.ret_count, s.returns, s.clip_obs, s.clip_reward, s.gamma, s.epsilon}; }
@@ -630,6 +737,16 @@ int usim_policy_reward(const usim_norm_stats* st, const float* rew_dev, const ui
                            next_obs_dev, st->scratch, reinterpret_cast<unsigned int*>(st->scratch + PL_SB * PL_OBS * 2));
     } else
     hipLaunchKernelGGL(usim_policy_reward_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, rew_dev, done_dev, n, S, training, norm_reward, nrew_dev, raw_sum_dev);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+int usim_policy_bootstrap(const usim_policy_net* net, const usim_norm_stats* st, const float* term_obs_dev, const uint8_t* done_dev, const int32_t* ep_length_dev,
+                          int n, int horizon, float gamma, float* rew_dev, int32_t* count_dev, void* stream) {
+    if (!net || !st || !term_obs_dev || !done_dev || !ep_length_dev || !rew_dev) return USIM_ERR_INVALID;
+    if (!net->vf_w1 || !net->vf_b1 || !net->vf_w2 || !net->vf_b2 || !net->val_w || !net->val_b || !st->obs_mean || !st->obs_var) return USIM_ERR_INVALID;
+    if (n <= 0 || horizon <= 0 || !(gamma >= 0.f && gamma <= 1.f)) return USIM_ERR_INVALID;           // (a NaN fails both comparisons)
+    hipLaunchKernelGGL(usim_policy_bootstrap_kernel, dim3((n + BT_TM - 1) / BT_TM), dim3(256), 0, (hipStream_t)stream, policy_net(*net), norm_stats(*st), term_obs_dev,
+                       done_dev, ep_length_dev, n, horizon, gamma, rew_dev, count_dev);
     return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
 }
 

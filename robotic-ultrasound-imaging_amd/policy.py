@@ -379,16 +379,22 @@ class DeviceRolloutBuffer:
 
 
 @torch.no_grad()
-def _rollout_step(env, policy, vecnorm, low, high, obs, episode_start, generator=None, store=None, raw_reward_sum=None):
+def _rollout_step(env, policy, vecnorm, low, high, obs, episode_start, generator=None, store=None, raw_reward_sum=None, bootstrap_gamma=None):
     """One step of the rollout loop, for collect_rollouts and GraphedCollector alike: normalise the observation, sample, clip the action to the box
     for the env, step, normalise the reward; store(normalised obs, unclipped action, normalised reward, episode_start, value, log-prob) where a store is
-    given.  Returns (next raw obs, next episode_start, done flags of this step); the first two are copies: the env rewrites its buffers."""
+    given.  bootstrap_gamma (the buffer's gamma; None: off): SB3's time-limit bootstrap -- where the step ended at the horizon (env.truncated) the
+    normalised reward becomes reward + gamma V(terminal observation), the terminal observation normalised with the statistics as they are after this
+    step (frozen for that normalisation: VecNormalize.step_wait has already seen the new observation).  A `where` on all environments, not a product with the
+    mask (rows of terminal_obs that are not truncated are stale and may hold anything) and no indexing: nothing synchronises, so the step can be captured.
+    Returns (next raw obs, next episode_start, done flags of this step); the first two are copies: the env rewrites its buffers."""
     nobs = vecnorm.normalize_obs(obs)
     act, value, logp = policy.sample(nobs, generator)
     obs, rew, done = env.step_tensor(torch.max(torch.min(act, high), low))
     if raw_reward_sum is not None:
         raw_reward_sum.add_(rew.sum())
     nrew = vecnorm.normalize_reward(rew, done)
+    if bootstrap_gamma is not None:
+        nrew = _bootstrap_truncated(policy, vecnorm, nrew, obs, env.terminal_obs, env.truncated, bootstrap_gamma)
     if store is not None:
         store(nobs, act, nrew, episode_start, value, logp)
     return obs.clone(), done.bool().clone(), done
@@ -402,6 +408,22 @@ def _bootstrap_value(policy, vecnorm, obs):
         return policy.forward(vecnorm.normalize_obs(obs))[1]
     finally:
         vecnorm.training = was_training
+
+
+@torch.no_grad()
+def _bootstrap_truncated(policy, vecnorm, nrew, next_obs, terminal_obs, truncated, gamma):
+    """-> where(truncated, nrew + gamma V(normalize(terminal_obs)), nrew).  This loop updates the observation statistics when an observation is CONSUMED (the
+    next step's normalize_obs), SB3's VecNormalize.step_wait when the env RETURNS it and before it normalises the terminal observation: while training, the
+    statistics therefore take `next_obs` in for this normalisation and are put back, bit for bit, afterwards."""
+    rms = (vecnorm.obs_mean, vecnorm.obs_var, vecnorm._obs_count)
+    kept = [t.clone() for t in rms] if vecnorm.training else None
+    if kept is not None:
+        vecnorm._update(*rms, next_obs)
+    value = _bootstrap_value(policy, vecnorm, terminal_obs)
+    if kept is not None:
+        for t, k in zip(rms, kept):
+            t.copy_(k)
+    return torch.where(truncated, nrew + float(gamma) * value, nrew)
 
 
 def _capture(env, record, prologue=None, generator=None):
@@ -425,11 +447,13 @@ def _capture(env, record, prologue=None, generator=None):
 
 
 @torch.no_grad()
-def collect_rollouts(env, policy, vecnorm, buffer, obs=None, episode_start=None, generator=None):
+def collect_rollouts(env, policy, vecnorm, buffer, obs=None, episode_start=None, generator=None, bootstrap_truncation=False):
     """OnPolicyAlgorithm.collect_rollouts for one buffer: sample actions from the policy on normalised observations, clip them to
     the action box for the env, store the unclipped sample, normalise rewards, bootstrap with the value of the last observation.
-    (SB3 also bootstraps time-limit truncations with the terminal observation's value; the reference's GymWrapper does not report
-    truncations, so that branch never fires there either.)  Returns (next raw obs, next episode_start) to continue from."""
+    SB3 also bootstraps time-limit truncations with the terminal observation's value; the reference's GymWrapper does not report
+    truncations, so by default no reward is touched.  bootstrap_truncation=True: rewards of steps that ended at the horizon
+    (env.truncated) get + gamma V(terminal observation), gamma the buffer's (_rollout_step).
+    Returns (next raw obs, next episode_start) to continue from."""
     dev = env.device
     low, high = torch.as_tensor(env.action_space.low, device=dev), torch.as_tensor(env.action_space.high, device=dev)
     if obs is None:
@@ -439,7 +463,8 @@ def collect_rollouts(env, policy, vecnorm, buffer, obs=None, episode_start=None,
     buffer.reset()
     done = episode_start
     for _ in range(buffer.buffer_size):
-        obs, episode_start, done = _rollout_step(env, policy, vecnorm, low, high, obs, episode_start, generator, buffer.add)
+        obs, episode_start, done = _rollout_step(env, policy, vecnorm, low, high, obs, episode_start, generator, buffer.add,
+                                                 bootstrap_gamma=buffer.gamma if bootstrap_truncation else None)
     buffer.compute_returns_and_advantage(_bootstrap_value(policy, vecnorm, obs), done.bool())
     return obs, episode_start
 
@@ -460,8 +485,9 @@ class GraphedCollector:
     generator registered with the graph.  The policy's parameters are read at their addresses: an optimiser that updates them in place (torch.optim)
     is seen by the next replay."""
 
-    def __init__(self, env, policy, vecnorm, buffer, generator=None, warmup_steps=2):
+    def __init__(self, env, policy, vecnorm, buffer, generator=None, warmup_steps=2, bootstrap_truncation=False):
         self.env, self.policy, self.vecnorm, self.buffer, self.generator = env, policy, vecnorm, buffer, generator
+        self.bootstrap_truncation = bool(bootstrap_truncation)                  # collect_rollouts' option: recorded with the rest (no host dependency)
         dev = env.device
         self._low, self._high = torch.as_tensor(env.action_space.low, device=dev), torch.as_tensor(env.action_space.high, device=dev)
         self.obs = env.reset_tensor().clone()                                   # raw observation the next rollout starts from
@@ -480,7 +506,8 @@ class GraphedCollector:
     def _step(self, obs, episode_start, t):
         """_rollout_step; with t, into the buffer slices of step t and the reward sum"""
         store, raw_sum = (None, None) if t is None else (functools.partial(self.buffer.write, t), self.raw_reward_sum)
-        return _rollout_step(self.env, self.policy, self.vecnorm, self._low, self._high, obs, episode_start, self.generator, store, raw_sum)
+        return _rollout_step(self.env, self.policy, self.vecnorm, self._low, self._high, obs, episode_start, self.generator, store, raw_sum,
+                             bootstrap_gamma=self.buffer.gamma if self.bootstrap_truncation else None)
 
     @torch.no_grad()
     def _record(self):
@@ -513,7 +540,11 @@ class FusedRollout:
     those objects is unchanged.  Differences from collect_rollouts: sums are ordered differently (agreement to rounding, not bit for bit) and the
     Gaussian noise comes from the library's counter-based stream (seed, environment, step), not from a torch generator."""
 
-    def __init__(self, env, policy, vecnorm, buffer, seed=0, graph=True, fused_stats=None, init_stats=True):
+    def __init__(self, env, policy, vecnorm, buffer, seed=0, graph=True, fused_stats=None, init_stats=True, bootstrap_truncation=False):
+        # bootstrap_truncation: SB3's time-limit bootstrap (usim_policy_bootstrap: one more small launch per step; off: the launches are exactly those below).
+        # `truncations` counts the truncated environment-steps of the last rollout on the device.
+        self.bootstrap_truncation = bool(bootstrap_truncation)
+        self.truncations = torch.zeros(1, dtype=torch.int32, device=env.device)
         # fused_stats: VecNormalize's two updates inside the policy launch (usim_policy_step_fused: two launches per step instead of three).  Its workgroups wait
         # for one another, so all of them must be resident: by default only up to 4096 environments (256 workgroups, half of what the device holds -- room
         # for a collective's kernels beside them); fused_stats=True asks for it up to the library's limit of 8192 (a device to itself)
@@ -602,6 +633,12 @@ class FusedRollout:
                                                     ptr(self._low), ptr(self._high), self.seed, int(counter) & 0xffffffff, ptr(self._ctr),
                                                     int(env.env_offset), int(bool(deterministic)), C.byref(out), env._stream()))
 
+    def _bootstrap(self, t):
+        """usim_policy_bootstrap on the env's buffers of the step just taken, into the (already written) rewards of buffer row t"""
+        env, b = self.env, self.buffer
+        self._check(self.lib.usim_policy_bootstrap(C.byref(self._net), C.byref(self._stats), env._term.data_ptr(), env._done.data_ptr(), env._ep_len.data_ptr(),
+                                                   env.num_envs, int(env.horizon), b.gamma, b.rewards[t].data_ptr(), self.truncations.data_ptr(), env._stream()))
+
     @property
     def wait_ran_out(self):
         """True if a workgroup of usim_policy_step_fused ever gave up waiting for the others' partial sums (the device was shared; statistics are then wrong)"""
@@ -615,23 +652,35 @@ class FusedRollout:
         fused_stats: two launches per step -- the policy launch also takes the statistics of the observation it reads and the reward side of the step before.
         Otherwise three, and the observation statistics follow VecNormalize's timing: RunningMeanStd.update(obs) when the environment RETURNS the observation
         (reset: once, in __init__; step: in the launch that also does the reward side), so the policy kernel only normalises (training = 2) and the bootstrap
-        value sees statistics that include the last observation, as SB3's `_last_obs` does."""
+        value sees statistics that include the last observation, as SB3's `_last_obs` does.
+        bootstrap_truncation: usim_policy_bootstrap of step t goes where rewards[t] has been written, the statistics contain the observation step t returned and
+        the env's buffers of step t are still intact -- right after the reward launch of step t, or (fused_stats: rewards[t] is written by the policy launch of
+        step t + 1) between that launch and the env step t + 1; for the last step after the bootstrap-value launch."""
         env, b, vn = self.env, self.buffer, self.vecnorm
         T, n = b.buffer_size, env.num_envs
+        boot = self.bootstrap_truncation
         env.refill_bank()                      # first node of the recorded sequence as well as the last: a replay is valid whatever ran on the env since the last one
         self.raw_reward_sum.zero_()
+        if boot:
+            self.truncations.zero_()
         self.pack()                            # the weights of this rollout (they do not change inside it)
         for t in range(T):
             if self.fused_stats:
                 self.act_fused(self.obs, self._prev_done, counter=t, rewards_out=b.rewards[t - 1] if t else None, t=t, pack=False)
+                if boot and t:
+                    self._bootstrap(t - 1)
                 env.step_tensor(self._act_env)
             else:
                 self.act(self.obs, self._prev_done, counter=t, training=2 if vn.training else 0, t=t, pack=False)
                 o, rew, done = env.step_tensor(self._act_env)
                 self._check(self.lib.usim_policy_reward(C.byref(self._stats), rew.data_ptr(), done.data_ptr(), n, int(bool(vn.training)), int(bool(vn.norm_reward)),
                                                         b.rewards[t].data_ptr(), self.raw_reward_sum.data_ptr(), o.data_ptr() if vn.training else None, env._stream()))
+                if boot:
+                    self._bootstrap(t)
         if self.fused_stats:                   # bootstrap value (+ the last step's reward side)
             self.act_fused(self.obs, self._prev_done, counter=T, rewards_out=b.rewards[T - 1], deterministic=True, pack=False)
+            if boot:
+                self._bootstrap(T - 1)
         else:
             self.act(self.obs, self._prev_done, counter=T, training=0, deterministic=True, pack=False)
         self._check(self.lib.usim_policy_gae(b.rewards.data_ptr(), b.values.data_ptr(), b.episode_starts.data_ptr(), self._value.data_ptr(), self._prev_done.data_ptr(),

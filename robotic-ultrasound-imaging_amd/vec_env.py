@@ -387,6 +387,12 @@ class UltrasoundVecEnv:
         return self._term
 
     @property
+    def truncated(self):
+        """bool [n], valid after a step: the episode ended at the time limit -- done & (episode_length >= horizon), the rule of infos[i]["TimeLimit.truncated"]
+        on the numpy path (episode_length is stale where not done).  A new device tensor; nothing synchronises."""
+        return self._done.bool() & (self._ep_len >= self.horizon)
+
+    @property
     def contacts(self):
         return self._contacts
 

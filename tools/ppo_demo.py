@@ -1,11 +1,13 @@
 """Learnability check: a from-scratch PPO (clip objective, GAE, Adam; SB3's default hyper-parameters where they matter) trained on the
 batched simulator through the device-side collector of policy.py.  Not part of the product path (the reference's training loop is
 stable-baselines3 and stays the caller); it answers one question: does reward per step climb from the random-gain level (5.6) towards
-what the reference's own policy earns on it (8.1)?   usage: python tools/ppo_demo.py [iterations] [n_envs] [n_steps] [impedance_mode] [collector] [learner] [seed]
+what the reference's own policy earns on it (8.1)?   usage: python tools/ppo_demo.py [iterations] [n_envs] [n_steps] [impedance_mode] [collector] [learner] [seed] [bootstrap]
 collector: eager (policy.collect_rollouts, ~100 PyTorch launches per step), graph (the same loop recorded as a HIP graph) or fused (the library's policy
 kernels, usim_policy_step / _reward / _gae, recorded as a HIP graph; the default)
 learner: torch (the forty lines below: autograd + torch.optim.Adam; the default) or native (ppo.NativePPO: usim_ppo_grad + usim_ppo_adam per minibatch, the same
-four epochs of eight minibatches); seed: of the initialisation, the exploration noise and the minibatch shuffles (default 0)"""
+four epochs of eight minibatches); seed: of the initialisation, the exploration noise and the minibatch shuffles (default 0)
+bootstrap: the word `bootstrap` switches the collector's bootstrap_truncation on (SB3's time-limit bootstrap: + gamma V(terminal observation) on the reward of a
+step that ended at the horizon); with the fused collector every line then also reports how many of the iteration's episode ends were truncations"""
 import importlib, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -21,8 +23,11 @@ mode = sys.argv[4] if len(sys.argv) > 4 else "tracking"
 collector = sys.argv[5] if len(sys.argv) > 5 else "fused"
 learner = sys.argv[6] if len(sys.argv) > 6 else "torch"
 seed = int(sys.argv[7]) if len(sys.argv) > 7 else 0
+boot = len(sys.argv) > 8
 if learner not in ("torch", "native"):
     sys.exit(f"learner must be torch or native, got {learner!r}")
+if boot and sys.argv[8] != "bootstrap":
+    sys.exit(f"the eighth argument, if given, is the word bootstrap, got {sys.argv[8]!r}")
 torch.manual_seed(seed)
 kw = usim.default_robosuite_kwargs(); kw["controller_configs"] = dict(kw["controller_configs"], impedance_mode=mode)
 env = usim.UltrasoundVecEnv(n, device="cuda:0", seed=3, **kw)
@@ -40,9 +45,10 @@ if learner == "native":
 opt = torch.optim.Adam(policy.parameters(), lr=3e-4, eps=1e-5) if learner == "torch" else None
 gen = torch.Generator(device=dev); gen.manual_seed(seed)
 obs, start = None, None
-coll = pol.FusedRollout(env, policy, vn, buf, seed=seed) if collector == "fused" else (pol.GraphedCollector(env, policy, vn, buf) if collector == "graph" else None)
+bkw = dict(bootstrap_truncation=True) if boot else {}
+coll = pol.FusedRollout(env, policy, vn, buf, seed=seed, **bkw) if collector == "fused" else (pol.GraphedCollector(env, policy, vn, buf, **bkw) if collector == "graph" else None)
 native = usim.ppo.NativePPO(env, policy, vn, buf, coll if collector == "fused" else None, n_epochs=4, seed=seed) if learner == "native" else None
-print(f"collector: {collector}, learner: {learner}, seed {seed}", flush=True)
+print(f"collector: {collector}, learner: {learner}, seed {seed}" + (", bootstrap_truncation" if boot else ""), flush=True)
 torch.cuda.synchronize()
 t0 = time.time()
 t_collect = 0.0
@@ -58,7 +64,7 @@ for it in range(iters):
         def counting_step(a, _f=step_tensor):
             o, r, d = _f(a); raw.add_(r.sum()); return o, r, d
         env.step_tensor = counting_step
-        obs, start = pol.collect_rollouts(env, policy, vn, buf, obs=obs, episode_start=start, generator=gen)
+        obs, start = pol.collect_rollouts(env, policy, vn, buf, obs=obs, episode_start=start, generator=gen, **bkw)
         env.step_tensor = step_tensor
     torch.cuda.synchronize(); t_collect += time.time() - tc
     adv_all = buf.advantages
@@ -73,7 +79,12 @@ for it in range(iters):
             vf = torch.nn.functional.mse_loss(values, ret)
             loss = pg + 0.5 * vf - 0.0 * ent.mean()
             opt.zero_grad(); loss.backward(); torch.nn.utils.clip_grad_norm_(policy.parameters(), 0.5); opt.step()
+    # episode ends of this iteration: the starts the buffer recorded after its first row, and the done flags of its last step (fused collector: the env's own)
+    trunc = ""
+    if boot and collector == "fused":
+        ends = int(buf.episode_starts[1:].sum()) + int(coll._prev_done.bool().sum())
+        trunc = f"  truncated {int(coll.truncations):6d} of {ends:6d} episode ends"
     print(f"iter {it:3d}  env-steps {(it + 1) * n * T:9d}  reward/step {float(raw) / (n * T):6.3f}  value loss {float(vf.detach()):7.4f}  "
-          f"std {float(torch.exp(policy.log_std.detach()).mean()):5.3f}  wall {time.time() - t0:6.1f}s  (collecting {t_collect:5.2f}s)", flush=True)
+          f"std {float(torch.exp(policy.log_std.detach()).mean()):5.3f}  wall {time.time() - t0:6.1f}s  (collecting {t_collect:5.2f}s){trunc}", flush=True)
 print(f"collection: {iters * n * T / t_collect / 1e6:.1f} M env-steps/s; with the PPO updates: {iters * n * T / (time.time() - t0) / 1e6:.2f} M env-steps/s")
 env.close()

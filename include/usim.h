@@ -345,6 +345,43 @@ int usim_pack_step(const usim_step_io* io, int n, float* packed_dev, void* strea
  * length_dev, n <= 0 or nsteps <= 0: USIM_ERR_INVALID, nothing is written. */
 int usim_score_block(const float* rew_block_dev, const uint8_t* done_block_dev, int nsteps, int n, float gamma, float* return_dev, int32_t* length_dev, void* stream);
 
+/* ---- episode statistics on the device: SB3's Monitor + `ep_info_buffer = deque(maxlen = stats_window_size)` (the source of rollout/ep_rew_mean, the curve of
+ * src/utils/plot.py:420-436; src/rl.py:39 wraps every environment in a Monitor), fed by one launch after every usim_step (csrc/usim_monitor.hip; monitor.py
+ * DeviceMonitor, evaluate_policy).  usim_monitor_step reads io->done_dev, io->ep_return_dev and io->ep_length_dev of the step just taken (all three required; the
+ * other members are ignored), on the same stream, and updates monitor_dev, a caller-owned device block of usim_monitor_words(window) 32-bit words, 16-byte aligned,
+ * that lives across launches.  An all-zero block is an empty monitor.  The block:
+ *     words 0 - 1      episodes    int64    episodes counted over the monitor's life
+ *     words 2 - 3      length_sum  int64    sum of their lengths
+ *     words 4 - 5      return_sum  float64  sum of their returns
+ *     words 6 - 7      truncated   int64    counted episodes with ep_length >= horizon (horizon <= 0: none)
+ *     words 8 - 9      launches    int64    + 1 per call
+ *     words 10 - 15    zero
+ *     words 16 ..      the ring: `window` rows of USIM_MONITOR_ROW_WORDS words {ep_return (its bits), ep_length (int32), environment index (int32), the low 32 bits of
+ *                      `launches` as the call found it = the number of the launch, counted from 0}
+ * Environment i is COUNTED in a launch iff done_dev[i] != 0 (any non-zero byte, as in usim_pack_step) and either target_dev == NULL or count_dev[i] < target_dev[i]
+ * (int32 [n] each; SB3's evaluate_policy: "n episodes, at most target[i] of them from environment i"); count_dev[i] is then incremented.  The counted environments
+ * are appended IN ASCENDING ENVIRONMENT INDEX, as _update_info_buffer(infos) walks them: episode number e, counted from 0 over the monitor's life, is ring row
+ * e mod window, so the min(episodes, window) newest episodes are live and the oldest live one is row episodes mod window once the ring is full.  A launch that
+ * counts more than `window` episodes stores only the last `window` of them (no row is stored twice in a launch).  Words of ep_return / ep_length of an environment
+ * that is not counted are stale and enter nothing (a NaN there does not reach return_sum).  Floats travel as their bits into the ring.
+ * One launch of one workgroup; return_sum is accumulated in float64 in an order fixed by the code (no floating-point atomics, nothing ordered by arrival): the same
+ * block and the same inputs give the same block bit for bit.  No handle, no allocation, no synchronisation: capture-safe.  USIM_ERR_INVALID before anything is
+ * enqueued: a NULL io, done_dev, ep_return_dev, ep_length_dev or monitor_dev, a monitor_dev off the 16-byte grid, n <= 0, a window outside 1 .. USIM_MONITOR_MAX_WINDOW,
+ * target_dev without count_dev.
+ *
+ * usim_explained_variance: SB3's explained_variance(values, returns) = 1 - var(returns - values) / var(returns) (train/explained_variance) over `count` float32 words
+ * each, to out_dev[0] as float32; NaN when var(returns) == 0.  One launch; float64 sums of the words shifted by their first element (a large mean does not cancel
+ * the variance), in an order fixed by the code.  USIM_ERR_INVALID: a NULL pointer, count <= 0. */
+#define USIM_MONITOR_HEADER_WORDS 16
+#define USIM_MONITOR_ROW_WORDS     4
+#define USIM_MONITOR_MAX_WINDOW   (1 << 20)
+int usim_monitor_words(int window);   /* 16 + 4 * window 32-bit words; < 0: error code */
+int usim_monitor_step(const usim_step_io* io, int n, int window, int horizon,
+                      const int32_t* target_dev, int32_t* count_dev,
+                      uint32_t* monitor_dev, void* stream);
+int usim_explained_variance(const float* values_dev, const float* returns_dev,
+                            int64_t count, float* out_dev, void* stream);
+
 /* ---- a batched MPPI shooting planner: the sampler before usim_rollout_actions and the update after usim_score_block (csrc/usim_plan.hip; planner.py MPPIPlanner;
  * INTEGRATION.md section 4c).  `groups` = G controlled environments, `per_group` = K candidates each, n = G K simulated environments: environments [g K, (g + 1) K)
  * play the candidates of group g, and candidate k = 0 of every group is the unperturbed nominal.  Caller-owned float32 device buffers: the nominal mean [G][H][A]

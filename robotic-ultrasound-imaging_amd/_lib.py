@@ -24,6 +24,17 @@ WARM_WORDS = 8 + 16 * 4            # USIM_WARM_WORDS
 FULL_BODY_WORDS = 13 + 4 * 270 + 8 + 64      # USIM_FULL_BODY_WORDS: the free body (13), then the warm start of the full torso's contact solve
 PACK_HEAD_WORDS = 21               # USIM_PACK_HEAD_WORDS: obs[19], rew, done
 PACK_EPISODE_WORDS = 23            # USIM_PACK_EPISODE_WORDS: env index, ep_length, ep_return, status, terminal_observation[19]
+MONITOR_HEADER_WORDS = 16          # USIM_MONITOR_HEADER_WORDS: episodes, length_sum, return_sum, truncated, launches (64 bits each), six zero words
+MONITOR_ROW_WORDS = 4              # USIM_MONITOR_ROW_WORDS: ep_return bits, ep_length, environment index, launch number
+MONITOR_MAX_WINDOW = 1 << 20       # USIM_MONITOR_MAX_WINDOW
+
+
+def monitor_words(window):
+    """usim_monitor_words(window): 32-bit words of the block usim_monitor_step keeps for a ring of `window` episodes"""
+    w = int(window)
+    if not 1 <= w <= MONITOR_MAX_WINDOW:
+        raise ValueError(f"window must be 1 .. {MONITOR_MAX_WINDOW}, got {window!r}")
+    return MONITOR_HEADER_WORDS + MONITOR_ROW_WORDS * w
 
 
 def pack_words(n):
@@ -124,6 +135,9 @@ SYMBOLS = {
                                   C.c_void_p]),
     "usim_pack_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_void_p, C.c_void_p]),
     "usim_score_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_monitor_words": (C.c_int, [C.c_int]),
+    "usim_monitor_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_explained_variance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "usim_plan_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_plan_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,

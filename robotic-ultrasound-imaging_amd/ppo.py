@@ -11,6 +11,7 @@ so all of them keep working on the same memory.
     ppo.learn(40); ppo.save("model.zip")
 """
 import ctypes as C
+import time
 
 import torch
 
@@ -22,7 +23,8 @@ FIELDS = (("pi_w1", "policy_net.0.weight"), ("pi_b1", "policy_net.0.bias"), ("pi
           ("act_w", "action_net.weight"), ("act_b", "action_net.bias"), ("vf_w1", "value_net_body.0.weight"), ("vf_b1", "value_net_body.0.bias"),
           ("vf_w2", "value_net_body.2.weight"), ("vf_b2", "value_net_body.2.bias"), ("val_w", "value_net.weight"), ("val_b", "value_net.bias"),
           ("log_std", "log_std"))
-STAT_NAMES = ("train/policy_gradient_loss", "train/value_loss", "train/entropy_loss", "train/approx_kl", "train/clip_fraction", "train/loss")
+STAT_NAMES = ("train/policy_gradient_loss", "train/value_loss", "train/entropy_loss", "train/approx_kl", "train/clip_fraction", "train/loss",
+              "train/explained_variance")       # the first six: usim_ppo_grad's statistics of the last minibatch; the seventh: usim_explained_variance on the buffer
 
 
 def ppo_params(act_dim):
@@ -130,6 +132,9 @@ class NativePPO:
         self.step_count = z(1, torch.int32)                                   # Adam's step, advanced on the device
         self.stats = z(_lib.PPO_STATS)
         self.first_stats = z(_lib.PPO_STATS)                                  # the statistics of the first minibatch of the last update()
+        self._ev = z(1)                                                       # train/explained_variance of the last update() (usim_explained_variance)
+        self.history = []                                                     # learn(): one dict of logger scalars per iteration
+        self.num_timesteps = 0                                                # environment steps collected by learn() so far
         self._work = z(int(self.lib.usim_ppo_work_floats(A)))
         self._index = torch.zeros(rollout, dtype=torch.int32, device=dev)
         self.generator = torch.Generator(device=dev)
@@ -163,10 +168,14 @@ class NativePPO:
 
     def update(self):
         """PPO.train on the buffer as it is: n_epochs passes, each a torch.randperm on the device cut into minibatches of batch_size (the trailing partial one
-        is used, as in SB3), then the collector's pack().  -> the statistics of the last minibatch under SB3's logger names (one host read at the end)"""
+        is used, as in SB3), then the collector's pack().  -> the statistics of the last minibatch under SB3's logger names, and train/explained_variance of the
+        buffer's values against its returns as they are BEFORE the first minibatch (SB3's explained_variance; one launch into a device word).  One host read at
+        the end brings both."""
         b = self.buffer
         if not b.full:
             raise RuntimeError("rollout buffer is not full")
+        values, returns = b.values.contiguous(), b.returns.contiguous()
+        self._check(self.lib.usim_explained_variance(values.data_ptr(), returns.data_ptr(), values.numel(), self._ev.data_ptr(), self.env._stream()))
         data = tuple(self._flat(x) for x in (b.observations, b.actions, b.log_probs, b.advantages, b.returns))
         N, lr, first = self.rollout, self.current_lr(), True
         for _ in range(self.n_epochs):
@@ -179,18 +188,28 @@ class NativePPO:
                     first = False
         if self.collector is not None and hasattr(self.collector, "pack"):
             self.collector.pack()
-        s = self.stats.tolist()
-        return dict(zip(STAT_NAMES, s[:6]))
+        s = torch.cat((self.stats, self._ev)).tolist()                        # one read for both
+        return dict(zip(STAT_NAMES, s[:6] + s[_lib.PPO_STATS:]))
 
     def learn(self, iterations):
-        """`iterations` x (collector.collect(), update()); -> the statistics of the last update"""
+        """`iterations` x (collector.collect(), update()); -> the statistics of the last update.  Every iteration appends one dict to self.history -- SB3's logger
+        scalars: time/total_timesteps (environment steps collected by learn() so far), time/wall (time.time()), the train/* statistics of update(),
+        train/learning_rate and, when the env has a monitor attached (env.attach_monitor, before the collector was built), its summary(): rollout/ep_rew_mean,
+        rollout/ep_len_mean, ... -- the series monitor.write_scalar_csv writes out."""
         if self.collector is None:
             raise ValueError("learn() needs a collector")
         out = None
         for it in range(int(iterations)):
             self.progress_remaining = 1.0 - it / float(iterations)
+            lr = self.current_lr()
             self.collector.collect()
             out = self.update()
+            self.num_timesteps += self.rollout
+            row = {"time/total_timesteps": self.num_timesteps, "time/wall": time.time(), **out, "train/learning_rate": lr}
+            mon = getattr(self.env, "monitor", None)
+            if mon is not None:
+                row.update(mon.summary())
+            self.history.append(row)
         self.progress_remaining = 1.0
         return out
 

@@ -93,6 +93,7 @@ class UltrasoundVecEnv:
         self._t_start = time.time()
         self._pending = False
         self.horizon = int(self.cfg.horizon)
+        self._episode_monitor = None                                  # monitor.DeviceMonitor fed by step_tensor (attach_monitor); not the boolean _monitor of the numpy path's infos
 
     @property
     def env_offset(self):
@@ -167,7 +168,31 @@ class UltrasoundVecEnv:
         self._io.act_dev = a.data_ptr()
         self._check(self.lib.usim_step(self._handle, C.byref(self._io), int(auto_reset), self._stream()))
         self._last_act = a           # keep the tensor alive until the kernel has run
+        if self._episode_monitor is not None:
+            self._episode_monitor.record()
         return self._obs, self._rew, self._done
+
+    def attach_monitor(self, mon):
+        """Feed `mon` (a monitor.DeviceMonitor of this env) from now on: step_tensor enqueues mon.record() -- one usim_monitor_step launch -- right after every
+        usim_step, so everything that steps through step_tensor is monitored: the SB3 numpy path (step_async) and every collector of policy.py (collect_rollouts,
+        GraphedCollector, FusedRollout, hence ppo.NativePPO.learn), with no change to their signatures.  ATTACH BEFORE A COLLECTOR IS BUILT: a recorded collector
+        (GraphedCollector, FusedRollout(graph=True)) holds the launches that were enqueued while it was captured -- one built afterwards records the monitor's launch in
+        its graph, one built before never feeds it.  Detached is the default, and the launches are then exactly those of an env without the feature.
+        Multi-step launches are not monitored: rollout_random and rollout_actions keep no per-step ep_return / ep_length.  Returns mon."""
+        if mon.env is not self:
+            raise ValueError("the monitor was built for another environment")
+        self._episode_monitor = mon
+        return mon
+
+    def detach_monitor(self):
+        """Stop feeding the attached monitor (its block keeps what it holds); returns it, or None.  A collector recorded while it was attached goes on feeding it."""
+        mon, self._episode_monitor = self._episode_monitor, None
+        return mon
+
+    @property
+    def monitor(self):
+        """the attached monitor.DeviceMonitor, or None"""
+        return self._episode_monitor
 
     def refill_time(self):
         """(total device milliseconds, number) of the reset-bank refill launches issued so far (include/usim.h usim_refill_time)"""

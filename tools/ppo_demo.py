@@ -7,7 +7,10 @@ kernels, usim_policy_step / _reward / _gae, recorded as a HIP graph; the default
 learner: torch (the forty lines below: autograd + torch.optim.Adam; the default) or native (ppo.NativePPO: usim_ppo_grad + usim_ppo_adam per minibatch, the same
 four epochs of eight minibatches); seed: of the initialisation, the exploration noise and the minibatch shuffles (default 0)
 bootstrap: the word `bootstrap` switches the collector's bootstrap_truncation on (SB3's time-limit bootstrap: + gamma V(terminal observation) on the reward of a
-step that ended at the horizon); with the fused collector every line then also reports how many of the iteration's episode ends were truncations"""
+step that ended at the horizon); with the fused collector every line then also reports how many of the iteration's episode ends were truncations
+Every line also carries what SB3's logger prints: rollout/ep_rew_mean and ep_len_mean over the last 100 episodes (a monitor.DeviceMonitor attached to the env before
+the collector is built) and train/explained_variance of the buffer the update starts from.  An argument of the form csv=PATH, anywhere, writes the ep_rew_mean
+series as TensorBoard's CSV export (monitor.write_scalar_csv: the file src/utils/plot.py plot_training_rew_mean reads)."""
 import importlib, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -16,6 +19,8 @@ import torch
 usim = importlib.import_module("robotic-ultrasound-imaging_amd")
 pol = importlib.import_module("robotic-ultrasound-imaging_amd.policy")
 
+csv_path = next((a[4:] for a in sys.argv[1:] if a.startswith("csv=")), None)
+sys.argv = [a for a in sys.argv if not a.startswith("csv=")]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 128
@@ -44,6 +49,8 @@ if learner == "native":
     usim.ppo.flatten_parameters(policy)                          # before the collector records the parameters' addresses
 opt = torch.optim.Adam(policy.parameters(), lr=3e-4, eps=1e-5) if learner == "torch" else None
 gen = torch.Generator(device=dev); gen.manual_seed(seed)
+mon = env.attach_monitor(usim.DeviceMonitor(env))                # before the collector is built: a recorded collector holds the launches of its capture
+ev_word, rows = torch.zeros(1, dtype=torch.float32, device=dev), []
 obs, start = None, None
 bkw = dict(bootstrap_truncation=True) if boot else {}
 coll = pol.FusedRollout(env, policy, vn, buf, seed=seed, **bkw) if collector == "fused" else (pol.GraphedCollector(env, policy, vn, buf, **bkw) if collector == "graph" else None)
@@ -69,7 +76,12 @@ for it in range(iters):
     torch.cuda.synchronize(); t_collect += time.time() - tc
     adv_all = buf.advantages
     if native is not None:
-        vf = torch.tensor(native.update()["train/value_loss"])
+        stats = native.update()
+        vf, ev = torch.tensor(stats["train/value_loss"]), stats["train/explained_variance"]
+    else:                                                       # the torch learner: the same launch on the buffer before its first minibatch
+        values, returns = buf.values.contiguous(), buf.returns.contiguous()
+        usim._lib.check(env.lib, env.lib.usim_explained_variance(values.data_ptr(), returns.data_ptr(), values.numel(), ev_word.data_ptr(), env._stream()))
+        ev = float(ev_word)
     for epoch in range(4 if native is None else 0):
         for ob, ac, val, lp, adv, ret in buf.get(batch_size=n * T // 8, generator=gen):
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
@@ -84,7 +96,14 @@ for it in range(iters):
     if boot and collector == "fused":
         ends = int(buf.episode_starts[1:].sum()) + int(coll._prev_done.bool().sum())
         trunc = f"  truncated {int(coll.truncations):6d} of {ends:6d} episode ends"
-    print(f"iter {it:3d}  env-steps {(it + 1) * n * T:9d}  reward/step {float(raw) / (n * T):6.3f}  value loss {float(vf.detach()):7.4f}  "
+    summary = mon.summary()
+    rows.append({"time/total_timesteps": (it + 1) * n * T, "time/wall": time.time(), "train/explained_variance": ev, **summary})
+    print(f"iter {it:3d}  env-steps {(it + 1) * n * T:9d}  reward/step {float(raw) / (n * T):6.3f}  ep_rew_mean {summary['rollout/ep_rew_mean']:8.2f}  "
+          f"ep_len_mean {summary['rollout/ep_len_mean']:6.1f}  explained_variance {ev:6.3f}  value loss {float(vf.detach()):7.4f}  "
           f"std {float(torch.exp(policy.log_std.detach()).mean()):5.3f}  wall {time.time() - t0:6.1f}s  (collecting {t_collect:5.2f}s){trunc}", flush=True)
 print(f"collection: {iters * n * T / t_collect / 1e6:.1f} M env-steps/s; with the PPO updates: {iters * n * T / (time.time() - t0) / 1e6:.2f} M env-steps/s")
+print(f"episodes {rows[-1]['rollout/episodes']} ({rows[-1]['rollout/truncated']} at the time limit); over all of them: ep_rew_mean {rows[-1]['rollout/ep_rew_mean_all']:.2f}, "
+      f"ep_len_mean {rows[-1]['rollout/ep_len_mean_all']:.1f}")
+if csv_path:
+    print(f"{usim.write_scalar_csv(csv_path, rows, 'rollout/ep_rew_mean')} lines of rollout/ep_rew_mean -> {csv_path}")
 env.close()

@@ -530,8 +530,25 @@ int usim_policy_gae(const float* rewards_dev, const float* values_dev, const flo
  * usim_ppo_adam: g' = g min(1, max_grad_norm / (|g| + 1e-6)) (max_grad_norm <= 0: no clipping); *step_dev += 1 on the device, t = *step_dev;
  *   m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2;  theta -= lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
  * in float64 on the float32 words, each result rounded once.  The norm is formed here from grad_dev (the two calls are independent); stats_dev may be NULL, otherwise
- * slot 6 receives the norm used. ---- */
+ * slot 6 receives the norm used.
+ *
+ * clip_range_vf > 0 (SB3's clip_range_vf; 0 is its None), with old = old_value_dev[row] and c = clip_range_vf: the value term becomes (ret - Vp)^2 with
+ * Vp = old + clamp(V - old, -c, c).  Where |V - old| <= c (the closed interval, as torch's clamp passes its gradient) Vp is V itself and the row and its gradient
+ * 2 vf_coef (V - ret) / batch are the unclipped ones; elsewhere the row takes old +- c formed in float32 and its gradient is exactly 0.  With clip_range_vf == 0
+ * old_value_dev is not read and the call computes the bits it computes without the field.
+ *
+ * The gate: target_kl's early stop of PPO.train as a decision taken on the device.  gate_dev points to USIM_PPO_GATE_WORDS int32 words that the caller clears at
+ * the start of an update: [0] stop flag (0 or 1), [1] gradient calls evaluated since the words were cleared, [2] optimizer steps applied since then, [3] 0.
+ * Every kernel of usim_ppo_grad reads [0] on entry.  Set: the call is a no-op -- grad_dev, stats_dev and the gate keep their contents (the workspace is
+ * unspecified).  Clear: the call computes as without a gate, adds 1 to [1] and, last thing, sets [0] iff target_kl > 0 and the float32 approx_kl it has just
+ * written satisfies stats[3] > 1.5f * target_kl (a float32 product and compare, SB3's condition), so [0] is a function of the written stats[3] exactly.
+ * usim_ppo_adam_gated with [0] set writes nothing (theta, m, v, *step_dev and stats[6] keep their contents); otherwise it produces usim_ppo_adam's bits and adds 1
+ * to [2].  That is SB3's order: the minibatch whose KL trips the threshold is evaluated but not stepped, and no later one is.  The caller reads the gate when it
+ * reads the statistics -- once per update; a gated grad + adam pair is still launches on `stream` and nothing else, capturable as one chain.  The gate words are
+ * written by single threads of single-workgroup kernels with plain stores.  Further refusals (USIM_ERR_INVALID): a negative or non-finite clip_range_vf or
+ * target_kl, clip_range_vf > 0 with a NULL old_value_dev, target_kl > 0 with a NULL gate_dev. ---- */
 #define USIM_PPO_STATS 8
+#define USIM_PPO_GATE_WORDS 4
 #define USIM_PPO_WORKGROUPS 128                /* gradient workgroups per network = partial blocks of the workspace: a constant, not the device's CU count */
 /* floats in the flat parameter / gradient block, in the field order of usim_policy_net:
  * pi_w1 pi_b1 pi_w2 pi_b2 act_w act_b vf_w1 vf_b1 vf_w2 vf_b2 val_w val_b log_std
@@ -544,11 +561,18 @@ typedef struct usim_ppo_batch {
     const int32_t* index_dev;                  /* [batch] rows of this minibatch (repeats allowed); NULL: rows 0 .. batch-1 */
     int32_t rows, batch, act_dim, normalize_advantage;
     float clip_range, ent_coef, vf_coef, reserved_;
+    const float* old_value_dev;                /* [rows] RolloutBuffer.values, flattened like ret_dev; required iff clip_range_vf > 0 */
+    int32_t*     gate_dev;                     /* USIM_PPO_GATE_WORDS int32 words, or NULL: no gate */
+    float        clip_range_vf;                /* 0: off (SB3's None) */
+    float        target_kl;                    /* 0: off (SB3's None) */
 } usim_ppo_batch;
 
 int usim_ppo_grad(const usim_policy_net* net, const usim_ppo_batch* b, float* work_dev, float* grad_dev, float* stats_dev, void* stream);
 int usim_ppo_adam(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int params,
                   float lr, float beta1, float beta2, float eps, float max_grad_norm, float* stats_dev, void* stream);
+/* usim_ppo_adam behind the gate (gate_dev NULL: usim_ppo_adam itself) */
+int usim_ppo_adam_gated(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int params,
+                        float lr, float beta1, float beta2, float eps, float max_grad_norm, float* stats_dev, int32_t* gate_dev, void* stream);
 
 const char* usim_strerror(int status);
 const char* usim_last_hip_error(const usim_handle* h);

@@ -18,6 +18,7 @@ POLICY_SCRATCH = 1280              # USIM_POLICY_SCRATCH
 POLICY_FUSED_ROW = 48              # doubles per row of usim_policy_fused.work_dev (one row of partial sums per 32 environments)
 PPO_STATS = 8                      # USIM_PPO_STATS
 PPO_WORKGROUPS = 128               # USIM_PPO_WORKGROUPS: gradient workgroups per network (tiles of 32 minibatch rows at this stride)
+PPO_GATE_WORDS = 4                 # USIM_PPO_GATE_WORDS: stop flag, gradient calls evaluated, optimizer steps applied, 0
 RESET_PARAMS = 13
 LOG_WIDTH = 53
 WARM_WORDS = 8 + 16 * 4            # USIM_WARM_WORDS
@@ -118,7 +119,8 @@ class UsimPpoBatch(C.Structure):
     """struct usim_ppo_batch (include/usim.h): device pointers to the flattened rollout-buffer slices + the minibatch's index list and loss constants"""
     _fields_ = [(n, C.c_void_p) for n in ("obs_dev", "act_dev", "old_logp_dev", "adv_dev", "ret_dev", "index_dev")] + \
                [(n, C.c_int32) for n in ("rows", "batch", "act_dim", "normalize_advantage")] + \
-               [(n, C.c_float) for n in ("clip_range", "ent_coef", "vf_coef", "reserved_")]
+               [(n, C.c_float) for n in ("clip_range", "ent_coef", "vf_coef", "reserved_")] + \
+               [(n, C.c_void_p) for n in ("old_value_dev", "gate_dev")] + [(n, C.c_float) for n in ("clip_range_vf", "target_kl")]
 
 
 # every exported symbol of include/usim.h: name -> (restype, argtypes)
@@ -147,6 +149,8 @@ SYMBOLS = {
     "usim_ppo_grad": (C.c_int, [C.POINTER(UsimPolicyNet), C.POINTER(UsimPpoBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_ppo_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_void_p, C.c_void_p]),
+    "usim_ppo_adam_gated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_default_config": (C.c_int, [C.POINTER(UsimConfig)]),
     "usim_create": (C.c_int, [C.POINTER(UsimConfig), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "usim_destroy": (None, [C.c_void_p]),

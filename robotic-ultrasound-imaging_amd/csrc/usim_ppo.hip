@@ -16,6 +16,12 @@
 //   finish    one workgroup: the W rows of loss sums in row order, the gradient's 2-norm, the eight statistics
 // usim_ppo_adam is two: a one-thread launch that advances the step count, and the update (every workgroup forms the same norm from the whole gradient itself).
 //
+// clip_range_vf (SB3's value clipping) is a second instance of the gradient kernel (template parameter VF): stage 3's value lanes clamp V around the row's old
+// value, one more LDS row.  A call without it launches the instance without it, whose value path is the one above, instruction for instruction.
+// The gate (target_kl's early stop, taken on the device; include/usim.h states the words): every kernel of both calls reads the stop flag on entry -- one word, the
+// same for every thread, in front of every barrier -- and returns when it is set.  Thread 0 of finish counts the call and, last thing, sets the flag from the
+// float32 approx_kl it has just written; the one-thread count kernel counts the step.  Plain stores by single threads of single-workgroup kernels; no atomics.
+//
 // THE ORDER OF EVERY SUM IS FIXED: a thread adds its rows in ascending order inside a tile and its tiles in ascending order; blocks are added in block order; sums
 // over a workgroup are a butterfly inside the wave and the waves in order (as usim_plan.hip).  No floating-point atomics, nothing ordered by arrival, no dependence
 // on the device's CU count: the same inputs give the same bits on every call.
@@ -61,7 +67,13 @@ struct PpoBatch {
     const int32_t* index;
     int rows, batch, adim, normalize;
     float clip, inv_b, vf2;                                       // clip_range, 1 / batch, 2 vf_coef / batch
+    const float* oldv;                                            // RolloutBuffer.values, read only when cvf > 0
+    float cvf;                                                    // clip_range_vf; 0: off
+    const int32_t* gate;                                          // the gate words or NULL; [0] set: every kernel of the call returns on entry
 };
+
+// the stop flag of the gate, read by every thread on entry (the same word for all: the branch is uniform and in front of every barrier)
+DI bool pp_stopped(const int32_t* gate) { return gate && gate[0] != 0; }
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1), as usim_policy.hip's tanh_ (v_exp_f32 + v_rcp_f32: 2^-22 absolute; saturates to +-1)
 DI float pp_tanh(float x) { const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f); return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f); }
@@ -84,6 +96,7 @@ __global__ __launch_bounds__(PP_RED) void usim_ppo_prep_kernel(const float* __re
                                                                double* __restrict__ adv_out) {
     __shared__ double red[PP_RED / 64];
     const int tid = threadIdx.x;
+    if (pp_stopped(b.gate)) return;
     if (blockIdx.x > 0) {                                         // one word of one matrix per thread: 2 x 128 x 256 = 64 workgroups
         const int idx = (blockIdx.x - 1) * PP_RED + tid, net = idx / PP_W2, c = (idx / PP_H1) % PP_H2, k = idx % PP_H1;
         const float v = (net ? vf_w2 : pi_w2)[c * PP_H1 + k];
@@ -116,6 +129,9 @@ __global__ __launch_bounds__(PP_RED) void usim_ppo_prep_kernel(const float* __re
     if (tid == 0) { adv_out[0] = mean; adv_out[1] = inv; }
 }
 
+// VF: clip_range_vf > 0.  The value clip is compiled into an instance of its own, so that the kernel of a call without it is the one it was before the clip existed
+// (the branch in the shared body changed the register allocation of the whole kernel: profiles/ppo/resource_usage_gate.txt)
+template <bool VF>
 __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch b, float* __restrict__ work) {
     __shared__ __attribute__((aligned(16))) float xs[PP_TM][PP_XS];          // the tile's observations, column 19 zero
     __shared__ __attribute__((aligned(16))) float h1[PP_TM][PP_H1S];         // layer-1 activations; from the end of stage 6 the layer-1 deltas
@@ -123,8 +139,9 @@ __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch
     __shared__ __attribute__((aligned(16))) float whs[PP_MAXA][PP_H2];       // head weights, rows >= O zero
     __shared__ __attribute__((aligned(16))) float dout[PP_TM][PP_MAXA];      // d loss / d head output, columns >= O zero
     __shared__ float dls[PP_TM][PP_MAXA], acts[PP_TM][PP_MAXA];             // per-row d loss / d log_std; the tile's actions
-    __shared__ float r_old[PP_TM], r_adv[PP_TM], r_ret[PP_TM];
+    __shared__ float r_old[PP_TM], r_adv[PP_TM], r_ret[PP_TM], r_oldv[VF ? PP_TM : 1];      // r_oldv: the tile's old values (VF only)
     __shared__ double red[PP_WG / 64];
+    if (pp_stopped(b.gate)) return;
     const int tid = threadIdx.x, net = blockIdx.y, A = b.adim, O = net ? 1 : A, B = b.batch;
     const PpoLayout L = ppo_layout(net, A);
     const int P = ppo_params(A);
@@ -170,6 +187,7 @@ __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch
             r_old[r] = valid ? b.old_logp[src] : 0.f;
             r_adv[r] = valid ? (float)(((double)b.adv[src] - adv_mean) * adv_inv) : 0.f;
             r_ret[r] = valid ? b.ret[src] : 0.f;
+            if constexpr (VF) r_oldv[r] = valid ? b.oldv[src] : 0.f;
         }
         __syncthreads();
         // ---- stage 1: layer 1 (19 -> 256, tanh) ----
@@ -241,6 +259,15 @@ __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch
                     s_kl += (double)((ratio - 1.f) - lr);
                     s_cf += fabsf(ratio - 1.f) > b.clip ? 1.0 : 0.0;
                 }
+            } else if constexpr (VF) {
+                // clip_range_vf: Vp = old + clamp(V - old, -c, c).  Inside the closed band Vp is V itself (not re-rounded through old) and the row is the
+                // unclipped one; outside it the loss row takes old +- c formed in float32 and the gradient is exactly zero
+                const float d = out - r_ret[r], old = r_oldv[r], dv = out - old;
+                const bool inside = fabsf(dv) <= b.cvf;
+                const float dc = inside ? d : (dv > 0.f ? old + b.cvf : old - b.cvf) - r_ret[r];
+                dout[r][a] = (a == 0 && valid && inside) ? b.vf2 * d : 0.f;
+                dls[r][a] = 0.f;
+                if (a == 0 && valid) s_vl += (double)(dc * dc);
             } else {
                 const float d = out - r_ret[r];
                 dout[r][a] = (a == 0 && valid) ? b.vf2 * d : 0.f;
@@ -355,7 +382,9 @@ __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch
     }
 }
 
-__global__ __launch_bounds__(256) void usim_ppo_reduce_kernel(const float* __restrict__ work, int P, int A, float ent_coef, float* __restrict__ grad) {
+__global__ __launch_bounds__(256) void usim_ppo_reduce_kernel(const float* __restrict__ work, int P, int A, float ent_coef, float* __restrict__ grad,
+                                                               const int32_t* gate) {
+    if (pp_stopped(gate)) return;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     float s = 0.f;
@@ -378,8 +407,10 @@ DI double sum_of_squares(const float* __restrict__ g, int P, double* lds) {
 }
 
 __global__ __launch_bounds__(PP_RED) void usim_ppo_finish_kernel(const float* __restrict__ work, const float* __restrict__ grad, const float* __restrict__ log_std, int P,
-                                                                 int A, int batch, float vf_coef, float ent_coef, float* __restrict__ stats) {
+                                                                 int A, int batch, float vf_coef, float ent_coef, float* __restrict__ stats, int32_t* gate,
+                                                                 float target_kl) {
     __shared__ double red[PP_RED / 64];
+    if (pp_stopped(gate)) return;                                 // (every thread has read the flag before the barriers below; thread 0 writes it behind them)
     const double norm = sqrt(sum_of_squares(grad, P, red));
     if (threadIdx.x != 0) return;
     const double* sums = reinterpret_cast<const double*>(work + ppo_off_sums(A));
@@ -388,17 +419,30 @@ __global__ __launch_bounds__(PP_RED) void usim_ppo_finish_kernel(const float* __
     for (int a = 0; a < A; ++a) ent += (double)log_std[a];
     ent += A * (0.5 + 0.9189385332046727);                       // A / 2 (1 + log 2 pi)
     pl /= batch; vl /= batch; kl /= batch; cf /= batch;
-    stats[0] = (float)pl; stats[1] = (float)vl; stats[2] = (float)-ent; stats[3] = (float)kl; stats[4] = (float)cf;
+    const float kl32 = (float)kl;
+    stats[0] = (float)pl; stats[1] = (float)vl; stats[2] = (float)-ent; stats[3] = kl32; stats[4] = (float)cf;
     stats[5] = (float)(pl + (double)vf_coef * vl - (double)ent_coef * ent); stats[6] = (float)norm; stats[7] = 0.f;
+    if (gate) {                                                   // this thread alone writes the gate: the call's count, then -- last thing -- the stop flag
+        gate[1] += 1;
+        if (target_kl > 0.f && kl32 > 1.5f * target_kl) gate[0] = 1;      // SB3: approx_kl > 1.5 target_kl, on the float32 word just written
+    }
 }
 
-__global__ void usim_ppo_count_kernel(int32_t* __restrict__ step) { *step += 1; }
+// one thread: Adam's step count and, with a gate that is open, the gate's count of optimizer steps
+__global__ void usim_ppo_count_kernel(int32_t* __restrict__ step, int32_t* gate) {
+    if (gate) {
+        if (gate[0] != 0) return;
+        gate[2] += 1;
+    }
+    *step += 1;
+}
 
 __global__ __launch_bounds__(PP_RED) void usim_ppo_adam_kernel(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v,
                                                                const int32_t* __restrict__ step, int P, float lr, float beta1, float beta2, float eps, float max_norm,
-                                                               float* __restrict__ stats) {
+                                                               float* __restrict__ stats, const int32_t* gate) {
     __shared__ double red[PP_RED / 64];
     __shared__ double corr[2];
+    if (pp_stopped(gate)) return;
     const double norm = sqrt(sum_of_squares(grad, P, red));       // every workgroup: the same words in the same order
     if (threadIdx.x == 0) {
         const double t = (double)*step;
@@ -433,28 +477,37 @@ extern "C" int usim_ppo_grad(const usim_policy_net* net, const usim_ppo_batch* b
     if (b->act_dim < 1 || b->act_dim > PP_MAXA || b->batch < 1 || b->rows < 1 || (!b->index_dev && b->rows < b->batch)) return USIM_ERR_INVALID;
     if (b->batch > INT32_MAX - PP_LOADS * PP_RED) return USIM_ERR_INVALID;                  // (sample numbers are ints, and the strided loops step past the end once)
     if (!nonneg_finite(b->clip_range) || !isfinite(b->ent_coef) || !isfinite(b->vf_coef)) return USIM_ERR_INVALID;
+    if (!nonneg_finite(b->clip_range_vf) || !nonneg_finite(b->target_kl)) return USIM_ERR_INVALID;
+    if ((b->clip_range_vf > 0.f && !b->old_value_dev) || (b->target_kl > 0.f && !b->gate_dev)) return USIM_ERR_INVALID;
     const int A = b->act_dim, P = ppo_params(A);
     const PpoNet N{{net->pi_w1, net->vf_w1}, {net->pi_b1, net->vf_b1}, {net->pi_w2, net->vf_w2}, {net->pi_b2, net->vf_b2}, {net->act_w, net->val_w},
                    {net->act_b, net->val_b}, net->log_std};
     const PpoBatch K{b->obs_dev, b->act_dev, b->old_logp_dev, b->adv_dev, b->ret_dev, b->index_dev, b->rows, b->batch, A, b->normalize_advantage,
-                     b->clip_range, (float)(1.0 / b->batch), (float)(2.0 * (double)b->vf_coef / b->batch)};
+                     b->clip_range, (float)(1.0 / b->batch), (float)(2.0 * (double)b->vf_coef / b->batch), b->old_value_dev, b->clip_range_vf, b->gate_dev};
     const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(usim_ppo_prep_kernel, dim3(1 + 2 * PP_W2 / PP_RED), dim3(PP_RED), 0, s, net->pi_w2, net->vf_w2, K, work_dev + ppo_off_pack(A),
                        reinterpret_cast<double*>(work_dev + ppo_off_adv(A)));
-    hipLaunchKernelGGL(usim_ppo_grad_kernel, dim3(PP_W, 2), dim3(PP_WG), 0, s, N, K, work_dev);
-    hipLaunchKernelGGL(usim_ppo_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, work_dev, P, A, b->ent_coef, grad_dev);
-    hipLaunchKernelGGL(usim_ppo_finish_kernel, dim3(1), dim3(PP_RED), 0, s, work_dev, grad_dev, net->log_std, P, A, b->batch, b->vf_coef, b->ent_coef, stats_dev);
+    if (K.cvf > 0.f) hipLaunchKernelGGL(usim_ppo_grad_kernel<true>, dim3(PP_W, 2), dim3(PP_WG), 0, s, N, K, work_dev);
+    else hipLaunchKernelGGL(usim_ppo_grad_kernel<false>, dim3(PP_W, 2), dim3(PP_WG), 0, s, N, K, work_dev);
+    hipLaunchKernelGGL(usim_ppo_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, work_dev, P, A, b->ent_coef, grad_dev, b->gate_dev);
+    hipLaunchKernelGGL(usim_ppo_finish_kernel, dim3(1), dim3(PP_RED), 0, s, work_dev, grad_dev, net->log_std, P, A, b->batch, b->vf_coef, b->ent_coef, stats_dev,
+                       b->gate_dev, b->target_kl);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+extern "C" int usim_ppo_adam_gated(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int params, float lr, float beta1,
+                                   float beta2, float eps, float max_grad_norm, float* stats_dev, int32_t* gate_dev, void* stream) {
+    using namespace usim;
+    if (!theta_dev || !grad_dev || !m_dev || !v_dev || !step_dev || params < 1) return USIM_ERR_INVALID;
+    if (!nonneg_finite(lr) || !nonneg_finite(eps) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || isnan(max_grad_norm)) return USIM_ERR_INVALID;
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(usim_ppo_count_kernel, dim3(1), dim3(1), 0, s, step_dev, gate_dev);
+    hipLaunchKernelGGL(usim_ppo_adam_kernel, dim3((params + PP_RED - 1) / PP_RED), dim3(PP_RED), 0, s, theta_dev, grad_dev, m_dev, v_dev, step_dev, params, lr, beta1, beta2,
+                       eps, max_grad_norm, stats_dev, gate_dev);
     return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
 }
 
 extern "C" int usim_ppo_adam(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int params, float lr, float beta1, float beta2,
                              float eps, float max_grad_norm, float* stats_dev, void* stream) {
-    using namespace usim;
-    if (!theta_dev || !grad_dev || !m_dev || !v_dev || !step_dev || params < 1) return USIM_ERR_INVALID;
-    if (!nonneg_finite(lr) || !nonneg_finite(eps) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || isnan(max_grad_norm)) return USIM_ERR_INVALID;
-    const hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(usim_ppo_count_kernel, dim3(1), dim3(1), 0, s, step_dev);
-    hipLaunchKernelGGL(usim_ppo_adam_kernel, dim3((params + PP_RED - 1) / PP_RED), dim3(PP_RED), 0, s, theta_dev, grad_dev, m_dev, v_dev, step_dev, params, lr, beta1, beta2,
-                       eps, max_grad_norm, stats_dev);
-    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+    return usim_ppo_adam_gated(theta_dev, grad_dev, m_dev, v_dev, step_dev, params, lr, beta1, beta2, eps, max_grad_norm, stats_dev, nullptr, stream);
 }

@@ -10,7 +10,10 @@ bootstrap: the word `bootstrap` switches the collector's bootstrap_truncation on
 step that ended at the horizon); with the fused collector every line then also reports how many of the iteration's episode ends were truncations
 Every line also carries what SB3's logger prints: rollout/ep_rew_mean and ep_len_mean over the last 100 episodes (a monitor.DeviceMonitor attached to the env before
 the collector is built) and train/explained_variance of the buffer the update starts from.  An argument of the form csv=PATH, anywhere, writes the ep_rew_mean
-series as TensorBoard's CSV export (monitor.write_scalar_csv: the file src/utils/plot.py plot_training_rew_mean reads)."""
+series as TensorBoard's CSV export (monitor.write_scalar_csv: the file src/utils/plot.py plot_training_rew_mean reads).
+With the native learner three more arguments of that form: target_kl=X (SB3's early stop, decided on the device; every line then reports the optimizer steps of
+the update, of 32), save=FOLDER/NAME (NativePPO.save_checkpoint after the last iteration) and resume=FOLDER/NAME (NativePPO.load_checkpoint before the first:
+weights, Adam's moments and step count, VecNormalize statistics -- src/rl.py's continual training)."""
 import importlib, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -20,7 +23,8 @@ usim = importlib.import_module("robotic-ultrasound-imaging_amd")
 pol = importlib.import_module("robotic-ultrasound-imaging_amd.policy")
 
 csv_path = next((a[4:] for a in sys.argv[1:] if a.startswith("csv=")), None)
-sys.argv = [a for a in sys.argv if not a.startswith("csv=")]
+extra = {k: next((a[len(k) + 1:] for a in sys.argv[1:] if a.startswith(k + "=")), None) for k in ("target_kl", "save", "resume")}
+sys.argv = [a for a in sys.argv if not a.startswith(("csv=", "target_kl=", "save=", "resume="))]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 T = int(sys.argv[3]) if len(sys.argv) > 3 else 128
@@ -31,6 +35,8 @@ seed = int(sys.argv[7]) if len(sys.argv) > 7 else 0
 boot = len(sys.argv) > 8
 if learner not in ("torch", "native"):
     sys.exit(f"learner must be torch or native, got {learner!r}")
+if learner != "native" and any(v is not None for v in extra.values()):
+    sys.exit("target_kl=, save= and resume= are the native learner's")
 if boot and sys.argv[8] != "bootstrap":
     sys.exit(f"the eighth argument, if given, is the word bootstrap, got {sys.argv[8]!r}")
 torch.manual_seed(seed)
@@ -54,7 +60,12 @@ ev_word, rows = torch.zeros(1, dtype=torch.float32, device=dev), []
 obs, start = None, None
 bkw = dict(bootstrap_truncation=True) if boot else {}
 coll = pol.FusedRollout(env, policy, vn, buf, seed=seed, **bkw) if collector == "fused" else (pol.GraphedCollector(env, policy, vn, buf, **bkw) if collector == "graph" else None)
-native = usim.ppo.NativePPO(env, policy, vn, buf, coll if collector == "fused" else None, n_epochs=4, seed=seed) if learner == "native" else None
+native = usim.ppo.NativePPO(env, policy, vn, buf, coll if collector == "fused" else None, n_epochs=4, seed=seed,
+                          target_kl=None if extra["target_kl"] is None else float(extra["target_kl"])) if learner == "native" else None
+if extra["resume"]:
+    folder, _, name = extra["resume"].rpartition("/")
+    data = native.load_checkpoint(folder or ".", name)
+    print(f"resumed {extra['resume']}: Adam step {int(native.step_count.item())}, {data.get('num_timesteps', 0)} timesteps behind it", flush=True)
 print(f"collector: {collector}, learner: {learner}, seed {seed}" + (", bootstrap_truncation" if boot else ""), flush=True)
 torch.cuda.synchronize()
 t0 = time.time()
@@ -78,6 +89,7 @@ for it in range(iters):
     if native is not None:
         stats = native.update()
         vf, ev = torch.tensor(stats["train/value_loss"]), stats["train/explained_variance"]
+        native.num_timesteps += n * T
     else:                                                       # the torch learner: the same launch on the buffer before its first minibatch
         values, returns = buf.values.contiguous(), buf.returns.contiguous()
         usim._lib.check(env.lib, env.lib.usim_explained_variance(values.data_ptr(), returns.data_ptr(), values.numel(), ev_word.data_ptr(), env._stream()))
@@ -92,10 +104,10 @@ for it in range(iters):
             loss = pg + 0.5 * vf - 0.0 * ent.mean()
             opt.zero_grad(); loss.backward(); torch.nn.utils.clip_grad_norm_(policy.parameters(), 0.5); opt.step()
     # episode ends of this iteration: the starts the buffer recorded after its first row, and the done flags of its last step (fused collector: the env's own)
-    trunc = ""
+    trunc = "" if extra["target_kl"] is None else f"  approx_kl {stats['train/approx_kl']:.4f}  optimizer steps {native.last_update['train/optimizer_steps']:2d}"
     if boot and collector == "fused":
         ends = int(buf.episode_starts[1:].sum()) + int(coll._prev_done.bool().sum())
-        trunc = f"  truncated {int(coll.truncations):6d} of {ends:6d} episode ends"
+        trunc += f"  truncated {int(coll.truncations):6d} of {ends:6d} episode ends"
     summary = mon.summary()
     rows.append({"time/total_timesteps": (it + 1) * n * T, "time/wall": time.time(), "train/explained_variance": ev, **summary})
     print(f"iter {it:3d}  env-steps {(it + 1) * n * T:9d}  reward/step {float(raw) / (n * T):6.3f}  ep_rew_mean {summary['rollout/ep_rew_mean']:8.2f}  "
@@ -104,6 +116,9 @@ for it in range(iters):
 print(f"collection: {iters * n * T / t_collect / 1e6:.1f} M env-steps/s; with the PPO updates: {iters * n * T / (time.time() - t0) / 1e6:.2f} M env-steps/s")
 print(f"episodes {rows[-1]['rollout/episodes']} ({rows[-1]['rollout/truncated']} at the time limit); over all of them: ep_rew_mean {rows[-1]['rollout/ep_rew_mean_all']:.2f}, "
       f"ep_len_mean {rows[-1]['rollout/ep_len_mean_all']:.1f}")
+if extra["save"]:
+    folder, _, name = extra["save"].rpartition("/")
+    print("saved", *native.save_checkpoint(folder or ".", name))
 if csv_path:
     print(f"{usim.write_scalar_csv(csv_path, rows, 'rollout/ep_rew_mean')} lines of rollout/ep_rew_mean -> {csv_path}")
 env.close()

@@ -564,7 +564,7 @@ int usim_profile_step(usim_handle* h, const usim_step_io* s, int64_t step, uint6
     unsigned long long host[64];
     HIPCHK(h, hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost));
     HIPCHK(h, hipFree(d));
-    for (int i = 0; i < (max_ticks < 64 ? max_ticks : 64); ++i) ticks[i] = host[i];      // 0-16: phases of the single-wave kernels; 20-29 / 30-39: arm / lattice side of the split kernel
+    for (int i = 0; i < (max_ticks < 64 ? max_ticks : 64); ++i) ticks[i] = host[i];      // 0-16: phases of the single-wave kernels; 20-29 / 30-39: arm / lattice side of the split kernel; 54-61: 1 + broad-phase queue length of the environments of its first lattice wave
     return rc;
 }
 

@@ -116,6 +116,16 @@ struct DevCfg {
     int substeps;                       // physics steps (of dt) per control step: int(control_timestep / model_timestep) of robosuite MujocoEnv.step
     float dt_ctrl;                      // control timestep = substeps * dt (ultrasound.py:542)
     float frictionloss;                 // dry friction of every arm joint, N m (usim_config.joint_frictionloss)
+    float probe_cull2c;                 // broad phase with the element as a capsule (collide_cull CULL_CAPSULE): (rp + ELEM_R + margin)^2 with
+                                        //     rp = max(hypot(H, probe_h) + probe_r, H + probe_r2),  H = hypot(probe_hl, probe_hw).
+                                        // c = centre of the probe's upper axis (probe_tip - probe_r - probe_h along site z), S = the element's axis segment.  A point p of the blade
+                                        // (probe_sdf) is b + rho u + z with b in the rectangle |x| <= hl, |y| <= hw of the site's xy plane (|b| <= H), u a unit vector of that plane,
+                                        // and (rho, py) a point of the cross-section K = hull of the discs (0, 0; r) and (0, h; r2); c is the point (0, h) of the axis.  So
+                                        // |p - c|^2 = |b + rho u|^2 + (py - h)^2 <= (H + rho)^2 + (py - h)^2, the squared distance of (rho, py) from A = (-H, h).  The farthest point
+                                        // of a hull of two discs from A lies on one of them, at |centre - A| + radius: hypot(H, h) + r or H + r2.  Hence |p - c| <= rp, whatever
+                                        // probe_tip (it only moves c along site z) and for every probe_hw >= 0.  A point of the element lies within ELEM_R of S, so a common point
+                                        // needs dist(c, S) <= rp + ELEM_R: an element with dist(c, S)^2 >= probe_cull2c cannot touch.  margin 1e-4 m: fp32 rounding of the
+                                        // positions (~1e-7 m) and a clamped projection that misses the minimiser by |1 - |axis|| ELEM_HL (it can only lengthen the distance found)
 };
 
 struct DevIO {

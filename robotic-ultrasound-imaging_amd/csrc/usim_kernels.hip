@@ -217,10 +217,22 @@ DI void collide_elem(const float* lds, float* recs, const bool valid, const int 
 // axis segment.  An element whose ball misses that capsule cannot touch the probe: 80 % of the 99 elements, for 20 instructions each instead
 // of three distance evaluations.  The survivors go, in ascending element order, into a queue that the lanes of the group then walk together
 // (collide_queue): typically one pass of 16 instead of seven rounds.
+// CULL_CAPSULE: the roles of the two segments swapped -- the ELEMENT is tested as the capsule it is (radius ELEM_R around its axis segment of half-length
+// ELEM_HL) and the probe's short upper axis (half-length probe_hl, 0.65 cm against the element's 2.5 cm) is bounded by a ball around its centre: the lateral
+// reach falls from 7.35 cm to 4.97 cm for the same instructions per round (DevCfg::probe_cull2c states the inequality).  The cull only filters what the exact
+// narrow phase decides, so the contact lists keep their bits.
+#ifndef USIM_CULL_CAPSULE
+#define USIM_CULL_CAPSULE 1
+#endif
+constexpr bool CULL_CAPSULE = USIM_CULL_CAPSULE != 0;
 DI bool collide_cull(const float* lds, const int e, const DevModel& M, const DevCfg& C, const float se, const float dz, const f3 Kx, const f3 Ksx, const f3 Ksz) {
     const f3 ax = mk(lds[TB_AXIS + 3 * e], lds[TB_AXIS + 3 * e + 1], lds[TB_AXIS + 3 * e + 2]);
     const f3 mid = mk(M.torso[0] + lds[TB_POS + 3 * e], M.torso[1] + lds[TB_POS + 3 * e + 1], M.torso[2] + lds[TB_POS + 3 * e + 2] + dz) + ax * (se - ELEM_R - ELEM_HL);
     const f3 d = mid - (Kx - Ksz * (C.probe_r + C.probe_h - C.probe_tip));         // from the centre of the upper axis (site z points away from the probe body)
+    if constexpr (CULL_CAPSULE) {
+        const f3 v = d - ax * clampf(dot(d, ax), -ELEM_HL, ELEM_HL);               // from the centre of the upper axis to the nearest point of the element's axis segment
+        return dot(v, v) < C.probe_cull2c;
+    }
     const f3 v = d - Ksx * clampf(dot(d, Ksx), -C.probe_hl, C.probe_hl);
     return dot(v, v) < C.probe_cull2;
 }

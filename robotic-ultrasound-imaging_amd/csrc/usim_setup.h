@@ -6,6 +6,7 @@
 //     normal matrix; ModelTables);
 //   - the usim_config -> DevCfg translation with its derived probe and torso constants (translate_config).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -316,6 +317,12 @@ inline DevCfg translate_config(const usim_config& cfg) {
         C.probe_r2 = (float)cfg.probe_radius2; C.probe_h = (float)cfg.probe_height; C.probe_ca = (float)ca; C.probe_cb = (float)cb;
         C.probe_cah = C.probe_ca * C.probe_h;
         { const double cr = cfg.probe_radius + cfg.probe_height + cfg.probe_halfwidth + 0.025 + 0.0075 + 1e-4; C.probe_cull2 = (float)(cr * cr); }    // (sideways sweep: triangle inequality)
+        // element as a capsule, probe inside a ball of radius rp about the centre c of its upper axis: touching needs dist(c, element axis segment) <= rp + ELEM_R (DevCfg::probe_cull2c)
+        {
+            const double hh = std::hypot(cfg.probe_halflen, cfg.probe_halfwidth);
+            const double rp = std::max(std::hypot(hh, cfg.probe_height) + cfg.probe_radius, hh + cfg.probe_radius2), cr = rp + 0.0075 + 1e-4;
+            C.probe_cull2c = (float)(cr * cr);
+        }
         C.probe_deep0 = (float)(cfg.probe_radius * (2.0 / 3.0)); C.probe_inv_band = (float)(1.0 / (cfg.probe_radius * (0.96 - 2.0 / 3.0)));
     }
     {

@@ -252,15 +252,36 @@ constexpr int MB_OP = MB_POSE + 12;                   // op-space quantities: 6 
 constexpr int MB_W = MB_OP + 64;                      // contact wrench 6, contact count, overflow flag, shell ids 8 (between the steps of a resident launch: the new episode's parameters)
 constexpr int MB_Q = MB_W + 16;                       // broad-phase queue (element ids; the spare last word takes the non-candidates' stores)
 constexpr int MB_GOAL = MB_Q + 100;                   // `fixed` mode with physics substeps: the goal anchored at the policy step (12 words)
-constexpr int X2_STRIDE = MB_GOAL + 12;
+// DRAW_AHEAD (split kernel, resident launches of usim_rollout_random): the arm wave draws the NEXT pass's random action in its idle window between precompute() and
+// hand-off (3) and keeps the seven words in its own mailbox block (written and read by the same wave), so that the Philox rounds leave the chain behind hand-off (1).
+#ifndef USIM_DRAW_AHEAD
+#define USIM_DRAW_AHEAD 1
+#endif
+constexpr bool DRAW_AHEAD = USIM_DRAW_AHEAD != 0;
+// LIST_AHEAD (split kernel, 16-lane groups): the lattice wave applies the slot rule and forms ncmax and the contact elements before hand-off (2) (step16_one).
+// OFF: workgroup 0's timeline gains 400 ticks per step with it, the benchmark nothing (17.27 -> 17.32 us/step, profiles/handoff_balance/ab.txt)
+#ifndef USIM_LIST_AHEAD
+#define USIM_LIST_AHEAD 0
+#endif
+constexpr bool LIST_AHEAD = USIM_LIST_AHEAD != 0;
+constexpr int MB_ACT = MB_GOAL + 12;                  // DRAW_AHEAD: the action of the running control step / of the next one (7 words + 1)
+constexpr int X2_STRIDE = MB_ACT + (DRAW_AHEAD ? 8 : 0);
 template <int G> constexpr int x2_base() { return TB_WORDS + (64 * wpr<G>() / G) * GE_STRIDE; }
-static_assert(x2_base<16>() % 4 == 0 && x2_base<8>() % 4 == 0 && X2_STRIDE % 4 == 0 && MB_OP % 4 == 0 && MB_W % 4 == 0, "mailbox block: 16-byte accesses");
+static_assert(x2_base<16>() % 4 == 0 && x2_base<8>() % 4 == 0 && X2_STRIDE % 4 == 0 && MB_OP % 4 == 0 && MB_W % 4 == 0 && MB_ACT % 4 == 0, "mailbox block: 16-byte accesses");
 static_assert((x2_base<8>() + 32 * X2_STRIDE) * 4 <= 160 * 1024, "split kernel with 8-lane groups: LDS of a CU");
 // Collision in the split kernel: the ARM side, which has the site pose first, runs the broad phase (collide_cull) while the lattice side still stages its
 // right-hand side and solves, and leaves the survivors' ids (ascending) in the queue; after hand-off (1) the lattice side appends what the arm side left of the
 // broad phase and evaluates the whole queue (collide_queue), typically in one pass of its 16 lanes per environment.  (Giving the arm side a share of the narrow
 // phase measured slower for every share and both group sizes -- DESIGN.md section 4.6 -- and was removed.)
-template <int G> constexpr int arm_cull_rounds() { return 7; }   // broad-phase rounds the arm side runs before hand-off (1); the lattice side runs the rest after it.  16-lane groups, measured (us/step, one box): 0 -> 15.67, 2 -> 15.98, 4 -> 15.92, 7 (all) -> 15.48
+// (How the broad phase is divided is arm_cull_rounds: 8-lane groups as described; with 16-lane groups the lattice side now runs all of it after the hand-off.)
+// broad-phase rounds the arm side runs before hand-off (1); the lattice side runs the rest after it.  16-lane groups: NONE since the capsule-form cull -- the narrow phase
+// is one pass and the lattice wave has 2.3 k ticks to spare before hand-off (2), while the arm wave is the longer one on both sides of hand-off (1): kernel us/step, four
+// samples each, one box: 7 (all) -> 17.27, 5 -> 17.25, 3 -> 17.07, 0 -> 17.02 (parent 17.40; profiles/handoff_balance/ab.txt).  (With the ball-form cull, when the lattice
+// wave was the one waited for: 0 -> 15.67, 2 -> 15.98, 4 -> 15.92, 7 -> 15.48.)  8-lane groups: 7 of 13.
+#ifndef USIM_ARM_CULL16
+#define USIM_ARM_CULL16 0
+#endif
+template <int G> constexpr int arm_cull_rounds() { return G == 16 ? USIM_ARM_CULL16 : 7; }
 
 // workgroup barrier of the step kernels; the profiling build counts them per role (BARRIER INVARIANT at usim_step32_kernel)
 #if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
@@ -291,9 +312,11 @@ template <int TORSO, int ROLE, int G> constexpr int arm_lds_base() {
 static_assert((arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS) * 4 <= 160 * 1024 && arm_lds_base<1, 1, 8>() % 4 == 0 && arm_lds_base<1, 1, 16>() % 4 == 0 && arm_lds_base<1, 0, 16>() % 4 == 0
               && arm_lds_base<0, 0, 16>() % 4 == 0, "arm table behind the LDS blocks of every 16-lane kernel");
 
-template <int TORSO, int MODE, int ROLE, int NT, int G = 16, bool RES = false, class WR = NoWarm>
+// AHEAD (DRAW_AHEAD; arm side of the split kernel in resident launches that draw their actions): `more` = another pass of this launch follows this one
+template <int TORSO, int MODE, int ROLE, int NT, int G = 16, bool RES = false, class WR = NoWarm, bool AHEAD = false>
 DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __restrict__ st, const int n, const int npad, const DevIO& io, const int flags, const long long rstep,
-                   const bool first_pass, const int sub, int& nbar, Carry<TORSO ? (N_TOP + G - 1) / G : 1, WR>& cy) {
+                   const bool first_pass, const int sub, const bool more, int& nbar, Carry<TORSO ? (N_TOP + G - 1) / G : 1, WR>& cy) {
+    static_assert(!AHEAD || (ROLE == 1 && RES), "action drawn ahead: the arm wave of a resident split launch");
     // warm start of the contact solve (WR = WarmRec): the side that solves the contacts loads the lane's record of the kept list with the state, hands it to
     // contact_solve and stores the new one with the lattice; the side that restarts an episode clears the environment's warm rows
     constexpr bool WARM = !std::is_same<WR, NoWarm>::value;
@@ -485,6 +508,10 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             nq += __popc(gm);
         }
         group_sync();
+#if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
+        // profiling build: queue length of every environment of the first lattice wave of workgroup 0 (dbg[54 ..]; collide_queue makes max ceil(nq / G) passes over the wave)
+        if (dbg && blockIdx.x == 0 && wave == 0 && gl == 0) dbg[54 + ge] = 1ull + (unsigned long long)nq;
+#endif
         // narrow phase: the whole queue, against the element positions the arm side parked in the environment's block
         int nc = 0;
         collide_queue<G>(lds, mb + MB_Q, nq, &EB(GE_CG), gl, gbase, M, C, &EB(GE_S), dz, xs, sxc, sy, sz, nc);
@@ -497,27 +524,38 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         // (The early list lives in variables of its own and is adopted after the hand-off.  Forming it in nc / overflow / ncmax / cel directly, with the slot rule as
         //  one lambda called on either side of the barrier, reads better and cost the 8-lane multi-step kernel two more spilled registers, 8 B of scratch and 0.6 % of
         //  the 8192-environment step: DESIGN.md section 10.)
+        // LIST_AHEAD (16-lane groups; switched off, see the switch): with the capsule-form broad phase the queue is one pass and this wave reaches hand-off (2) ~2.3 k ticks
+        // before the arm wave: what of the list needs no Lambda^-1 / alpha / vs -- the slot rule, the wave's largest count, the contact elements -- can be formed in that slack;
+        // the rows stay behind the hand-off (contact_solve keeps its CLONE layout).  The count is uniform over a group, so the wave's maximum is that of the four groups'
+        // first lanes.
+        constexpr bool LIST_EARLY = EARLY || (G == 16 && LIST_AHEAD);
         int nc_early = nc, overflow_early = 0, ncmax_early = 0, cel_early[MAXC];
-        if constexpr (EARLY) {
+        if constexpr (LIST_EARLY) {
             contact_overflow<G>(lds, eb, gl, gbase, nc_early);
             if (nc_early > MAXC) { overflow_early = 1; nc_early = MAXC; }
             group_sync();
+            if constexpr (G == 16) {
+                const int m01 = max(__builtin_amdgcn_readlane(nc_early, 0), __builtin_amdgcn_readlane(nc_early, 16));
+                const int m23 = max(__builtin_amdgcn_readlane(nc_early, 32), __builtin_amdgcn_readlane(nc_early, 48));
+                ncmax_early = max(m01, m23);
+            } else {
 #pragma unroll
-            for (int k = MAXC; k >= 1; --k) if (ncmax_early == 0 && __any(nc_early >= k)) ncmax_early = k;
+                for (int k = MAXC; k >= 1; --k) if (ncmax_early == 0 && __any(nc_early >= k)) ncmax_early = k;
+            }
 #pragma unroll
             for (int k = 0; k < MAXC; ++k) cel_early[k] = (k < nc_early) ? __float_as_int(EB(GE_CG + k * CG_WORDS + 6)) : 0;
-            if (ncmax_early > 0) contact_rows<G>(lds, eb, gl, M, C, nc_early, cel_early, vz, P);
+            if constexpr (EARLY) { if (ncmax_early > 0) contact_rows<G>(lds, eb, gl, M, C, nc_early, cel_early, vz, P); }
         }
         RSTAMP(3);
         USIM_BAR();                                                 // (2) ... and Lambda^-1, alpha = J qs, vs = J qd
         RSTAMP(4);
-        if constexpr (!EARLY) contact_overflow<G>(lds, eb, gl, gbase, nc);
+        if constexpr (!LIST_EARLY) contact_overflow<G>(lds, eb, gl, gbase, nc);
         int overflow = 0;
         if (nc > MAXC) { overflow = 1; nc = MAXC; }
-        if constexpr (!EARLY) group_sync();
+        if constexpr (!LIST_EARLY) group_sync();
         XSTAMP(0);
         int ncmax = 0;
-        if constexpr (EARLY) { nc = nc_early; overflow = overflow_early; ncmax = ncmax_early; }
+        if constexpr (LIST_EARLY) { nc = nc_early; overflow = overflow_early; ncmax = ncmax_early; }
         else {
 #pragma unroll
             for (int k = MAXC; k >= 1; --k) if (ncmax == 0 && __any(nc >= k)) ncmax = k;
@@ -526,7 +564,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         float gf[MAXC], W[6] = {0, 0, 0, 0, 0, 0};
         int cel[MAXC];
 #pragma unroll
-        for (int k = 0; k < MAXC; ++k) { const int ek = __float_as_int(EB(GE_CG + k * CG_WORDS + 6)); gf[k] = 0.f; cel[k] = EARLY ? cel_early[k] : ((k < nc) ? ek : 0); }      // (read, then select: no branch per slot)
+        for (int k = 0; k < MAXC; ++k) { const int ek = __float_as_int(EB(GE_CG + k * CG_WORDS + 6)); gf[k] = 0.f; cel[k] = LIST_EARLY ? cel_early[k] : ((k < nc) ? ek : 0); }      // (read, then select: no branch per slot)
         if (ncmax > 0) {
             float alpha[6], vs[6], Lp[21];
 #pragma unroll
@@ -701,12 +739,11 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 
     // ---------------- action (replicated: seven words) ----------------
     float act[7] = {0, 0, 0, 0, 0, 0, 0};
-    if constexpr (MODE == 0) {
-    if constexpr (ROLE != 2) {
-    if (flags & LF_RANDOM_ACT) {
+    // the synthetic action of control step `cs` (usim_random_actions_kernel's stream)
+    auto draw_action = [&](const long long cs, float (&a7)[7]) {
         // the two counter blocks are evaluated side by side by the even and odd lanes of the group, then shared
         const uint32_t gid = (uint32_t)(C.env_offset + ei);
-        const u4 r = philox(gid, (uint32_t)rstep, (uint32_t)((unsigned long long)rstep >> 32), 1u + (uint32_t)(gl & 1), C.key0, C.key1);
+        const u4 r = philox(gid, (uint32_t)cs, (uint32_t)((unsigned long long)cs >> 32), 1u + (uint32_t)(gl & 1), C.key0, C.key1);
         const float ra = __uint_as_float(r.a), rb = __uint_as_float(r.b), rc = __uint_as_float(r.c), rd = __uint_as_float(r.d);
         uint32_t rr[7];
         rr[0] = __float_as_uint(rbc<G, 0>(ra)); rr[1] = __float_as_uint(rbc<G, 0>(rb)); rr[2] = __float_as_uint(rbc<G, 0>(rc)); rr[3] = __float_as_uint(rbc<G, 0>(rd));
@@ -716,12 +753,39 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         for (int a = 0; a < 7; ++a) {
             const float u = u01(rr[a]);
             const bool sgn = (C.mode == 1) || (C.mode == 3) || (C.mode == 2 && a == 6);
-            act[a] = sgn ? 2.f * u - 1.f : u;
-            if (C.mode == 3) act[a] *= WRENCH_MAX;
+            a7[a] = sgn ? 2.f * u - 1.f : u;
+            if (C.mode == 3) a7[a] *= WRENCH_MAX;
+        }
+    };
+    // AHEAD: the arm wave's own words of the mailbox block hold the action of the running control step (the same lanes write and read them)
+    auto keep_action = [&](const float (&a7)[7]) {
+        if (gl == 0) {
+            *reinterpret_cast<float4*>(&xl[MB_ACT]) = make_float4(a7[0], a7[1], a7[2], a7[3]);
+            *reinterpret_cast<float4*>(&xl[MB_ACT + 4]) = make_float4(a7[4], a7[5], a7[6], 0.f);
+        }
+    };
+    if constexpr (MODE == 0) {
+    if constexpr (ROLE != 2) {
+    if (flags & LF_RANDOM_ACT) {
+        if (AHEAD && !first_pass) {
+            // drawn during the previous pass of this launch (below, before hand-off (3)), or held over the physics substeps of a control step
+            const float4 a0 = *reinterpret_cast<const float4*>(&xl[MB_ACT]), a1 = *reinterpret_cast<const float4*>(&xl[MB_ACT + 4]);
+            act[0] = a0.x; act[1] = a0.y; act[2] = a0.z; act[3] = a0.w; act[4] = a1.x; act[5] = a1.y; act[6] = a1.z;
+        } else {
+            draw_action(rstep, act);
+            if constexpr (AHEAD) keep_action(act);                      // (for the later substeps of this control step)
         }
         if (io.act_out && store) {                                      // (one predicated region for the seven stores)
+            if constexpr (AHEAD) {
+                // adim is 6 or 7 (translate_config) and uniform: six plain stores and one scalar branch, not seven tests
+                float* const ao = io.act_out + (size_t)ei * C.adim;
 #pragma unroll
-            for (int a = 0; a < 7; ++a) if (a < C.adim) io.act_out[(size_t)ei * C.adim + a] = act[a];
+                for (int a = 0; a < 6; ++a) ao[a] = act[a];
+                if (C.adim > 6) ao[6] = act[6];
+            } else {
+#pragma unroll
+                for (int a = 0; a < 7; ++a) if (a < C.adim) io.act_out[(size_t)ei * C.adim + a] = act[a];
+            }
         }
     } else {
 #pragma unroll
@@ -973,6 +1037,15 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         USIM_BAR();                                                 // (2)
         RSTAMP(4);
         precompute();                                                    // ... while the lattice side solves the contacts
+        if constexpr (AHEAD) {
+            // ... and, in what is left of the wait, the action of the next control step (this pass completes one and another pass of the launch follows; after a
+            // substep that does not complete one the kept action stays).  Same counters and decoding as in place: every bit of `act` is what it was.
+            if ((flags & LF_RANDOM_ACT) && more && last_sub) {
+                float nxt[7];
+                draw_action(rstep + 1, nxt);
+                keep_action(nxt);
+            }
+        }
         RSTAMP(5);
         USIM_BAR();                                                 // (3) the lattice side has solved the contacts
         RSTAMP(6);
@@ -1270,7 +1343,9 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
     int sub = 0;
     long long cstep = rstep;                                             // control step: keys the in-kernel action draw
     for (int ks = 0; ks < nsub; ++ks) {
-        step16_one<TORSO, MODE, ROLE, NT, G, MULTI && MODE == 0, WR>(lds, M, C, st, n, npad, io, flags, cstep, ks == 0, sub, nbar, cy);
+        // (the launches of usim_rollout_actions -- ACTS -- never draw: they keep the code they had)
+        constexpr bool AHEAD = DRAW_AHEAD && ROLE == 1 && MULTI && MODE == 0 && !ACTS;
+        step16_one<TORSO, MODE, ROLE, NT, G, MULTI && MODE == 0, WR, AHEAD>(lds, M, C, st, n, npad, io, flags, cstep, ks == 0, sub, ks + 1 < nsub, nbar, cy);
         const bool ctrl_done = sub == S - 1;                             // this pass completed a control step
         if (ctrl_done) { sub = 0; ++cstep; } else ++sub;
         if (ks + 1 < nsub) {

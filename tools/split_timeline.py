@@ -2,8 +2,9 @@
 import importlib, os, subprocess, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
-PROF = ROOT / "robotic-ultrasound-imaging_amd" / "lib" / "libusim_prof.so"
-subprocess.run(["make", "-s", "-C", str(ROOT / "robotic-ultrasound-imaging_amd" / "csrc"), "prof"], check=True)
+PROF = Path(os.environ.get("USIM_PROF_LIB") or ROOT / "robotic-ultrasound-imaging_amd" / "lib" / "libusim_prof.so")      # USIM_PROF_LIB: another profiling build (the parent's, for a before / after)
+if not PROF.exists():
+    subprocess.run(["make", "-s", "-C", str(ROOT / "robotic-ultrasound-imaging_amd" / "csrc"), "prof"], check=True)
 os.environ["USIM_LIB"] = str(PROF)
 sys.path.insert(0, str(ROOT))
 import numpy as np, torch
@@ -13,7 +14,8 @@ nenv = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 lanes = int(sys.argv[3]) if len(sys.argv) > 3 else 32          # 32: 16-lane groups, 64: 8-lane groups
 env = usim.UltrasoundVecEnv(nenv, torso="soft", lanes_per_env=lanes, **usim.default_robosuite_kwargs())
 env.reset_tensor(); env.rollout_random(0, pre); torch.cuda.synchronize()
-rows = np.array([env.profile_step_raw(pre + k) for k in range(20 if pre < 100 else 50)], dtype=np.float64)
+count = int(sys.argv[4]) if len(sys.argv) > 4 else (20 if pre < 100 else 50)      # (0 100: the first 100 steps after the reset, where there is most contact)
+rows = np.array([env.profile_step_raw(pre + k) for k in range(count)], dtype=np.float64)
 print(f"stamps of steps {pre} .. {pre + len(rows) - 1} after the reset")
 t0 = rows[:, 20:21]
 names_a = ["start", "fk done", "barrier1 passed", "op-space + controller done", "barrier2 passed", "precompute done", "barrier3 passed (contacts solved)", "finish done", "barrier4 passed", "end"]
@@ -26,6 +28,17 @@ for base, names, title in ((20, names_a, "arm wave"), (30, names_b, "lattice wav
 print(f"   (contact_solve entered at {np.median(rows[:, 40] - t0[:, 0]):.0f}, left at {np.median(rows[:, 44] - t0[:, 0]):.0f}: median ticks since the step's start; ncmax of this quad varies)")
 for i, nm in enumerate(["contact list ready", "ncmax known", "before contact_solve", "after contact_solve"]):
     print(f"   x{i} {nm:32s} {np.median(rows[:, 50 + i] - t0[:, 0]):9.0f}")
+# broad-phase queue lengths of the environments of the first lattice wave of workgroup 0 (dbg[54 ..] = 1 + nq; a library built before they were recorded leaves zeros);
+# collide_queue walks the queue G elements at a time, uniformly over the wave: passes = max over the wave's environments of ceil(nq / G)
+G = 16 if lanes == 32 else 8
+nq = rows[:, 54:54 + 64 // G].astype(np.int64) - 1
+if (nq >= 0).all():
+    passes = ((nq + G - 1) // G).max(axis=1)
+    print(f"== broad-phase queue (groups of {G} lanes): nq per environment, passes of collide_queue per step")
+    print("   nq histogram     " + "  ".join(f"{v}:{c}" for v, c in zip(*np.unique(nq, return_counts=True))))
+    print(f"   nq median {np.median(nq):.0f}  max {nq.max()}   passes histogram " + "  ".join(f"{v}:{c}" for v, c in zip(*np.unique(passes, return_counts=True))))
+else:
+    print("== broad-phase queue: not recorded by this library")
 print("== contact solve of the lattice wave (ticks since its start)")
 c0 = rows[:, 40:41]
 for i, nm in enumerate(["start", "contact rows done", "Delassus blocks done", "sweeps done", "wrench done"]):

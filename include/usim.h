@@ -382,6 +382,56 @@ int usim_monitor_step(const usim_step_io* io, int n, int window, int horizon,
 int usim_explained_variance(const float* values_dev, const float* returns_dev,
                             int64_t count, float* out_dev, void* stream);
 
+/* ---- error metrics and episode records of evaluation runs on the device (csrc/usim_metrics.hip; evaluation.py DeviceEpisodeMetrics, EpisodeRecorder,
+ * evaluate_episodes).  The reference states its results as the thirteen numbers of src/utils/error.py:148-191 over the 24 CSV files that
+ * ultrasound.py:552-614 dumps per episode; the step kernels emit every channel of those files for every environment (io->log_dev, [n][53] float32).  Both entry
+ * points read io->log_dev and io->done_dev of the step just taken (both required; the other members are ignored) on the same stream, take no handle, allocate
+ * nothing, synchronise nothing and decide nothing on the host: each call is the same launches whatever the data, and records into a HIP graph.
+ *
+ * usim_metrics_step updates metrics_dev, a caller-owned device block of usim_metrics_words(n, window) 32-bit words, 16-byte aligned, that lives across calls.  An
+ * all-zero block is an empty one.  The block:
+ *     words 0 - 1      episodes    int64    episodes counted over the block's life
+ *     words 2 - 3      launches    int64    + 1 per call
+ *     words 4 - 5      length_sum  int64    sum of their lengths
+ *     words 6 - 7      nonfinite   int64    counted episodes with a metric that is not finite
+ *     words 8 - 33     total[13]     float64  per metric, the sum over the counted episodes whose thirteen metrics are all finite
+ *     words 34 - 59    total_sq[13]  float64  ... of their squares
+ *     words 60 - 63    zero
+ *     words 64 ..      the ring: `window` rows of USIM_METRICS_ROW_WORDS words {13 float64 metrics in the order of error_metrics.METRICS, environment index (int32),
+ *                      episode length (int32), the low 32 bits of `launches` as the call found it, three zero words}
+ *     words 64 + 32 window ..   the accumulators, float64 [n][13]
+ * Every call, for every environment i: acc[i][m] += term_m(row i of log_dev), the summands of error_metrics.step_terms in float64 on the float32 words widened first
+ * -- (a - b)^2 for x_pos (columns 0, 3), y_pos (1, 4), force (20, 21), mean_force (22, 21), der_force (23, 24), mean_velocity (10, 9); (sqrt(vx^2 + vy^2 + vz^2) -
+ * goal)^2 over columns 6 - 8 and 9 for velocity; the columns 19, 41, 42, 44, 45, 43 themselves for quat_diff and the pos / ori / force / der_force / vel rewards.
+ * Where done_dev[i] != 0 (any non-zero byte) the finished metrics are acc[i] / horizon (zero rows add nothing to the reference's means over `horizon` rows), the
+ * episode length is t + 1 with t = rint((double)row[40] * horizon / 100) (the time channel; episode_log.EpisodeLogger's rule), and acc[i] is zeroed -- counted or not.
+ * The environment is COUNTED by usim_monitor_step's rule: target_dev == NULL or count_dev[i] < target_dev[i], then count_dev[i]++ (int32 [n] each; a count array of
+ * this entry point's own, not the monitor's).  Counted environments are appended IN ASCENDING ENVIRONMENT INDEX: episode e, counted from 0 over the block's life, is
+ * ring row e mod window; a call that counts more than `window` stores only the last `window` of them.  total, total_sq and length_sum are added in that same order,
+ * one episode after the other.  A counted episode with a non-finite metric is stored in the ring as it is, adds 1 to nonfinite and nothing to total / total_sq.
+ * Two launches per call: the accumulation over a grid (coalesced reads of the record), then the ordered append in one workgroup.  No floating-point atomics, nothing
+ * ordered by arrival: the same block and the same inputs give the same block bit for bit.  USIM_ERR_INVALID before anything is enqueued: a NULL io, log_dev, done_dev
+ * or metrics_dev, a metrics_dev off the 16-byte grid, n <= 0, horizon <= 0, a window outside 1 .. USIM_MONITOR_MAX_WINDOW, target_dev without count_dev.
+ *
+ * usim_record_step keeps whole episodes of m chosen environments: record_dev is a caller-owned block of usim_record_words(m, episodes, horizon) 32-bit words, 16-byte
+ * aligned, all zero = empty:
+ *     filled[m] int32, lengths[m][episodes] int32, zero words up to a multiple of 4, then float32 rows[m][episodes][horizon][53]
+ * For tracked row r with e = env_index_dev[r] (int32 [m], distinct): while filled[r] < episodes, row e of log_dev is copied, as its bits, into
+ * rows[r][filled[r]][t], t by the rule above; where done_dev[e] != 0, lengths[r][filled[r]] = t + 1 and filled[r]++.  Rows an episode never reached stay zero, as
+ * the reference's np.zeros(horizon, ...) buffers do; after `episodes` episodes a row records nothing more.  e and t come from device memory and are checked by the
+ * kernel: an index outside [0, n) writes nothing at all, a t outside [0, horizon) copies no row.  One launch.  USIM_ERR_INVALID: a NULL io, log_dev, done_dev,
+ * env_index_dev or record_dev, a record_dev off the 16-byte grid, n, m, episodes or horizon <= 0. */
+#define USIM_METRICS               13   /* order of error_metrics.METRICS */
+#define USIM_METRICS_HEADER_WORDS  64
+#define USIM_METRICS_ROW_WORDS     32
+int usim_metrics_words(int n, int window);   /* 64 + 32*window + 26*n 32-bit words; < 0: error code */
+int usim_metrics_step(const usim_step_io* io, int n, int window, int horizon,
+                      const int32_t* target_dev, int32_t* count_dev,
+                      uint32_t* metrics_dev, void* stream);
+int usim_record_words(int m, int episodes, int horizon);  /* 4*ceil((m + m*episodes)/4) + m*episodes*horizon*53; < 0: error */
+int usim_record_step(const usim_step_io* io, int n, int horizon, const int32_t* env_index_dev,
+                     int m, int episodes, float* record_dev, void* stream);
+
 /* ---- a batched MPPI shooting planner: the sampler before usim_rollout_actions and the update after usim_score_block (csrc/usim_plan.hip; planner.py MPPIPlanner;
  * INTEGRATION.md section 4c).  `groups` = G controlled environments, `per_group` = K candidates each, n = G K simulated environments: environments [g K, (g + 1) K)
  * play the candidates of group g, and candidate k = 0 of every group is the unperturbed nominal.  Caller-owned float32 device buffers: the nominal mean [G][H][A]

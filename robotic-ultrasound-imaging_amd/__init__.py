@@ -11,8 +11,9 @@ from .config import default_robosuite_kwargs, load_yaml, make_config
 from .spaces import Box
 from .vec_env import UltrasoundEnv, UltrasoundVecEnv
 
-from . import episode_log, error_metrics, monitor, planner, policy, ppo  # noqa: E402  (checkpoint readers, on-device VecNormalize, MLP policy replay, MPPI planner, PPO learner, episode statistics + evaluation, CSV dump, error metrics)
+from . import episode_log, error_metrics, evaluation, monitor, planner, policy, ppo  # noqa: E402  (checkpoint readers, on-device VecNormalize, MLP policy replay, MPPI planner, PPO learner, episode statistics + evaluation, CSV dump, error metrics, their device-side evaluation runs)
 from .monitor import DeviceMonitor, evaluate_policy, write_scalar_csv  # noqa: E402
+from .evaluation import DeviceEpisodeMetrics, EpisodeRecorder, evaluate_episodes  # noqa: E402
 
 __all__ = ["UltrasoundVecEnv", "UltrasoundEnv", "Box", "default_robosuite_kwargs", "load_yaml", "make_config", "policy", "planner", "ppo", "monitor", "DeviceMonitor",
-           "evaluate_policy", "write_scalar_csv", "episode_log", "error_metrics", "_lib"]
+           "evaluate_policy", "write_scalar_csv", "episode_log", "error_metrics", "evaluation", "DeviceEpisodeMetrics", "EpisodeRecorder", "evaluate_episodes", "_lib"]

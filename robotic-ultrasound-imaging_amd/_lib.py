@@ -28,6 +28,9 @@ PACK_EPISODE_WORDS = 23            # USIM_PACK_EPISODE_WORDS: env index, ep_leng
 MONITOR_HEADER_WORDS = 16          # USIM_MONITOR_HEADER_WORDS: episodes, length_sum, return_sum, truncated, launches (64 bits each), six zero words
 MONITOR_ROW_WORDS = 4              # USIM_MONITOR_ROW_WORDS: ep_return bits, ep_length, environment index, launch number
 MONITOR_MAX_WINDOW = 1 << 20       # USIM_MONITOR_MAX_WINDOW
+METRICS = 13                       # USIM_METRICS: the metrics of error_metrics.METRICS, in that order
+METRICS_HEADER_WORDS = 64          # USIM_METRICS_HEADER_WORDS: episodes, launches, length_sum, nonfinite (64 bits each), total[13], total_sq[13] (float64), four zero words
+METRICS_ROW_WORDS = 32             # USIM_METRICS_ROW_WORDS: 13 float64 metrics, environment index, episode length, launch number, three zero words
 
 
 def monitor_words(window):
@@ -36,6 +39,30 @@ def monitor_words(window):
     if not 1 <= w <= MONITOR_MAX_WINDOW:
         raise ValueError(f"window must be 1 .. {MONITOR_MAX_WINDOW}, got {window!r}")
     return MONITOR_HEADER_WORDS + MONITOR_ROW_WORDS * w
+
+
+def metrics_words(n, window):
+    """usim_metrics_words(n, window): 32-bit words of the block usim_metrics_step keeps for n environments and a ring of `window` episodes"""
+    n_, w = int(n), int(window)
+    if n_ < 1:
+        raise ValueError(f"n must be at least 1, got {n!r}")
+    if not 1 <= w <= MONITOR_MAX_WINDOW:
+        raise ValueError(f"window must be 1 .. {MONITOR_MAX_WINDOW}, got {window!r}")
+    words = METRICS_HEADER_WORDS + METRICS_ROW_WORDS * w + 2 * METRICS * n_
+    if words > 2 ** 31 - 1:
+        raise ValueError(f"a metrics block for {n_} environments and a window of {w} is beyond 2^31 - 1 words")
+    return words
+
+
+def record_words(m, episodes, horizon):
+    """usim_record_words(m, episodes, horizon): 32-bit words of the block usim_record_step keeps for `episodes` episodes of m environments"""
+    m_, e, h = int(m), int(episodes), int(horizon)
+    if m_ < 1 or e < 1 or h < 1:
+        raise ValueError(f"m, episodes and horizon must be at least 1, got {m!r}, {episodes!r}, {horizon!r}")
+    words = (m_ + m_ * e + 3) // 4 * 4 + m_ * e * h * LOG_WIDTH
+    if words > 2 ** 31 - 1:
+        raise ValueError(f"a record block of {m_} x {e} episodes of {h} rows is beyond 2^31 - 1 words")
+    return words
 
 
 def pack_words(n):
@@ -140,6 +167,10 @@ SYMBOLS = {
     "usim_monitor_words": (C.c_int, [C.c_int]),
     "usim_monitor_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_explained_variance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "usim_metrics_words": (C.c_int, [C.c_int, C.c_int]),
+    "usim_metrics_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_record_words": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "usim_record_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "usim_plan_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_plan_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,

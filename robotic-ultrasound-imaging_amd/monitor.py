@@ -92,26 +92,21 @@ def eval_targets(n_eval_episodes, n_envs):
     return [(int(n_eval_episodes) + i) // int(n_envs) for i in range(int(n_envs))]
 
 
-def evaluate_policy(env, policy, vecnorm, n_eval_episodes=10, deterministic=True, seed=0, check_every=50, return_episode_rewards=False):
-    """stable_baselines3.common.evaluation.evaluate_policy (what EvalCallback and src/rl.py's `training: False` branch run) on the device: n_eval_episodes
-    complete episodes, environment i contributing its first (n_eval_episodes + i) // n_envs, their returns the raw Monitor returns.  The env is reset, then an
-    eager loop of FusedRollout.act(training=0: the statistics of `vecnorm` are frozen, never updated) and env.step_tensor runs with a fresh DeviceMonitor
-    (window = n_eval_episodes: the ring holds every counted episode) attached; the host reads the episode count every `check_every` steps and stops at
-    n_eval_episodes.  An episode cannot outlast env.horizon, so the loop is bounded by max(target) * env.horizon steps; RuntimeError if that bound is reached
-    short of the count.  A monitor that was attached before is attached again afterwards, its block untouched.
-    -> (mean, std) = np.mean / np.std of the episode returns in the order SB3 appends them (step by step, ascending environment index); with
-    return_episode_rewards=True (episode returns, episode lengths) as two lists instead."""
+def _evaluation_run(env, policy, vecnorm, mon, observers, n_eval, targets, deterministic, seed, check_every, what):
+    """The loop of evaluate_policy (and of evaluation.evaluate_episodes): reset, then FusedRollout.act(training=0) and env.step_tensor with `mon` and
+    `observers` attached -- and nothing else: the monitor and the observers that were attached before are taken off first and put back afterwards, in their
+    order, whatever happens -- until mon has counted n_eval episodes (read every `check_every` steps) or max(targets) * env.horizon steps have run
+    (RuntimeError).  -> mon.episodes()"""
     from .policy import DeviceRolloutBuffer, FusedRollout
-    n_eval, n = int(n_eval_episodes), env.num_envs
-    if n_eval < 1:
-        raise ValueError("n_eval_episodes must be at least 1")
-    targets = eval_targets(n_eval, n)
-    mon = DeviceMonitor(env, window=n_eval, targets=targets)
+    n = env.num_envs
     before = env.detach_monitor()                                   # (FusedRollout's constructor does not step, but nothing of this run may reach `before`)
+    others = env.detach_observer()
     try:
         fr = FusedRollout(env, policy, vecnorm, DeviceRolloutBuffer(1, n, _lib.OBS_DIM, env.action_dim, device=env.device), seed=seed, graph=False, init_stats=False)
         obs = env.reset_tensor()
         env.attach_monitor(mon)
+        for o in observers:
+            env.attach_observer(o)
         fr.pack()                                                   # the weights do not change inside the loop
         bound, every, got = max(targets) * int(env.horizon), max(1, int(check_every)), 0
         for k in range(bound):
@@ -122,12 +117,32 @@ def evaluate_policy(env, policy, vecnorm, n_eval_episodes=10, deterministic=True
                 if got >= n_eval:
                     break
         if got < n_eval:
-            raise RuntimeError(f"evaluate_policy: {got} of {n_eval} episodes after {bound} steps (max(target) x horizon)")
-        eps = mon.episodes()
+            raise RuntimeError(f"{what}: {got} of {n_eval} episodes after {bound} steps (max(target) x horizon)")
+        return mon.episodes()
     finally:
         env.detach_monitor()
+        env.detach_observer()
         if before is not None:
             env.attach_monitor(before)
+        for o in others:
+            env.attach_observer(o)
+
+
+def evaluate_policy(env, policy, vecnorm, n_eval_episodes=10, deterministic=True, seed=0, check_every=50, return_episode_rewards=False):
+    """stable_baselines3.common.evaluation.evaluate_policy (what EvalCallback and src/rl.py's `training: False` branch run) on the device: n_eval_episodes
+    complete episodes, environment i contributing its first (n_eval_episodes + i) // n_envs, their returns the raw Monitor returns.  The env is reset, then an
+    eager loop of FusedRollout.act(training=0: the statistics of `vecnorm` are frozen, never updated) and env.step_tensor runs with a fresh DeviceMonitor
+    (window = n_eval_episodes: the ring holds every counted episode) attached; the host reads the episode count every `check_every` steps and stops at
+    n_eval_episodes.  An episode cannot outlast env.horizon, so the loop is bounded by max(target) * env.horizon steps; RuntimeError if that bound is reached
+    short of the count.  A monitor that was attached before is attached again afterwards, its block untouched; so are the env's observers.
+    -> (mean, std) = np.mean / np.std of the episode returns in the order SB3 appends them (step by step, ascending environment index); with
+    return_episode_rewards=True (episode returns, episode lengths) as two lists instead."""
+    n_eval = int(n_eval_episodes)
+    if n_eval < 1:
+        raise ValueError("n_eval_episodes must be at least 1")
+    targets = eval_targets(n_eval, env.num_envs)
+    mon = DeviceMonitor(env, window=n_eval, targets=targets)
+    eps = _evaluation_run(env, policy, vecnorm, mon, (), n_eval, targets, deterministic, seed, check_every, "evaluate_policy")
     returns, lengths = [e["r"] for e in eps], [e["l"] for e in eps]
     if return_episode_rewards:
         return returns, lengths

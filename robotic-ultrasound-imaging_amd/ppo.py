@@ -8,6 +8,7 @@ so all of them keep working on the same memory.
     theta = flatten_parameters(policy)                     # BEFORE the collector is built: it records the parameters' addresses
     collector = FusedRollout(env, policy, vecnorm, buffer)
     ppo = NativePPO(env, policy, vecnorm, buffer, collector)
+    ppo.set_evaluation(1_000_000, eval_env)                # SB3's EvalCallback: eval/mean_reward and the error metrics in ppo.history (evaluation.evaluate_episodes)
     ppo.set_checkpointing(1_000_000); ppo.learn(40); ppo.save_checkpoint("trained_models", "tracking")
     ...
     ppo.load_checkpoint("trained_models", "tracking", reset_num_timesteps=False); ppo.learn(40)      # src/rl.py's continual training
@@ -21,6 +22,7 @@ import time
 import zipfile
 from pathlib import Path
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -237,6 +239,7 @@ class NativePPO:
         self._std = z(1)                                                      # train/std of the last update(): mean(exp(log_std))
         self.last_update = {}                                                 # the logger scalars of the last update() beyond its return value
         self.set_checkpointing(None)                                          # learn(): no periodic save until set_checkpointing(every, ...)
+        self.set_evaluation(None)                                             # learn(): no periodic evaluation until set_evaluation(every, eval_env, ...)
         self.history = []                                                     # learn(): one dict of logger scalars per iteration
         self.num_timesteps = 0                                                # environment steps collected by learn() so far
         self._work = z(int(self.lib.usim_ppo_work_floats(A)))
@@ -328,12 +331,44 @@ class NativePPO:
         self.checkpoint_every = None if checkpoint_every is None else int(checkpoint_every)
         self.checkpoint_dir, self.name_prefix = checkpoint_dir, str(name_prefix)
 
+    def set_evaluation(self, eval_every, eval_env=None, n_eval_episodes=10, deterministic=True):
+        """SB3's EvalCallback (imported at src/rl.py:16) for learn(): with eval_every set, in environment timesteps, learn() runs
+        evaluation.evaluate_episodes(eval_env, the live policy, the live vecnorm, n_eval_episodes, deterministic) after every iteration in which num_timesteps
+        reaches or passes a further multiple of it, and puts eval/mean_reward, eval/mean_ep_length and the thirteen eval/<metric> means into that iteration's
+        history row.  The statistics of vecnorm are frozen and only read during an evaluation (EvalCallback's sync_envs_normalization: the evaluation sees the
+        training statistics as they are).  eval_env must be an environment other than the training one -- an evaluation resets its env -- with the same
+        action_dim, on the same device: ValueError otherwise.  None, the state of a new learner: no evaluation, learn() behaves exactly as before."""
+        if eval_every is None:
+            self.eval_every, self.eval_env = None, None
+            return
+        if int(eval_every) < 1:
+            raise ValueError("eval_every must be None or at least 1 timestep")
+        if int(n_eval_episodes) < 1:
+            raise ValueError("n_eval_episodes must be at least 1")
+        if eval_env is None or eval_env is self.env:
+            raise ValueError("eval_env must be an environment other than the training one: an evaluation resets it")
+        if int(eval_env.action_dim) != self.act_dim or torch.device(eval_env.device) != torch.device(self.env.device):
+            raise ValueError(f"eval_env has action_dim {eval_env.action_dim} on {eval_env.device}, the training env {self.act_dim} on {self.env.device}")
+        self.eval_every, self.eval_env = int(eval_every), eval_env
+        self.n_eval_episodes, self.eval_deterministic = int(n_eval_episodes), bool(deterministic)
+
+    def evaluate(self):
+        """one evaluation as learn() runs it -> (the eval/* scalars of a history row, the result of evaluation.evaluate_episodes)"""
+        from .evaluation import evaluate_episodes
+        if self.eval_every is None:
+            raise ValueError("set_evaluation(eval_every, eval_env, ...) first")
+        res = evaluate_episodes(self.eval_env, self.policy, self.vecnorm, n_eval_episodes=self.n_eval_episodes, deterministic=self.eval_deterministic)
+        row = {"eval/mean_reward": res["mean"], "eval/mean_ep_length": float(np.mean(res["lengths"]))}
+        row.update({f"eval/{name}": float(np.mean(v)) for name, v in res["metrics"].items()})
+        return row, res
+
     def learn(self, iterations):
         """`iterations` x (collector.collect(), update()); -> the statistics of the last update.  Every iteration appends one dict to self.history -- SB3's logger
         scalars: time/total_timesteps (environment steps collected by learn() so far), time/wall (time.time()), the train/* statistics of update() and of
         self.last_update, train/learning_rate and, when the env has a monitor attached (env.attach_monitor, before the collector was built), its summary():
         rollout/ep_rew_mean, rollout/ep_len_mean, ... -- the series monitor.write_scalar_csv writes out.  After set_checkpointing(every, ...) it also writes
-        the periodic checkpoints; without, it behaves exactly as before."""
+        the periodic checkpoints, after set_evaluation(every, eval_env, ...) it also runs the periodic evaluations (eval/* scalars in the rows of those
+        iterations); without, it behaves exactly as before."""
         if self.collector is None:
             raise ValueError("learn() needs a collector")
         every, out = self.checkpoint_every, None
@@ -348,6 +383,8 @@ class NativePPO:
             mon = getattr(self.env, "monitor", None)
             if mon is not None:
                 row.update(mon.summary())
+            if self.eval_every is not None and self.num_timesteps // self.eval_every > before // self.eval_every:
+                row.update(self.evaluate()[0])
             self.history.append(row)
             if every is not None and self.num_timesteps // every > before // every:
                 self.save_checkpoint(self.checkpoint_dir, f"{self.name_prefix}_{self.num_timesteps}_steps")

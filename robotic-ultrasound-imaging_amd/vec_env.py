@@ -94,6 +94,7 @@ class UltrasoundVecEnv:
         self._pending = False
         self.horizon = int(self.cfg.horizon)
         self._episode_monitor = None                                  # monitor.DeviceMonitor fed by step_tensor (attach_monitor); not the boolean _monitor of the numpy path's infos
+        self._observers = []                                          # further consumers of a step fed by step_tensor (attach_observer), in attach order
 
     @property
     def env_offset(self):
@@ -170,6 +171,8 @@ class UltrasoundVecEnv:
         self._last_act = a           # keep the tensor alive until the kernel has run
         if self._episode_monitor is not None:
             self._episode_monitor.record()
+        for observer in self._observers:
+            observer.record()
         return self._obs, self._rew, self._done
 
     def attach_monitor(self, mon):
@@ -193,6 +196,36 @@ class UltrasoundVecEnv:
     def monitor(self):
         """the attached monitor.DeviceMonitor, or None"""
         return self._episode_monitor
+
+    def attach_observer(self, obj):
+        """Feed `obj` -- an evaluation.DeviceEpisodeMetrics or evaluation.EpisodeRecorder of this env, or anything with `.env` and a capture-safe `.record()` --
+        from now on: step_tensor calls obj.record() right after every usim_step, after the monitor's record() and after the observers attached earlier.  The rule
+        of attach_monitor holds: ATTACH BEFORE A COLLECTOR IS BUILT -- a recorded collector holds the launches that were enqueued while it was captured -- and
+        multi-step launches (rollout_random, rollout_actions) feed no observer.  With none attached the launches are exactly those of an env without the
+        feature.  Attaching an observer twice is refused.  Returns obj."""
+        if getattr(obj, "env", None) is not self:
+            raise ValueError("the observer was built for another environment")
+        if any(o is obj for o in self._observers):
+            raise ValueError("the observer is attached already")
+        self._observers.append(obj)
+        return obj
+
+    def detach_observer(self, obj=None):
+        """Stop feeding `obj` (it keeps what it holds) and return it; None: detach every observer and return them as a list, in attach order.  A collector
+        recorded while an observer was attached goes on feeding it."""
+        if obj is None:
+            out, self._observers = self._observers, []
+            return out
+        for k, o in enumerate(self._observers):
+            if o is obj:
+                del self._observers[k]
+                return obj
+        raise ValueError("the observer is not attached")
+
+    @property
+    def observers(self):
+        """the attached observers, in attach order (a tuple)"""
+        return tuple(self._observers)
 
     def refill_time(self):
         """(total device milliseconds, number) of the reset-bank refill launches issued so far (include/usim.h usim_refill_time)"""

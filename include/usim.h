@@ -624,6 +624,30 @@ int usim_ppo_adam(float* theta_dev, const float* grad_dev, float* m_dev, float* 
 int usim_ppo_adam_gated(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int params,
                         float lr, float beta1, float beta2, float eps, float max_grad_norm, float* stats_dev, int32_t* gate_dev, void* stream);
 
+/* ---- behaviour cloning (imitation.py NativeBC, DAggerTrainer): the supervised minibatch loss of the `imitation` package's BC on the same
+ * networks, as further instances of usim_ppo_grad's gradient kernel -- the same parameter order, the same workspace (usim_ppo_work_floats; one buffer may serve both
+ * calls in turn), the same four launches on `stream` and nothing else, the same fixed order of every sum, the same clamping of an index outside [0, rows).  The
+ * optimiser step is usim_ppo_adam.  Per row, with mean the action head's output and log-prob the DiagGaussianDistribution.log_prob of usim_ppo_grad:
+ *   policy term  USIM_BC_NLL: -log-prob(act | mean(obs), log_std)     (its gradient reaches mean and log_std)
+ *                USIM_BC_MSE: sum_a (mean_a - act_a)^2                (its gradient reaches mean only)
+ *   value term   (value - V(obs))^2, only with value_dev             entropy  sum log_std + A / 2 (1 + log 2 pi)
+ *   loss = mean(policy) + vf_coef mean(value) - ent_coef entropy
+ * Without a value term (value_dev NULL, or vf_coef == 0) the value network is not evaluated: every value-network word of grad_dev is +0.0f, value_loss is 0.
+ * stats_dev[USIM_PPO_STATS]: policy_loss, value_loss, entropy_loss (= -entropy), action_mse (mean over rows of sum_a (mean_a - act_a)^2, in both forms), the mean
+ * log-prob (in both forms), loss, the gradient's 2-norm, 0.
+ * USIM_ERR_INVALID before anything is enqueued: a NULL net (or a NULL parameter of it other than w2_packed), b, obs_dev, act_dev, work_dev, grad_dev or stats_dev,
+ * act_dim outside 1 .. 8, batch < 1, rows < 1, rows < batch without an index list, loss outside the two, a non-finite coefficient, work_dev off the 16-byte grid. ---- */
+#define USIM_BC_NLL 0
+#define USIM_BC_MSE 1
+typedef struct usim_bc_batch {
+    const float *obs_dev, *act_dev;            /* [rows][19] normalised observations, [rows][A] expert actions */
+    const float *value_dev;                    /* [rows] value targets, or NULL: no value term */
+    const int32_t* index_dev;                  /* as usim_ppo_batch */
+    int32_t rows, batch, act_dim, loss;        /* loss: USIM_BC_NLL | USIM_BC_MSE */
+    float ent_coef, vf_coef, reserved_[2];
+} usim_bc_batch;
+int usim_bc_grad(const usim_policy_net* net, const usim_bc_batch* b, float* work_dev, float* grad_dev, float* stats_dev, void* stream);
+
 const char* usim_strerror(int status);
 const char* usim_last_hip_error(const usim_handle* h);
 const char* usim_version(void);

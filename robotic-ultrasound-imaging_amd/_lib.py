@@ -19,6 +19,7 @@ POLICY_FUSED_ROW = 48              # doubles per row of usim_policy_fused.work_d
 PPO_STATS = 8                      # USIM_PPO_STATS
 PPO_WORKGROUPS = 128               # USIM_PPO_WORKGROUPS: gradient workgroups per network (tiles of 32 minibatch rows at this stride)
 PPO_GATE_WORDS = 4                 # USIM_PPO_GATE_WORDS: stop flag, gradient calls evaluated, optimizer steps applied, 0
+BC_NLL, BC_MSE = 0, 1              # USIM_BC_NLL, USIM_BC_MSE: the policy term of usim_bc_grad
 RESET_PARAMS = 13
 LOG_WIDTH = 53
 WARM_WORDS = 8 + 16 * 4            # USIM_WARM_WORDS
@@ -150,6 +151,12 @@ class UsimPpoBatch(C.Structure):
                [(n, C.c_void_p) for n in ("old_value_dev", "gate_dev")] + [(n, C.c_float) for n in ("clip_range_vf", "target_kl")]
 
 
+class UsimBcBatch(C.Structure):
+    """struct usim_bc_batch (include/usim.h): device pointers to normalised observations, expert actions and optional value targets + the minibatch's index list"""
+    _fields_ = [(n, C.c_void_p) for n in ("obs_dev", "act_dev", "value_dev", "index_dev")] + \
+               [(n, C.c_int32) for n in ("rows", "batch", "act_dim", "loss")] + [("ent_coef", C.c_float), ("vf_coef", C.c_float), ("reserved_", C.c_float * 2)]
+
+
 # every exported symbol of include/usim.h: name -> (restype, argtypes)
 SYMBOLS = {
     "usim_policy_step_fused": (C.c_int, [C.POINTER(UsimPolicyNet), C.POINTER(UsimNormStats), C.POINTER(UsimPolicyFused), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -178,6 +185,7 @@ SYMBOLS = {
     "usim_ppo_params": (C.c_int, [C.c_int]),
     "usim_ppo_work_floats": (C.c_int64, [C.c_int]),
     "usim_ppo_grad": (C.c_int, [C.POINTER(UsimPolicyNet), C.POINTER(UsimPpoBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_bc_grad": (C.c_int, [C.POINTER(UsimPolicyNet), C.POINTER(UsimBcBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_ppo_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_void_p, C.c_void_p]),
     "usim_ppo_adam_gated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,

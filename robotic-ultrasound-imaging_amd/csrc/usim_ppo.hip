@@ -18,6 +18,8 @@
 //
 // clip_range_vf (SB3's value clipping) is a second instance of the gradient kernel (template parameter VF): stage 3's value lanes clamp V around the row's old
 // value, one more LDS row.  A call without it launches the instance without it, whose value path is the one above, instruction for instruction.
+// Behaviour cloning (usim_bc_grad; imitation.py NativeBC) is two more instances (template parameter LOSS): the supervised loss of the `imitation` package's BC in
+// stage 3, fewer loads in stage 0, everything else -- the workspace, prep, reduce, finish, usim_ppo_adam -- shared as it is.
 // The gate (target_kl's early stop, taken on the device; include/usim.h states the words): every kernel of both calls reads the stop flag on entry -- one word, the
 // same for every thread, in front of every barrier -- and returns when it is set.  Thread 0 of finish counts the call and, last thing, sets the flag from the
 // float32 approx_kl it has just written; the one-thread count kernel counts the step.  Plain stores by single threads of single-workgroup kernels; no atomics.
@@ -47,6 +49,7 @@ constexpr int PP_LOADS = 8;                                      // loads a thre
 constexpr int PP_BODY = PP_H1 * PP_OBS + PP_H1 + PP_H2 * PP_H1 + PP_H2;      // w1 b1 w2 b2 of one network: 38016
 constexpr int PP_W2 = PP_H2 * PP_H1;                             // one layer-2 matrix
 constexpr float LOG_SQRT_2PI_F = 0.9189385332046727f;
+constexpr int PP_PPO = 0, PP_BC_NLL = 1 + USIM_BC_NLL, PP_BC_MSE = 1 + USIM_BC_MSE;      // the loss of a gradient-kernel instance (stage 0 and stage 3)
 
 // offsets of one network's fields in the flat block (include/usim.h: pi_w1 pi_b1 pi_w2 pi_b2 act_w act_b vf_w1 vf_b1 vf_w2 vf_b2 val_w val_b log_std)
 struct PpoLayout { int w1, b1, w2, b2, wh, bh; };
@@ -131,7 +134,13 @@ __global__ __launch_bounds__(PP_RED) void usim_ppo_prep_kernel(const float* __re
 
 // VF: clip_range_vf > 0.  The value clip is compiled into an instance of its own, so that the kernel of a call without it is the one it was before the clip existed
 // (the branch in the shared body changed the register allocation of the whole kernel: profiles/ppo/resource_usage_gate.txt)
-template <bool VF>
+//
+// LOSS: PP_PPO, or one of the two behaviour-cloning forms of usim_bc_grad (imitation.py NativeBC): the row's policy term is -log-prob(act) (PP_BC_NLL) or
+// sum_a (mean_a - act_a)^2 (PP_BC_MSE), the value term regresses V on the row's target, there is no old log-prob, advantage or clip.  Only what a tile loads
+// (stage 0) and the heads' loss (stage 3) differ, each behind `if constexpr`, so the PPO instances are compiled from the statements they were compiled from.  A
+// behaviour-cloning call without value targets gives the value network's workgroups no tile: they write zeros.  b.ret carries the value targets (NULL: none), the
+// float64 sums of approx_kl and clip_fraction carry the rows' squared action error and log-prob.
+template <bool VF, int LOSS = PP_PPO>
 __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch b, float* __restrict__ work) {
     __shared__ __attribute__((aligned(16))) float xs[PP_TM][PP_XS];          // the tile's observations, column 19 zero
     __shared__ __attribute__((aligned(16))) float h1[PP_TM][PP_H1S];         // layer-1 activations; from the end of stage 6 the layer-1 deltas
@@ -169,7 +178,7 @@ __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch
     for (int i = 0; i < 10; ++i) aw1[i] = 0.f;
     double s_pl = 0.0, s_kl = 0.0, s_cf = 0.0, s_vl = 0.0;        // loss sums of the rows this thread speaks for (tid < 256, tid % 8 == 0)
 
-    const int ntiles = (B + PP_TM - 1) / PP_TM;
+    const int ntiles = (LOSS != PP_PPO && net == 1 && !b.ret) ? 0 : (B + PP_TM - 1) / PP_TM;
     for (int tile = blockIdx.x; tile < ntiles; tile += PP_W) {
         const int row0 = tile * PP_TM;
         // ---- stage 0: the tile's samples (rows past the batch: zeros, and no gradient below) ----
@@ -184,10 +193,14 @@ __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch
             const int r = tid - 256;
             const bool valid = row0 + r < B;
             const size_t src = valid ? pp_row(b, row0 + r) : 0;
-            r_old[r] = valid ? b.old_logp[src] : 0.f;
-            r_adv[r] = valid ? (float)(((double)b.adv[src] - adv_mean) * adv_inv) : 0.f;
-            r_ret[r] = valid ? b.ret[src] : 0.f;
-            if constexpr (VF) r_oldv[r] = valid ? b.oldv[src] : 0.f;
+            if constexpr (LOSS == PP_PPO) {
+                r_old[r] = valid ? b.old_logp[src] : 0.f;
+                r_adv[r] = valid ? (float)(((double)b.adv[src] - adv_mean) * adv_inv) : 0.f;
+                r_ret[r] = valid ? b.ret[src] : 0.f;
+                if constexpr (VF) r_oldv[r] = valid ? b.oldv[src] : 0.f;
+            } else {
+                r_ret[r] = (valid && b.ret) ? b.ret[src] : 0.f;   // the value target (read by the value network's workgroups only)
+            }
         }
         __syncthreads();
         // ---- stage 1: layer 1 (19 -> 256, tanh) ----
@@ -241,7 +254,37 @@ __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch
                     out = fmaf(h.x, w.x, out); out = fmaf(h.y, w.y, out); out = fmaf(h.z, w.z, out); out = fmaf(h.w, w.w, out);
                 }
             }
-            if (net == 0) {
+            if constexpr (LOSS != PP_PPO) {
+                if (net == 0) {
+                    // behaviour cloning: d = act - mean; log-prob as below; the row's squared action error sum_a d^2.  d loss / d log-prob = -1 / batch
+                    // (PP_BC_NLL: the gradient reaches the mean, y / sigma, and log_std, y^2 - 1); d loss / d mean = -2 d / batch (PP_BC_MSE: the mean only)
+                    const bool is_act = a < A;
+                    const float ls = is_act ? N.log_std[a] : 0.f, inv_s = expf(-ls);
+                    const float d = acts[r][a] - out, y = d * inv_s;
+                    float lp = is_act ? fmaf(-0.5f * y, y, -ls - LOG_SQRT_2PI_F) : 0.f;
+                    float sq = is_act ? d * d : 0.f;
+                    lp += __shfl_xor(lp, 1); lp += __shfl_xor(lp, 2); lp += __shfl_xor(lp, 4);
+                    sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4);
+                    if constexpr (LOSS == PP_BC_NLL) {
+                        const float g = valid ? -b.inv_b : 0.f;
+                        dout[r][a] = is_act ? (g * y) * inv_s : 0.f;
+                        dls[r][a] = is_act ? g * fmaf(y, y, -1.f) : 0.f;
+                    } else {
+                        dout[r][a] = (is_act && valid) ? (-2.f * b.inv_b) * d : 0.f;
+                        dls[r][a] = 0.f;
+                    }
+                    if (a == 0 && valid) {
+                        s_pl += LOSS == PP_BC_NLL ? -(double)lp : (double)sq;
+                        s_kl += (double)sq;
+                        s_cf += (double)lp;
+                    }
+                } else {
+                    const float d = out - r_ret[r];
+                    dout[r][a] = (a == 0 && valid) ? b.vf2 * d : 0.f;
+                    dls[r][a] = 0.f;
+                    if (a == 0 && valid) s_vl += (double)(d * d);
+                }
+            } else if (net == 0) {
                 const bool is_act = a < A;
                 const float ls = is_act ? N.log_std[a] : 0.f, inv_s = expf(-ls);
                 const float y = (acts[r][a] - out) * inv_s;
@@ -492,6 +535,36 @@ extern "C" int usim_ppo_grad(const usim_policy_net* net, const usim_ppo_batch* b
     hipLaunchKernelGGL(usim_ppo_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, work_dev, P, A, b->ent_coef, grad_dev, b->gate_dev);
     hipLaunchKernelGGL(usim_ppo_finish_kernel, dim3(1), dim3(PP_RED), 0, s, work_dev, grad_dev, net->log_std, P, A, b->batch, b->vf_coef, b->ent_coef, stats_dev,
                        b->gate_dev, b->target_kl);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+// usim_bc_grad: usim_ppo_grad's four launches with a behaviour-cloning instance of the gradient kernel in the second.  prep copies both W2 matrices and takes its
+// identity path for the advantages (none are read); reduce and finish are the ones above without a gate: their sums 3 and 4 are the rows' action error and log-prob
+extern "C" int usim_bc_grad(const usim_policy_net* net, const usim_bc_batch* b, float* work_dev, float* grad_dev, float* stats_dev, void* stream) {
+    using namespace usim;
+    if (!net || !b || !work_dev || !grad_dev || !stats_dev || (reinterpret_cast<uintptr_t>(work_dev) & 15)) return USIM_ERR_INVALID;
+    if (!net->pi_w1 || !net->pi_b1 || !net->pi_w2 || !net->pi_b2 || !net->act_w || !net->act_b || !net->vf_w1 || !net->vf_b1 || !net->vf_w2 || !net->vf_b2 ||
+        !net->val_w || !net->val_b || !net->log_std) return USIM_ERR_INVALID;
+    if (!b->obs_dev || !b->act_dev) return USIM_ERR_INVALID;
+    if (b->act_dim < 1 || b->act_dim > PP_MAXA || b->batch < 1 || b->rows < 1 || (!b->index_dev && b->rows < b->batch)) return USIM_ERR_INVALID;
+    if (b->batch > INT32_MAX - PP_LOADS * PP_RED) return USIM_ERR_INVALID;
+    if (b->loss != USIM_BC_NLL && b->loss != USIM_BC_MSE) return USIM_ERR_INVALID;
+    if (!isfinite(b->ent_coef) || !isfinite(b->vf_coef)) return USIM_ERR_INVALID;
+    const int A = b->act_dim, P = ppo_params(A);
+    const bool valued = b->value_dev && b->vf_coef != 0.f;         // no value term: the value network is not evaluated, its gradient words are +0
+    const float vf_coef = valued ? b->vf_coef : 0.f;
+    const PpoNet N{{net->pi_w1, net->vf_w1}, {net->pi_b1, net->vf_b1}, {net->pi_w2, net->vf_w2}, {net->pi_b2, net->vf_b2}, {net->act_w, net->val_w},
+                   {net->act_b, net->val_b}, net->log_std};
+    const PpoBatch K{b->obs_dev, b->act_dev, nullptr, nullptr, valued ? b->value_dev : nullptr, b->index_dev, b->rows, b->batch, A, 0,
+                     0.f, (float)(1.0 / b->batch), (float)(2.0 * (double)vf_coef / b->batch), nullptr, 0.f, nullptr};
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(usim_ppo_prep_kernel, dim3(1 + 2 * PP_W2 / PP_RED), dim3(PP_RED), 0, s, net->pi_w2, net->vf_w2, K, work_dev + ppo_off_pack(A),
+                       reinterpret_cast<double*>(work_dev + ppo_off_adv(A)));
+    if (b->loss == USIM_BC_NLL) hipLaunchKernelGGL((usim_ppo_grad_kernel<false, PP_BC_NLL>), dim3(PP_W, 2), dim3(PP_WG), 0, s, N, K, work_dev);
+    else hipLaunchKernelGGL((usim_ppo_grad_kernel<false, PP_BC_MSE>), dim3(PP_W, 2), dim3(PP_WG), 0, s, N, K, work_dev);
+    hipLaunchKernelGGL(usim_ppo_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, work_dev, P, A, b->ent_coef, grad_dev, nullptr);
+    hipLaunchKernelGGL(usim_ppo_finish_kernel, dim3(1), dim3(PP_RED), 0, s, work_dev, grad_dev, net->log_std, P, A, b->batch, vf_coef, b->ent_coef, stats_dev,
+                       nullptr, 0.f);
     return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
 }
 

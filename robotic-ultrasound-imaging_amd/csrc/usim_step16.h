@@ -264,6 +264,26 @@ constexpr bool DRAW_AHEAD = USIM_DRAW_AHEAD != 0;
 #define USIM_LIST_AHEAD 0
 #endif
 constexpr bool LIST_AHEAD = USIM_LIST_AHEAD != 0;
+// LATTICE_AHEAD (split kernel, 16-lane groups, resident launches): lattice_rhs and lattice_solve need nothing from the arm side but "this episode ended", which happens once
+// per episode.  The lattice wave therefore goes straight from integrating pass k into the right-hand side and the solve of pass k + 1 on the state in its registers and
+// meets the arm wave only at hand-off (1) of pass k + 1; hand-off (4) and the barrier between the passes exist on the last pass of a launch only.  After hand-off (1) it
+// reads the arm wave's new-episode word; if an environment of the wave has one it adopts it and runs the two phases again for the wave (same instructions on the same
+// inputs for the environments that went on: same bits).  The lattice wave then owns EB(GE_S) and carries kst / kdmp / mu / t, the lattice and the warm record between the
+// passes.  The hand-offs and what each hazard rests on: BARRIER INVARIANT at usim_step32_kernel.
+#ifndef USIM_LATTICE_AHEAD
+#define USIM_LATTICE_AHEAD 1
+#endif
+constexpr bool LATTICE_AHEAD = USIM_LATTICE_AHEAD != 0;
+// LATTICE_PRIO (with LATTICE_AHEAD): the two waves of a pair share the VALU issue of their SIMD, the older one -- the arm wave -- first.  With LATTICE_AHEAD the lattice wave is
+// the longer one from hand-off (2) to hand-off (1) of the next pass (contact solve, integration, right-hand side, solve) and runs its right-hand side beside the arm wave's
+// finish, where it got the slots the arm wave left: 6.2 k ticks for the two phases against 4.9 k beside an idle partner, and the step gained 0.7 % instead of 4 %.  The
+// lattice wave therefore raises its priority (s_setprio 1) from hand-off (2) to hand-off (1) and drops it between (1) and (2), where the arm wave is the longer one.
+// One box, kernel us/step at 4096 envs, four samples each (profiles/lattice_ahead/ab.txt): parent 17.00, no priority 16.85, this window 16.58; raised for the whole pass
+// 17.27 (the arm wave's op-space phase 5.7 k -> 7.2 k ticks), from (2) to (3) only 16.63, from (2) to the end of the integration 16.75, from (2) to the right-hand side 16.75.
+#ifndef USIM_LATTICE_PRIO
+#define USIM_LATTICE_PRIO 1
+#endif
+constexpr bool LATTICE_PRIO = USIM_LATTICE_PRIO != 0;
 constexpr int MB_ACT = MB_GOAL + 12;                  // DRAW_AHEAD: the action of the running control step / of the next one (7 words + 1)
 constexpr int X2_STRIDE = MB_ACT + (DRAW_AHEAD ? 8 : 0);
 template <int G> constexpr int x2_base() { return TB_WORDS + (64 * wpr<G>() / G) * GE_STRIDE; }
@@ -282,6 +302,8 @@ static_assert((x2_base<8>() + 32 * X2_STRIDE) * 4 <= 160 * 1024, "split kernel w
 #define USIM_ARM_CULL16 0
 #endif
 template <int G> constexpr int arm_cull_rounds() { return G == 16 ? USIM_ARM_CULL16 : 7; }
+static_assert(!LATTICE_AHEAD || USIM_ARM_CULL16 == 0, "LATTICE_AHEAD: the arm wave must not need the integrated element positions (no broad-phase rounds on its side)");
+template <int ROLE, int G, bool RES> constexpr bool lattice_ahead() { return LATTICE_AHEAD && ROLE != 0 && G == 16 && RES; }
 
 // workgroup barrier of the step kernels; the profiling build counts them per role (BARRIER INVARIANT at usim_step32_kernel)
 #if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
@@ -333,7 +355,9 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & (WPR - 1);      // wave within its role = quad of environments
     // resident state (see Carry): everywhere but on the lattice side of the split kernel with 16-lane groups, where it measured slower (one box,
     // us/step at 4096 envs: neither side 15.00, arm side only 14.78, both 15.28, lattice side only 15.60; 8-lane groups at 8192 envs: 23.10 / 22.73 / 22.67)
-    constexpr bool RES_HERE = RES && !(ROLE == 2 && G == 16);
+    // (LATTICE_AHEAD makes the lattice side resident too: it no longer waits for the arm side's stores between the passes, which is what the reload was for)
+    constexpr bool LA = lattice_ahead<ROLE, G, RES>();
+    constexpr bool RES_HERE = RES && (LA || !(ROLE == 2 && G == 16));
     const bool fresh = !RES_HERE || first_pass;                         // the state comes from HBM (first step of a launch; every single-step launch)
     const int gl = lane & (G - 1), ge = lane / G;
     const int gbase = lane - gl;
@@ -426,16 +450,17 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             const int e = gl + i * G;
             s_pre[i] = 0.f; sd_pre[i] = 0.f;
             if (TORSO && MODE == 0 && ROLE != 1 && e < N_TOP) { s_pre[i] = LAT(LAT_S + e); sd_pre[i] = LAT(LAT_SD + e); }
-            if (TORSO && MODE == 0 && ROLE == 1 && e < N_TOP) s_pre[i] = LAT(LAT_S + e);      // the arm side runs the broad phase of the collision
+            if (TORSO && MODE == 0 && ROLE == 1 && !LA && e < N_TOP) s_pre[i] = LAT(LAT_S + e);      // the arm side runs the broad phase of the collision (LA: none of it, and the lattice side parks the positions)
         }
         if constexpr (WARM && MODE == 0 && ROLE != 1) warm_load(warm_rows, gl, cy.wr);
-    } else if constexpr (RES && ROLE == 1) {
+    } else if constexpr (RES && ROLE == 1 && !LA) {
         // resident launch, arm side: the element positions the lattice side integrated (or the zeros this side left for a new episode) are in
         // the environment's LDS block
 #pragma unroll
         for (int i = 0; i < NE; ++i) { const int e = gl + i * G; s_pre[i] = (e < N_TOP) ? EB(GE_S + e) : 0.f; }
-    } else if constexpr (RES && ROLE == 2) {
+    } else if constexpr (RES && ROLE == 2 && !LA) {
         // resident launch, lattice side: the arm side reports a new episode (lattice at rest, its parameters, t = 0) through the mailbox
+        // (LA: read behind hand-off (1), below)
         const float4 nx = *reinterpret_cast<const float4*>(&lds[mbo + MB_W]);
         if (nx.w != 0.f) {
             kst = nx.x; kdmp = nx.y; mu = nx.z; t = 0;
@@ -480,10 +505,20 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     if constexpr (ROLE == 2) {
         // ================= lattice / contact side of the split kernel =================
         RSTAMP(0);
+        if constexpr (LA && LATTICE_PRIO) __builtin_amdgcn_s_setprio(1);        // (first pass; later ones come here with it raised)
         float* const mb = &lds[mbo];
         const int* tb_shell = reinterpret_cast<const int*>(lds + TB_SHELL);
         float dz, vz, az;
         torso_motion(C, tphys, dz, vz, az);
+        if constexpr (LA) {
+            // this side owns EB(GE_S): from the state it loaded (first pass), from every integration, and zeros when it adopts a new episode
+            if (first_pass) {
+#pragma unroll
+                for (int i = 0; i < NE; ++i) { const int e = gl + i * G; if (e < N_TOP) EB(GE_S + e) = s_pre[i]; }
+            }
+        }
+        // (LA, not the first pass: this wave comes here straight from integrating the previous pass -- the arm wave may still be in its finish -- and assumes that no
+        //  episode of the wave ended)
         lattice_rhs<G, NE>(lds, eb, gl, M, az, kst, kdmp, true, s_pre, sd_pre);
         // The matrix-core solve a~ = Linv rhs needs nothing from the arm side: it runs here, where this wave used to wait for the site pose (hand-off (1)
         // comes when the arm side has finished its kinematics and the broad phase), and leaves only the narrow phase for after the hand-off: one box,
@@ -494,6 +529,27 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         RSTAMP(1);
         USIM_BAR();                                                 // (1) the arm side has published the site pose
         RSTAMP(2);
+        if constexpr (LA && LATTICE_PRIO) __builtin_amdgcn_s_setprio(0);
+        if constexpr (LA) {
+            if (!first_pass) {
+                // the arm side's word of the previous pass (written behind its reads of the wrench, read here before this pass's wrench is written): a new episode starts
+                // with the lattice at rest, its own parameters and t = 0 -- adopt it (t advances as at the top of the pass: once) and run the two phases again
+                const float4 nx = *reinterpret_cast<const float4*>(&mb[MB_W]);
+                const bool began = nx.w != 0.f;
+                if (__any(began)) {
+                    if (began) {
+                        kst = nx.x; kdmp = nx.y; mu = nx.z; t = 0;
+                        if (sub == 0) t += 1;
+#pragma unroll
+                        for (int i = 0; i < NE; ++i) { const int e = gl + i * G; s_pre[i] = 0.f; sd_pre[i] = 0.f; if (e < N_TOP) EB(GE_S + e) = 0.f; }
+                        warm_clear(cy.wr);                                   // an episode starts cold
+                    }
+                    torso_motion(C, (t - 1) * C.substeps + sub, dz, vz, az);
+                    lattice_rhs<G, NE>(lds, eb, gl, M, az, kst, kdmp, true, s_pre, sd_pre);
+                    lattice_solve<G>(lds, eb, gl, gbase);
+                }
+            }
+        }
         const f3 xs = mk(mb[MB_POSE], mb[MB_POSE + 1], mb[MB_POSE + 2]), sy = mk(mb[MB_POSE + 3], mb[MB_POSE + 4], mb[MB_POSE + 5]),
                  sz = mk(mb[MB_POSE + 6], mb[MB_POSE + 7], mb[MB_POSE + 8]);
         const f3 sxc = cross(sy, sz);
@@ -549,6 +605,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         RSTAMP(3);
         USIM_BAR();                                                 // (2) ... and Lambda^-1, alpha = J qs, vs = J qd
         RSTAMP(4);
+        if constexpr (LA && LATTICE_PRIO) __builtin_amdgcn_s_setprio(1);
         if constexpr (!LIST_EARLY) contact_overflow<G>(lds, eb, gl, gbase, nc);
         int overflow = 0;
         if (nc > MAXC) { overflow = 1; nc = MAXC; }
@@ -586,6 +643,9 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         RSTAMP(5);
         USIM_BAR();                                                 // (3) contact wrench and contact list published
         RSTAMP(6);
+#if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
+        if (more && dbg && blockIdx.x == 0 && (threadIdx.x & (64 * WPR - 1)) == 0) dbg[62] = __builtin_readcyclecounter();      // hand-off (3) of the pass before the last one
+#endif
         {
             float acc_e[NE];
 #pragma unroll
@@ -611,7 +671,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             if constexpr (WARM) { if (valid) warm_store(warm_rows, gl, cy.wr); }
         }
         RSTAMP(7);
-        USIM_BAR();                                                 // (4) lattice stored: the arm side may now zero it for an episode that ended
+        if (!LA || !more) USIM_BAR();                               // (4) lattice stored: the arm side may now zero it for an episode that ended (LA: last pass of a launch only)
         RSTAMP(8);
         return;
     }
@@ -719,7 +779,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
                 const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
-                if (eraw < N_TOP) EB(GE_S + eraw) = s_pre[i];
+                if (!LA && eraw < N_TOP) EB(GE_S + eraw) = s_pre[i];          // (LA: the lattice side owns the area)
                 if (i >= arm_cull_rounds<G>()) continue;
                 const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz_, xs, sxc, sz);
                 const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & GMASK;
@@ -1049,6 +1109,9 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         RSTAMP(5);
         USIM_BAR();                                                 // (3) the lattice side has solved the contacts
         RSTAMP(6);
+#if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
+        if (more && dbg && blockIdx.x == 0 && (threadIdx.x & (64 * WPR - 1)) == 0) dbg[63] = __builtin_readcyclecounter();      // hand-off (3) of the pass before the last one
+#endif
         const float4 w0 = *reinterpret_cast<const float4*>(&xl[MB_W]), w1 = *reinterpret_cast<const float4*>(&xl[MB_W + 4]);
         W[0] = w0.x; W[1] = w0.y; W[2] = w0.z; W[3] = w0.w; W[4] = w1.x; W[5] = w1.y;
         ncon = __float_as_int(w1.z); overflow = __float_as_int(w1.w);
@@ -1261,7 +1324,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         }
     }
 
-    if constexpr (ROLE == 1) { RSTAMP(7); USIM_BAR(); RSTAMP(8); }   // (4) the lattice side has stored the integrated lattice
+    if constexpr (ROLE == 1) { RSTAMP(7); if (!LA || !more) USIM_BAR(); RSTAMP(8); }   // (4) the lattice side has stored the integrated lattice (LA: last pass of a launch only)
     if (MODE == 0 && need) {
         // ================= auto-reset: adopt the initial state prepared in the reset bank and queue the slot for refill =================
         episode += 1;
@@ -1274,11 +1337,14 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 #pragma unroll
             for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = BK(sl, BOBS + a);
         }
-        if (TORSO && valid) for (int e = gl; e < N_TOP; e += G) { LAT(LAT_S + e) = 0.f; LAT(LAT_SD + e) = 0.f; }
+        // (LA, another pass follows: no hand-off (4), the lattice side may still be storing -- its next integration and warm_store write every one of these words
+        //  from the registers and the record it cleared when it adopted the episode)
+        const bool zero_here = !LA || !more;
+        if (TORSO && valid && zero_here) for (int e = gl; e < N_TOP; e += G) { LAT(LAT_S + e) = 0.f; LAT(LAT_SD + e) = 0.f; }
         if constexpr (WARM) {
             // an episode starts cold: the warm rows (after hand-off (4) in the split kernel: the lattice side has stored this step's list) and, where this wave
             // solves the contacts itself, its record (the lattice side of a resident launch learns of the new episode through the mailbox)
-            if (valid) warm_rows_clear<G>(warm_rows, gl);
+            if (valid && zero_here) warm_rows_clear<G>(warm_rows, gl);
             warm_clear(cy.wr);
         }
         if constexpr (RES && TORSO != 0) {
@@ -1287,13 +1353,14 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
                 s_pre[i] = 0.f; sd_pre[i] = 0.f;
-                if (ROLE == 1 && gl + i * G < N_TOP) EB(GE_S + gl + i * G) = 0.f;
+                if (ROLE == 1 && !LA && gl + i * G < N_TOP) EB(GE_S + gl + i * G) = 0.f;
             }
         }
         if (store) order_refill(io, env, episode);
     }
     if constexpr (RES && ROLE == 1) {
-        // (the wrench mailbox is free between hand-off (4) and the lattice side's next contact solve)
+        // (the wrench mailbox is free between hand-off (4) and the lattice side's next contact solve; LA: between this wave's reads behind hand-off (3) and the
+        //  lattice side's read behind hand-off (1) of the next pass)
         if (gl == 0) *reinterpret_cast<float4*>(&xl[MB_W]) = make_float4(kst, kdmp, mu, (MODE == 0 && need) ? 1.f : 0.f);
     }
     USIM_STAMP(dbg, 15);
@@ -1356,8 +1423,13 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
             // Tried for the split kernel and dropped: hand-offs between the two waves of a pair only (LDS counters, s_sleep + s_wakeup) instead of
             // workgroup barriers, so that a pair with few contacts runs ahead of its neighbours over the 64 steps of a launch -- 15.4 us/step
             // against 14.8 with the barriers, whatever the sleep length (8192 envs, 8-lane groups: 23.4 against 22.7).
-            __threadfence_block();
-            if constexpr (ROLE != 0) USIM_BAR();
+            // LATTICE_AHEAD: nothing of that is left -- the lattice side carries its state, each side owns its LDS areas and the mailbox words change hands at hand-offs
+            // (1) and (3) -- so neither the fence nor the barrier: the lattice wave runs on into the next pass
+            constexpr bool LA = lattice_ahead<ROLE, G, MULTI && MODE == 0>();
+            if constexpr (!LA) {
+                __threadfence_block();
+                if constexpr (ROLE != 0) USIM_BAR();
+            }
             if (io0.block && ctrl_done) advance_rollout_block(io, (size_t)n, C.adim);
             // usim_rollout_actions (ACTS): the next control step plays the next slice of the caller's action block [nsub][n][A], whether or not the outputs move --
             // a scalar add on a kernel argument, the same in both roles.  Instantiations of their own (usim_step16_acts_kernel, usim_step32_acts_kernel): in
@@ -1393,6 +1465,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // early return, a barrier under a branch that is not uniform over the whole workgroup, or a fifth hand-off on one side only would hang the
 // GPU instead of failing a test.  The profiling build counts the barriers of both roles (USIM_BAR: ticks[46] / ticks[47] of usim_profile_step) and
 // tests/test_gpu_properties.py compares them; the split-vs-single-wave bit-exactness tests cover ragged workgroups and slot overflow.
+// LATTICE_AHEAD (16-lane groups, multi-step launches): hand-off (4) and the barrier between the passes exist on the last pass only.  Barriers per pass, the same for
+// both roles (`first_pass` and `more` are uniform over the workgroup; a launch of one pass is first and last: T (1) (2) (3) (4)):
+//     pass                 arm wave                 lattice wave
+//     first, more follow   T (1) (2) (3)            T (1) (2) (3)            T = table copy
+//     middle               (1) (2) (3)              (1) (2) (3)
+//     last                 (1) (2) (3) (4)          (1) (2) (3) (4)
+//   a launch of n passes: 3 n + 2 in each role (switch off: 5 n; the profiling build counts both, tests/test_gpu_lattice_ahead.py compares them with this).  No fence
+//   between the passes: __syncthreads() at the hand-offs orders what changes hands there, and nothing changes hands in HBM inside a launch (below).
+//   What the missing barriers guarded, and what guards it now:
+//   * EB(GE_S): the arm wave neither reads nor writes it (it runs no broad-phase round); the lattice wave writes it on the first pass from the state it loaded, at every
+//     integration, and zeros when it adopts a new episode.  Every other word of the EB blocks was the lattice wave's already.
+//   * the lattice's state between the passes: in the lattice wave's registers (s, sd, kst, kdmp, mu, t, the warm record), no longer reloaded from what the arm wave stored;
+//     a new episode reaches it through MB_W behind hand-off (1), then lattice_rhs and lattice_solve run again for the wave; t advances at the top of the pass once and is
+//     set to its first value again on adoption, never advanced twice.
+//   * MB_W: wrench (lattice wave writes before (3), arm wave reads behind (3)), then the new-episode word (arm wave writes behind those reads, lattice wave reads behind
+//     (1) of the next pass, before it writes the next wrench): every change of hands has a hand-off in between.  MB_POSE is written before (1) of pass k + 1 and was
+//     read between (1) and (2) of pass k; MB_OP is written between (1) and (2) and read between (2) and (3); MB_Q belongs to the lattice wave; the transpose scratch, MB_GOAL
+//     and MB_ACT to the arm wave: hand-off (3) of pass k lies between every such pair.
+//   * zeroing on reset: the arm wave zeroes the lattice and clears the warm rows in HBM behind (4), so on the last pass only; on the others the lattice wave's next
+//     integration and warm_store overwrite every one of those words from the registers and the record it cleared on adoption.  What a launch leaves in HBM is unchanged.
 // G = 16: 16 environments per workgroup (a quad per wave pair).  G = 8: 32 environments per workgroup (eight per wave pair; two per DPP row) -- the
 // mapping for more than 4096 envs/GPU, where 16-lane groups would need a second round of workgroups.
 template <bool MULTI, int G = 16, bool WARM = false>

@@ -25,6 +25,19 @@ for base, names, title in ((20, names_a, "arm wave"), (30, names_b, "lattice wav
     for i, nm in enumerate(names):
         v = rows[:, base + i] - t0[:, 0]
         print(f"   {nm:36s} {np.median(v):9.0f}")
+# The step boundary (USIM_PROFILE_NSUB > 1: the stamps are those of the last pass of a launch): hand-off (1) of the last pass counted from hand-off (3) of the pass before it.
+# A library with LATTICE_AHEAD records that hand-off (3) (dbg[63] arm wave, dbg[62] lattice wave); for one without, the same path is pieced together from the stamps of one
+# pass, taken as periodic: hand-off (3) -> end of the pass, then start -> hand-off (1) (the barrier between the passes falls between the two pieces).
+# (With LATTICE_AHEAD the lattice wave's "start" lies BEFORE the arm wave's, the zero of this table: it enters the pass while the arm wave finishes the previous one; hand-off
+#  (4) exists on the last pass of a launch only, which is the one shown.)
+if rows.shape[1] > 63 and (rows[:, 62:64] > 0).all():
+    for col, title in ((63, "arm wave"), (62, "lattice wave")):
+        base = 20 if col == 63 else 30
+        print(f"== step boundary, {title}: hand-off (3) of the pass before -> hand-off (1) passed   {np.median(rows[:, base + 2] - rows[:, col]):9.0f}   (recorded)")
+else:
+    for base, title, last in ((20, "arm wave", 9), (30, "lattice wave", 8)):
+        v = (rows[:, base + last] - rows[:, base + 6]) + (rows[:, base + 2] - rows[:, base])
+        print(f"== step boundary, {title}: hand-off (3) -> end of the pass + start -> hand-off (1) passed   {np.median(v):9.0f}   (pieced together; excludes the wait at the barrier between the passes)")
 print(f"   (contact_solve entered at {np.median(rows[:, 40] - t0[:, 0]):.0f}, left at {np.median(rows[:, 44] - t0[:, 0]):.0f}: median ticks since the step's start; ncmax of this quad varies)")
 for i, nm in enumerate(["contact list ready", "ncmax known", "before contact_solve", "after contact_solve"]):
     print(f"   x{i} {nm:32s} {np.median(rows[:, 50 + i] - t0[:, 0]):9.0f}")

@@ -64,13 +64,13 @@ template <int TORSO, int OCC, bool WARM, Launch L> constexpr Row wave_row() {   
     else f = usim_step16_kernel<TORSO, OCC, 1, false, WARM>;
     return {TORSO == 0 ? Mapping::RIGID16 : OCC == 1 ? Mapping::SOFT16_W1 : Mapping::SOFT16_W2, WARM, L, {f, nullptr, 16, 256, arm_lds_base<TORSO, 0, 16>() + ARM_LDS_WORDS}};
 }
-template <int G, bool WARM, Launch L> constexpr Row split_row() {                               // split kernels: a wave pair per 64 / G environments, wpr<G>() pairs
+template <int G, bool WARM, Launch L> constexpr Row split_row() {                               // split kernels: a wave pair per 64 / G environments, SPLIT_WPR pairs
     static_assert((G == 16 || G == 8) && L != Launch::RESET, "SPLIT16, SPLIT8; they reset with SOFT16_W2's kernel");
     SplitKernel f = nullptr;
     if constexpr (L == Launch::STEP) f = usim_step32_kernel<false, G, WARM>;
     else if constexpr (L == Launch::MULTI) f = usim_step32_kernel<true, G, WARM>;
     else f = usim_step32_acts_kernel<G, WARM>;
-    return {G == 16 ? Mapping::SPLIT16 : Mapping::SPLIT8, WARM, L, {nullptr, f, (64 / G) * wpr<G>(), 128 * wpr<G>(), arm_lds_base<1, 1, G>() + ARM_LDS_WORDS}};
+    return {G == 16 ? Mapping::SPLIT16 : Mapping::SPLIT8, WARM, L, {nullptr, f, (64 / G) * SPLIT_WPR, 128 * SPLIT_WPR, arm_lds_base<1, 1, G>() + ARM_LDS_WORDS}};
 }
 
 // Every step kernel of the library, once.  The compiler emits the kernels in the order in which they are named here: the order is the one the code object has always

@@ -105,7 +105,7 @@ struct DevCfg {
     float dt, kp_fixed, damping_ratio, kp_min, kp_max, out_pos, out_ori;
     float stiffness, damping, elem_fric, probe_fric, probe_r, probe_hl;
     float probe_hw, probe_tip;                                   // half-width of the flat face across the blade, lowest point beyond the site (probe_sdf)
-    float probe_cull2;                                           // broad phase: (probe_r + probe_h + probe_hw + ELEM_HL + ELEM_R + margin)^2 (collide_cull)
+    float probe_cull2;                                           // read by no kernel; kept for the block's layout (the ball-form broad phase's (probe_r + probe_h + probe_hw + ELEM_HL + ELEM_R + margin)^2)
     float probe_deep0, probe_inv_band;                           // direction field below the surface: blend band (probe_sdf)
     float probe_r2, probe_h, probe_ca, probe_cb, probe_cah;   // flared blade (usim_kernels.hip probe_sdf): upper radius, height, flank direction (ca, cb), ca * h
     float top_off, y_range, drop;       // trajectory height above the torso centre, half width of the waypoint grid, spawn gap
@@ -116,7 +116,7 @@ struct DevCfg {
     int substeps;                       // physics steps (of dt) per control step: int(control_timestep / model_timestep) of robosuite MujocoEnv.step
     float dt_ctrl;                      // control timestep = substeps * dt (ultrasound.py:542)
     float frictionloss;                 // dry friction of every arm joint, N m (usim_config.joint_frictionloss)
-    float probe_cull2c;                 // broad phase with the element as a capsule (collide_cull CULL_CAPSULE): (rp + ELEM_R + margin)^2 with
+    float probe_cull2c;                 // broad phase, the element as a capsule (collide_cull): (rp + ELEM_R + margin)^2 with
                                         //     rp = max(hypot(H, probe_h) + probe_r, H + probe_r2),  H = hypot(probe_hl, probe_hw).
                                         // c = centre of the probe's upper axis (probe_tip - probe_r - probe_h along site z), S = the element's axis segment.  A point p of the blade
                                         // (probe_sdf) is b + rho u + z with b in the rectangle |x| <= hl, |y| <= hw of the site's xy plane (|b| <= H), u a unit vector of that plane,

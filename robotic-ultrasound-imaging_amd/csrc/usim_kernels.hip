@@ -213,28 +213,19 @@ DI void collide_elem(const float* lds, float* recs, const bool valid, const int 
 }
 
 // Broad phase (split kernel).  The probe -- convex hull of two parallel capsules whose axes are probe_h apart -- lies inside the capsule of
-// radius probe_r + probe_h around its UPPER axis; an element's capsule lies inside the ball of radius ELEM_HL + ELEM_R around the midpoint of its
-// axis segment.  An element whose ball misses that capsule cannot touch the probe: 80 % of the 99 elements, for 20 instructions each instead
-// of three distance evaluations.  The survivors go, in ascending element order, into a queue that the lanes of the group then walk together
-// (collide_queue): typically one pass of 16 instead of seven rounds.
-// CULL_CAPSULE: the roles of the two segments swapped -- the ELEMENT is tested as the capsule it is (radius ELEM_R around its axis segment of half-length
-// ELEM_HL) and the probe's short upper axis (half-length probe_hl, 0.65 cm against the element's 2.5 cm) is bounded by a ball around its centre: the lateral
-// reach falls from 7.35 cm to 4.97 cm for the same instructions per round (DevCfg::probe_cull2c states the inequality).  The cull only filters what the exact
-// narrow phase decides, so the contact lists keep their bits.
-#ifndef USIM_CULL_CAPSULE
-#define USIM_CULL_CAPSULE 1
-#endif
-constexpr bool CULL_CAPSULE = USIM_CULL_CAPSULE != 0;
-DI bool collide_cull(const float* lds, const int e, const DevModel& M, const DevCfg& C, const float se, const float dz, const f3 Kx, const f3 Ksx, const f3 Ksz) {
+// radius probe_r + probe_h around its UPPER axis, a short segment (half-length probe_hl, 0.65 cm) that the test bounds by a ball around its centre.  The
+// element is tested as the capsule it is: radius ELEM_R around its axis segment of half-length ELEM_HL (2.5 cm).  An element whose axis segment stays
+// farther from that centre than the two radii, probe_hl and the margin allow (DevCfg::probe_cull2c states the inequality; lateral reach 4.97 cm) cannot
+// touch the probe: most of the 99 elements, for 20 instructions each instead of three distance evaluations.  The survivors go, in ascending element
+// order, into a queue that the lanes of the group then walk together (collide_queue): typically one pass instead of seven rounds.  The cull only filters
+// what the exact narrow phase decides, so the contact lists do not depend on how tight it is.
+// (History: the first form bounded the ELEMENT by a ball around its midpoint and kept the probe's upper axis as the segment -- reach 7.35 cm, DevCfg::probe_cull2.)
+DI bool collide_cull(const float* lds, const int e, const DevModel& M, const DevCfg& C, const float se, const float dz, const f3 Kx, const f3 Ksz) {
     const f3 ax = mk(lds[TB_AXIS + 3 * e], lds[TB_AXIS + 3 * e + 1], lds[TB_AXIS + 3 * e + 2]);
     const f3 mid = mk(M.torso[0] + lds[TB_POS + 3 * e], M.torso[1] + lds[TB_POS + 3 * e + 1], M.torso[2] + lds[TB_POS + 3 * e + 2] + dz) + ax * (se - ELEM_R - ELEM_HL);
     const f3 d = mid - (Kx - Ksz * (C.probe_r + C.probe_h - C.probe_tip));         // from the centre of the upper axis (site z points away from the probe body)
-    if constexpr (CULL_CAPSULE) {
-        const f3 v = d - ax * clampf(dot(d, ax), -ELEM_HL, ELEM_HL);               // from the centre of the upper axis to the nearest point of the element's axis segment
-        return dot(v, v) < C.probe_cull2c;
-    }
-    const f3 v = d - Ksx * clampf(dot(d, Ksx), -C.probe_hl, C.probe_hl);
-    return dot(v, v) < C.probe_cull2;
+    const f3 v = d - ax * clampf(dot(d, ax), -ELEM_HL, ELEM_HL);                   // from the centre of the upper axis to the nearest point of the element's axis segment
+    return dot(v, v) < C.probe_cull2c;
 }
 template <int G>
 DI void collide_queue(const float* lds, const float* queue, const int nq, float* recs, const int gl, const int gbase, const DevModel& M, const DevCfg& C,
@@ -407,7 +398,7 @@ DI int collide_all(float* lds, const int eb, const int gl, const int gbase, cons
         const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
         const float se = live ? s_pre[i] : 0.f;
         if (eraw < N_TOP) EBF(GE_S + eraw) = se;
-        const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, se, dz, Kx, Ksx, Ksz);
+        const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, se, dz, Kx, Ksz);
         const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & ((1u << G) - 1u);
         if (cand) q[nq + __popc(gm & ((1u << gl) - 1u))] = __int_as_float(e);
         nq += __popc(gm);

@@ -237,14 +237,9 @@ constexpr int X16_RIGID_STRIDE = 84;                  // rigid-torso launches: o
 // matrix-core solve, collision, contact solve, element integration).  They meet at workgroup barriers and hand over through per-environment
 // LDS mailboxes: site pose (1 -> 2), Lambda^-1 / alpha / vs (1 -> 2), contact wrench and contact list (2 -> 1).  ROLE 0 = one wave does both.
 //
-// waves per role in a workgroup of the split kernel (4: one 512-thread workgroup per CU; 2: two 256-thread workgroups per CU with barrier domains of their own)
-#ifndef USIM_WPR16
-#define USIM_WPR16 4
-#endif
-#ifndef USIM_WPR8
-#define USIM_WPR8 4
-#endif
-template <int G> constexpr int wpr() { return G == 16 ? USIM_WPR16 : USIM_WPR8; }
+// waves per role in a workgroup of the split kernel: one 512-thread workgroup per CU (two 256-thread workgroups per CU, with barrier domains of their own, measured slower
+// for both group sizes: DESIGN.md section 4.8)
+constexpr int SPLIT_WPR = 4;
 // Split kernel: behind the per-environment blocks (16 with 16-lane groups, 32 with 8-lane groups) every environment has a mailbox block, one layout for both
 // group sizes (word offsets):
 constexpr int MB_POSE = X16_WORDS;                    // (before it: the 8 x 8 transpose scratch of the arm wave)  site pose 9 words; word 10: length of the broad-phase queue
@@ -252,58 +247,32 @@ constexpr int MB_OP = MB_POSE + 12;                   // op-space quantities: 6 
 constexpr int MB_W = MB_OP + 64;                      // contact wrench 6, contact count, overflow flag, shell ids 8 (between the steps of a resident launch: the new episode's parameters)
 constexpr int MB_Q = MB_W + 16;                       // broad-phase queue (element ids; the spare last word takes the non-candidates' stores)
 constexpr int MB_GOAL = MB_Q + 100;                   // `fixed` mode with physics substeps: the goal anchored at the policy step (12 words)
-// DRAW_AHEAD (split kernel, resident launches of usim_rollout_random): the arm wave draws the NEXT pass's random action in its idle window between precompute() and
-// hand-off (3) and keeps the seven words in its own mailbox block (written and read by the same wave), so that the Philox rounds leave the chain behind hand-off (1).
-#ifndef USIM_DRAW_AHEAD
-#define USIM_DRAW_AHEAD 1
-#endif
-constexpr bool DRAW_AHEAD = USIM_DRAW_AHEAD != 0;
-// LIST_AHEAD (split kernel, 16-lane groups): the lattice wave applies the slot rule and forms ncmax and the contact elements before hand-off (2) (step16_one).
-// OFF: workgroup 0's timeline gains 400 ticks per step with it, the benchmark nothing (17.27 -> 17.32 us/step, profiles/handoff_balance/ab.txt)
-#ifndef USIM_LIST_AHEAD
-#define USIM_LIST_AHEAD 0
-#endif
-constexpr bool LIST_AHEAD = USIM_LIST_AHEAD != 0;
-// LATTICE_AHEAD (split kernel, 16-lane groups, resident launches): lattice_rhs and lattice_solve need nothing from the arm side but "this episode ended", which happens once
-// per episode.  The lattice wave therefore goes straight from integrating pass k into the right-hand side and the solve of pass k + 1 on the state in its registers and
-// meets the arm wave only at hand-off (1) of pass k + 1; hand-off (4) and the barrier between the passes exist on the last pass of a launch only.  After hand-off (1) it
-// reads the arm wave's new-episode word; if an environment of the wave has one it adopts it and runs the two phases again for the wave (same instructions on the same
-// inputs for the environments that went on: same bits).  The lattice wave then owns EB(GE_S) and carries kst / kdmp / mu / t, the lattice and the warm record between the
-// passes.  The hand-offs and what each hazard rests on: BARRIER INVARIANT at usim_step32_kernel.
-#ifndef USIM_LATTICE_AHEAD
-#define USIM_LATTICE_AHEAD 1
-#endif
-constexpr bool LATTICE_AHEAD = USIM_LATTICE_AHEAD != 0;
-// LATTICE_PRIO (with LATTICE_AHEAD): the two waves of a pair share the VALU issue of their SIMD, the older one -- the arm wave -- first.  With LATTICE_AHEAD the lattice wave is
-// the longer one from hand-off (2) to hand-off (1) of the next pass (contact solve, integration, right-hand side, solve) and runs its right-hand side beside the arm wave's
-// finish, where it got the slots the arm wave left: 6.2 k ticks for the two phases against 4.9 k beside an idle partner, and the step gained 0.7 % instead of 4 %.  The
-// lattice wave therefore raises its priority (s_setprio 1) from hand-off (2) to hand-off (1) and drops it between (1) and (2), where the arm wave is the longer one.
-// One box, kernel us/step at 4096 envs, four samples each (profiles/lattice_ahead/ab.txt): parent 17.00, no priority 16.85, this window 16.58; raised for the whole pass
-// 17.27 (the arm wave's op-space phase 5.7 k -> 7.2 k ticks), from (2) to (3) only 16.63, from (2) to the end of the integration 16.75, from (2) to the right-hand side 16.75.
-#ifndef USIM_LATTICE_PRIO
-#define USIM_LATTICE_PRIO 1
-#endif
-constexpr bool LATTICE_PRIO = USIM_LATTICE_PRIO != 0;
-constexpr int MB_ACT = MB_GOAL + 12;                  // DRAW_AHEAD: the action of the running control step / of the next one (7 words + 1)
-constexpr int X2_STRIDE = MB_ACT + (DRAW_AHEAD ? 8 : 0);
-template <int G> constexpr int x2_base() { return TB_WORDS + (64 * wpr<G>() / G) * GE_STRIDE; }
+// Action drawn ahead (split kernel, resident launches of usim_rollout_random; AHEAD of step16_one): the arm wave draws the NEXT pass's random action in its idle window
+// between precompute() and hand-off (3) and keeps the seven words in its own mailbox block (written and read by the same wave), so that the Philox rounds leave the
+// chain behind hand-off (1).
+constexpr int MB_ACT = MB_GOAL + 12;                  // the action of the running control step / of the next one (7 words + 1)
+constexpr int X2_STRIDE = MB_ACT + 8;
+template <int G> constexpr int x2_base() { return TB_WORDS + (64 * SPLIT_WPR / G) * GE_STRIDE; }
 static_assert(x2_base<16>() % 4 == 0 && x2_base<8>() % 4 == 0 && X2_STRIDE % 4 == 0 && MB_OP % 4 == 0 && MB_W % 4 == 0 && MB_ACT % 4 == 0, "mailbox block: 16-byte accesses");
 static_assert((x2_base<8>() + 32 * X2_STRIDE) * 4 <= 160 * 1024, "split kernel with 8-lane groups: LDS of a CU");
-// Collision in the split kernel: the ARM side, which has the site pose first, runs the broad phase (collide_cull) while the lattice side still stages its
-// right-hand side and solves, and leaves the survivors' ids (ascending) in the queue; after hand-off (1) the lattice side appends what the arm side left of the
-// broad phase and evaluates the whole queue (collide_queue), typically in one pass of its 16 lanes per environment.  (Giving the arm side a share of the narrow
-// phase measured slower for every share and both group sizes -- DESIGN.md section 4.6 -- and was removed.)
-// (How the broad phase is divided is arm_cull_rounds: 8-lane groups as described; with 16-lane groups the lattice side now runs all of it after the hand-off.)
-// broad-phase rounds the arm side runs before hand-off (1); the lattice side runs the rest after it.  16-lane groups: NONE since the capsule-form cull -- the narrow phase
-// is one pass and the lattice wave has 2.3 k ticks to spare before hand-off (2), while the arm wave is the longer one on both sides of hand-off (1): kernel us/step, four
-// samples each, one box: 7 (all) -> 17.27, 5 -> 17.25, 3 -> 17.07, 0 -> 17.02 (parent 17.40; profiles/handoff_balance/ab.txt).  (With the ball-form cull, when the lattice
-// wave was the one waited for: 0 -> 15.67, 2 -> 15.98, 4 -> 15.92, 7 -> 15.48.)  8-lane groups: 7 of 13.
-#ifndef USIM_ARM_CULL16
-#define USIM_ARM_CULL16 0
-#endif
-template <int G> constexpr int arm_cull_rounds() { return G == 16 ? USIM_ARM_CULL16 : 7; }
-static_assert(!LATTICE_AHEAD || USIM_ARM_CULL16 == 0, "LATTICE_AHEAD: the arm wave must not need the integrated element positions (no broad-phase rounds on its side)");
-template <int ROLE, int G, bool RES> constexpr bool lattice_ahead() { return LATTICE_AHEAD && ROLE != 0 && G == 16 && RES; }
+// Collision in the split kernel: the broad phase (collide_cull) leaves the ids of the elements that can touch the probe (ascending) in the environment's queue, and the
+// lattice side evaluates the whole queue after hand-off (1) (collide_queue), typically in one pass of its lanes.  Who culls:
+//   8-lane groups:  the arm side, which has the site pose first, runs 7 of the 13 rounds before hand-off (1), while the lattice side still stages its right-hand side and
+//                   solves; the lattice side appends the other 6 after the hand-off.
+//   16-lane groups: the lattice side runs all 7 rounds after the hand-off; the arm side, the longer one on both sides of hand-off (1), runs none and never needs the
+//                   integrated element positions (which is what lets the lattice wave run ahead, below).
+// (7 / 5 / 3 / 0 arm-side rounds of 16-lane groups measured: profiles/handoff_balance/ab.txt.  Giving the arm side a share of the NARROW phase measured slower for every
+// share and both group sizes -- DESIGN.md section 4.6 -- and was removed.)
+template <int G> constexpr int arm_cull_rounds() { return G == 16 ? 0 : 7; }
+// LA, the lattice solve ahead (split kernel, 16-lane groups, resident launches): lattice_rhs and lattice_solve need nothing from the arm side but "this episode ended", which
+// happens once per episode.  The lattice wave therefore goes straight from integrating pass k into the right-hand side and the solve of pass k + 1 on the state in its
+// registers and meets the arm wave only at hand-off (1) of pass k + 1; hand-off (4) and the barrier between the passes exist on the last pass of a launch only.  After
+// hand-off (1) it reads the arm wave's new-episode word; if an environment of the wave has one it adopts it and runs the two phases again for the wave (same instructions on
+// the same inputs for the environments that went on: same bits).  The lattice wave then owns EB(GE_S) and carries kst / kdmp / mu / t, the lattice and the warm record
+// between the passes.  The hand-offs and what each hazard rests on: BARRIER INVARIANT at usim_step32_kernel.
+// Such a lattice wave runs at s_setprio 1 from hand-off (2) to hand-off (1) of the next pass, where it is the longer one of the pair, and at 0 between (1) and (2), where the
+// arm wave is (the two share the VALU issue of their SIMD, the older one -- the arm wave -- first; the other windows measured: profiles/lattice_ahead/ab.txt).
+template <int ROLE, int G, bool RES> constexpr bool lattice_ahead() { return ROLE != 0 && G == 16 && RES; }
 
 // workgroup barrier of the step kernels; the profiling build counts them per role (BARRIER INVARIANT at usim_step32_kernel)
 #if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
@@ -329,12 +298,12 @@ struct Carry {
 };
 
 template <int TORSO, int ROLE, int G> constexpr int arm_lds_base() {
-    return ROLE != 0 ? x2_base<G>() + (64 * wpr<G>() / G) * X2_STRIDE : (TORSO ? SOFT16_LDS_WORDS : 16 * X16_RIGID_STRIDE);
+    return ROLE != 0 ? x2_base<G>() + (64 * SPLIT_WPR / G) * X2_STRIDE : (TORSO ? SOFT16_LDS_WORDS : 16 * X16_RIGID_STRIDE);
 }
 static_assert((arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS) * 4 <= 160 * 1024 && arm_lds_base<1, 1, 8>() % 4 == 0 && arm_lds_base<1, 1, 16>() % 4 == 0 && arm_lds_base<1, 0, 16>() % 4 == 0
               && arm_lds_base<0, 0, 16>() % 4 == 0, "arm table behind the LDS blocks of every 16-lane kernel");
 
-// AHEAD (DRAW_AHEAD; arm side of the split kernel in resident launches that draw their actions): `more` = another pass of this launch follows this one
+// AHEAD (action drawn ahead; arm side of the split kernel in resident launches that draw their actions): `more` = another pass of this launch follows this one
 template <int TORSO, int MODE, int ROLE, int NT, int G = 16, bool RES = false, class WR = NoWarm, bool AHEAD = false>
 DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __restrict__ st, const int n, const int npad, const DevIO& io, const int flags, const long long rstep,
                    const bool first_pass, const int sub, const bool more, int& nbar, Carry<TORSO ? (N_TOP + G - 1) / G : 1, WR>& cy) {
@@ -344,7 +313,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     constexpr bool WARM = !std::is_same<WR, NoWarm>::value;
     // (MODE 1, the reset launch of such a handle: its zero-torque forward pass solves cold and keeps nothing; it clears the rows of the environments it resets)
     static_assert(!WARM || (TORSO == 1 && ROLE == 0) || (TORSO == 1 && MODE == 0), "warm start: the soft-torso kernels");
-    constexpr int WPR = (ROLE != 0) ? wpr<G>() : 4;
+    constexpr int WPR = (ROLE != 0) ? SPLIT_WPR : 4;                    // (single-wave kernels: the four waves of a 256-thread workgroup)
     constexpr int EPW = 64 / G, EPB = WPR * EPW;                        // environments per wave / per workgroup (WPR waves per role)
     static_assert(!RES || MODE == 0, "resident state: step launches only");
     constexpr int X2_BASE = x2_base<G>();
@@ -353,12 +322,9 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     constexpr int NE = TORSO ? (N_TOP + G - 1) / G : 1;
     static_assert(ROLE == 0 || (TORSO == 1 && MODE == 0), "the split kernel is the soft-torso step");
     const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & (WPR - 1);      // wave within its role = quad of environments
-    // resident state (see Carry): everywhere but on the lattice side of the split kernel with 16-lane groups, where it measured slower (one box,
-    // us/step at 4096 envs: neither side 15.00, arm side only 14.78, both 15.28, lattice side only 15.60; 8-lane groups at 8192 envs: 23.10 / 22.73 / 22.67)
-    // (LATTICE_AHEAD makes the lattice side resident too: it no longer waits for the arm side's stores between the passes, which is what the reload was for)
+    // resident state (see Carry): every role of a multi-step launch.  (Before the lattice wave of 16-lane groups ran ahead it reloaded its state every pass instead.)
     constexpr bool LA = lattice_ahead<ROLE, G, RES>();
-    constexpr bool RES_HERE = RES && (LA || !(ROLE == 2 && G == 16));
-    const bool fresh = !RES_HERE || first_pass;                         // the state comes from HBM (first step of a launch; every single-step launch)
+    const bool fresh = !RES || first_pass;                              // the state comes from HBM (first step of a launch; every single-step launch)
     const int gl = lane & (G - 1), ge = lane / G;
     const int gbase = lane - gl;
     const int eb = wave * EPW + ge;
@@ -450,17 +416,17 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             const int e = gl + i * G;
             s_pre[i] = 0.f; sd_pre[i] = 0.f;
             if (TORSO && MODE == 0 && ROLE != 1 && e < N_TOP) { s_pre[i] = LAT(LAT_S + e); sd_pre[i] = LAT(LAT_SD + e); }
-            if (TORSO && MODE == 0 && ROLE == 1 && !LA && e < N_TOP) s_pre[i] = LAT(LAT_S + e);      // the arm side runs the broad phase of the collision (LA: none of it, and the lattice side parks the positions)
+            if (TORSO && MODE == 0 && ROLE == 1 && !LA && e < N_TOP) s_pre[i] = LAT(LAT_S + e);      // the arm side parks the positions for the narrow phase and, with 8-lane groups, culls on them (LA: the lattice side does both)
         }
         if constexpr (WARM && MODE == 0 && ROLE != 1) warm_load(warm_rows, gl, cy.wr);
     } else if constexpr (RES && ROLE == 1 && !LA) {
-        // resident launch, arm side: the element positions the lattice side integrated (or the zeros this side left for a new episode) are in
-        // the environment's LDS block
+        // resident launch, arm side of 8-lane groups (the only one that culls): the element positions the lattice side integrated (or the zeros this side left
+        // for a new episode) are in the environment's LDS block
 #pragma unroll
         for (int i = 0; i < NE; ++i) { const int e = gl + i * G; s_pre[i] = (e < N_TOP) ? EB(GE_S + e) : 0.f; }
     } else if constexpr (RES && ROLE == 2 && !LA) {
-        // resident launch, lattice side: the arm side reports a new episode (lattice at rest, its parameters, t = 0) through the mailbox
-        // (LA: read behind hand-off (1), below)
+        // resident launch, lattice side of 8-lane groups: the arm side reports a new episode (lattice at rest, its parameters, t = 0) through the mailbox
+        // (16-lane groups, LA: read behind hand-off (1), below)
         const float4 nx = *reinterpret_cast<const float4*>(&lds[mbo + MB_W]);
         if (nx.w != 0.f) {
             kst = nx.x; kdmp = nx.y; mu = nx.z; t = 0;
@@ -505,7 +471,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     if constexpr (ROLE == 2) {
         // ================= lattice / contact side of the split kernel =================
         RSTAMP(0);
-        if constexpr (LA && LATTICE_PRIO) __builtin_amdgcn_s_setprio(1);        // (first pass; later ones come here with it raised)
+        if constexpr (LA) __builtin_amdgcn_s_setprio(1);                   // (first pass; later ones come here with it raised)
         float* const mb = &lds[mbo];
         const int* tb_shell = reinterpret_cast<const int*>(lds + TB_SHELL);
         float dz, vz, az;
@@ -529,8 +495,8 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         RSTAMP(1);
         USIM_BAR();                                                 // (1) the arm side has published the site pose
         RSTAMP(2);
-        if constexpr (LA && LATTICE_PRIO) __builtin_amdgcn_s_setprio(0);
         if constexpr (LA) {
+            __builtin_amdgcn_s_setprio(0);
             if (!first_pass) {
                 // the arm side's word of the previous pass (written behind its reads of the wrench, read here before this pass's wrench is written): a new episode starts
                 // with the lattice at rest, its own parameters and t = 0 -- adopt it (t advances as at the top of the pass: once) and run the two phases again
@@ -558,7 +524,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 #pragma unroll
         for (int i = arm_cull_rounds<G>(); i < NE; ++i) {
             const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
-            const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz, xs, sxc, sz);
+            const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz, xs, sz);
             const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & GMASK;
             mb[MB_Q + (cand ? nq + __popc(gm & ((1u << gl) - 1u)) : 99)] = __int_as_float(e);       // (as on the arm side: the spare last word takes the non-candidates)
             nq += __popc(gm);
@@ -568,7 +534,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         // profiling build: queue length of every environment of the first lattice wave of workgroup 0 (dbg[54 ..]; collide_queue makes max ceil(nq / G) passes over the wave)
         if (dbg && blockIdx.x == 0 && wave == 0 && gl == 0) dbg[54 + ge] = 1ull + (unsigned long long)nq;
 #endif
-        // narrow phase: the whole queue, against the element positions the arm side parked in the environment's block
+        // narrow phase: the whole queue, against the element positions parked in the environment's block (by the arm side; LA: by this side)
         int nc = 0;
         collide_queue<G>(lds, mb + MB_Q, nq, &EB(GE_CG), gl, gbase, M, C, &EB(GE_S), dz, xs, sxc, sy, sz, nc);
         // The contact list is complete here.  8-lane groups (EARLY) apply the slot rule and form the contact elements and the arm-independent half of every
@@ -580,39 +546,28 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         // (The early list lives in variables of its own and is adopted after the hand-off.  Forming it in nc / overflow / ncmax / cel directly, with the slot rule as
         //  one lambda called on either side of the barrier, reads better and cost the 8-lane multi-step kernel two more spilled registers, 8 B of scratch and 0.6 % of
         //  the 8192-environment step: DESIGN.md section 10.)
-        // LIST_AHEAD (16-lane groups; switched off, see the switch): with the capsule-form broad phase the queue is one pass and this wave reaches hand-off (2) ~2.3 k ticks
-        // before the arm wave: what of the list needs no Lambda^-1 / alpha / vs -- the slot rule, the wave's largest count, the contact elements -- can be formed in that slack;
-        // the rows stay behind the hand-off (contact_solve keeps its CLONE layout).  The count is uniform over a group, so the wave's maximum is that of the four groups'
-        // first lanes.
-        constexpr bool LIST_EARLY = EARLY || (G == 16 && LIST_AHEAD);
         int nc_early = nc, overflow_early = 0, ncmax_early = 0, cel_early[MAXC];
-        if constexpr (LIST_EARLY) {
+        if constexpr (EARLY) {
             contact_overflow<G>(lds, eb, gl, gbase, nc_early);
             if (nc_early > MAXC) { overflow_early = 1; nc_early = MAXC; }
             group_sync();
-            if constexpr (G == 16) {
-                const int m01 = max(__builtin_amdgcn_readlane(nc_early, 0), __builtin_amdgcn_readlane(nc_early, 16));
-                const int m23 = max(__builtin_amdgcn_readlane(nc_early, 32), __builtin_amdgcn_readlane(nc_early, 48));
-                ncmax_early = max(m01, m23);
-            } else {
 #pragma unroll
-                for (int k = MAXC; k >= 1; --k) if (ncmax_early == 0 && __any(nc_early >= k)) ncmax_early = k;
-            }
+            for (int k = MAXC; k >= 1; --k) if (ncmax_early == 0 && __any(nc_early >= k)) ncmax_early = k;
 #pragma unroll
             for (int k = 0; k < MAXC; ++k) cel_early[k] = (k < nc_early) ? __float_as_int(EB(GE_CG + k * CG_WORDS + 6)) : 0;
-            if constexpr (EARLY) { if (ncmax_early > 0) contact_rows<G>(lds, eb, gl, M, C, nc_early, cel_early, vz, P); }
+            if (ncmax_early > 0) contact_rows<G>(lds, eb, gl, M, C, nc_early, cel_early, vz, P);
         }
         RSTAMP(3);
         USIM_BAR();                                                 // (2) ... and Lambda^-1, alpha = J qs, vs = J qd
         RSTAMP(4);
-        if constexpr (LA && LATTICE_PRIO) __builtin_amdgcn_s_setprio(1);
-        if constexpr (!LIST_EARLY) contact_overflow<G>(lds, eb, gl, gbase, nc);
+        if constexpr (LA) __builtin_amdgcn_s_setprio(1);
+        if constexpr (!EARLY) contact_overflow<G>(lds, eb, gl, gbase, nc);
         int overflow = 0;
         if (nc > MAXC) { overflow = 1; nc = MAXC; }
-        if constexpr (!LIST_EARLY) group_sync();
+        if constexpr (!EARLY) group_sync();
         XSTAMP(0);
         int ncmax = 0;
-        if constexpr (LIST_EARLY) { nc = nc_early; overflow = overflow_early; ncmax = ncmax_early; }
+        if constexpr (EARLY) { nc = nc_early; overflow = overflow_early; ncmax = ncmax_early; }
         else {
 #pragma unroll
             for (int k = MAXC; k >= 1; --k) if (ncmax == 0 && __any(nc >= k)) ncmax = k;
@@ -621,7 +576,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         float gf[MAXC], W[6] = {0, 0, 0, 0, 0, 0};
         int cel[MAXC];
 #pragma unroll
-        for (int k = 0; k < MAXC; ++k) { const int ek = __float_as_int(EB(GE_CG + k * CG_WORDS + 6)); gf[k] = 0.f; cel[k] = LIST_EARLY ? cel_early[k] : ((k < nc) ? ek : 0); }      // (read, then select: no branch per slot)
+        for (int k = 0; k < MAXC; ++k) { const int ek = __float_as_int(EB(GE_CG + k * CG_WORDS + 6)); gf[k] = 0.f; cel[k] = EARLY ? cel_early[k] : ((k < nc) ? ek : 0); }      // (read, then select: no branch per slot)
         if (ncmax > 0) {
             float alpha[6], vs[6], Lp[21];
 #pragma unroll
@@ -774,14 +729,13 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             // into the environment's LDS block for whoever evaluates them
             float dz_, vz_, az_;
             torso_motion(C, tphys, dz_, vz_, az_);
-            const f3 sxc = cross(sy, sz);
             int nq = 0;
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
                 const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
-                if (!LA && eraw < N_TOP) EB(GE_S + eraw) = s_pre[i];          // (LA: the lattice side owns the area)
+                if (!LA && eraw < N_TOP) EB(GE_S + eraw) = s_pre[i];          // (8-lane groups and single-step launches; LA: the lattice side owns the area)
                 if (i >= arm_cull_rounds<G>()) continue;
-                const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz_, xs, sxc, sz);
+                const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz_, xs, sz);
                 const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & GMASK;
                 xl[MB_Q + (cand ? nq + __popc(gm & ((1u << gl) - 1u)) : 99)] = __int_as_float(e);     // (a lane without a candidate writes the queue's spare last word -- 99 elements at most are queued --: a store, not a branch)
                 nq += __popc(gm);
@@ -1349,11 +1303,11 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         }
         if constexpr (RES && TORSO != 0) {
             // resident launch: the lattice of the new episode is at rest in the registers too (single wave) / in the LDS copy of the element
-            // positions this side reads back at the next step (split kernel; the lattice side learns of it through the mailbox below)
+            // positions this side reads back at the next step (split kernel with 8-lane groups; the lattice side learns of it through the mailbox below)
 #pragma unroll
             for (int i = 0; i < NE; ++i) {
                 s_pre[i] = 0.f; sd_pre[i] = 0.f;
-                if (ROLE == 1 && !LA && gl + i * G < N_TOP) EB(GE_S + gl + i * G) = 0.f;
+                if (ROLE == 1 && !LA && gl + i * G < N_TOP) EB(GE_S + gl + i * G) = 0.f;       // (8-lane groups only: with LA the lattice side zeroes its own copy)
             }
         }
         if (store) order_refill(io, env, episode);
@@ -1411,19 +1365,19 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
     long long cstep = rstep;                                             // control step: keys the in-kernel action draw
     for (int ks = 0; ks < nsub; ++ks) {
         // (the launches of usim_rollout_actions -- ACTS -- never draw: they keep the code they had)
-        constexpr bool AHEAD = DRAW_AHEAD && ROLE == 1 && MULTI && MODE == 0 && !ACTS;
+        constexpr bool AHEAD = ROLE == 1 && MULTI && MODE == 0 && !ACTS;
         step16_one<TORSO, MODE, ROLE, NT, G, MULTI && MODE == 0, WR, AHEAD>(lds, M, C, st, n, npad, io, flags, cstep, ks == 0, sub, ks + 1 < nsub, nbar, cy);
         const bool ctrl_done = sub == S - 1;                             // this pass completed a control step
         if (ctrl_done) { sub = 0; ++cstep; } else ++sub;
         if (ks + 1 < nsub) {
-            // Split kernel: the next step reads words this one stored through the other wave of the pair (the lattice side of 16-lane groups
-            // reloads the per-episode scalars; the LDS blocks are reused): order the stores, then meet.  (Both roles pass here once per step.)
+            // Split kernel with 8-lane groups: the next step reads words this one left in LDS through the other wave of the pair (the element positions,
+            // the new-episode word; the blocks are reused): order the stores, then meet.  (Both roles pass here once per step.)
             // A single-wave kernel keeps its state in registers and its LDS blocks to itself: its waves never meet after the table copy
             // (lanes 16 kernel 17.05 -> 16.76 us/step, rigid torso 5.12 -> 5.03).
             // Tried for the split kernel and dropped: hand-offs between the two waves of a pair only (LDS counters, s_sleep + s_wakeup) instead of
             // workgroup barriers, so that a pair with few contacts runs ahead of its neighbours over the 64 steps of a launch -- 15.4 us/step
             // against 14.8 with the barriers, whatever the sleep length (8192 envs, 8-lane groups: 23.4 against 22.7).
-            // LATTICE_AHEAD: nothing of that is left -- the lattice side carries its state, each side owns its LDS areas and the mailbox words change hands at hand-offs
+            // Split kernel with 16-lane groups (LA): nothing changes hands here -- the lattice side carries its state, each side owns its LDS areas and the mailbox words change hands at hand-offs
             // (1) and (3) -- so neither the fence nor the barrier: the lattice wave runs on into the next pass
             constexpr bool LA = lattice_ahead<ROLE, G, MULTI && MODE == 0>();
             if constexpr (!LA) {
@@ -1438,7 +1392,7 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
         }
     }
 #if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
-    if (ROLE != 0 && io0.dbg && blockIdx.x == 0 && (threadIdx.x & (64 * wpr<G>() - 1)) == 0) io0.dbg[ROLE == 1 ? 46 : 47] = (unsigned long long)nbar;
+    if (ROLE != 0 && io0.dbg && blockIdx.x == 0 && (threadIdx.x & (64 * SPLIT_WPR - 1)) == 0) io0.dbg[ROLE == 1 ? 46 : 47] = (unsigned long long)nbar;
 #endif
 }
 
@@ -1465,13 +1419,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // early return, a barrier under a branch that is not uniform over the whole workgroup, or a fifth hand-off on one side only would hang the
 // GPU instead of failing a test.  The profiling build counts the barriers of both roles (USIM_BAR: ticks[46] / ticks[47] of usim_profile_step) and
 // tests/test_gpu_properties.py compares them; the split-vs-single-wave bit-exactness tests cover ragged workgroups and slot overflow.
-// LATTICE_AHEAD (16-lane groups, multi-step launches): hand-off (4) and the barrier between the passes exist on the last pass only.  Barriers per pass, the same for
+// The lattice solve ahead (LA: 16-lane groups, multi-step launches): hand-off (4) and the barrier between the passes exist on the last pass only.  Barriers per pass, the same for
 // both roles (`first_pass` and `more` are uniform over the workgroup; a launch of one pass is first and last: T (1) (2) (3) (4)):
 //     pass                 arm wave                 lattice wave
 //     first, more follow   T (1) (2) (3)            T (1) (2) (3)            T = table copy
 //     middle               (1) (2) (3)              (1) (2) (3)
 //     last                 (1) (2) (3) (4)          (1) (2) (3) (4)
-//   a launch of n passes: 3 n + 2 in each role (switch off: 5 n; the profiling build counts both, tests/test_gpu_lattice_ahead.py compares them with this).  No fence
+//   a launch of n passes: 3 n + 2 in each role of usim_step32_kernel<true, 16, *> and usim_step32_acts_kernel<16, *>; 5 n in each role of the kernels of 8-lane groups
+//   (T, then (1)-(4) and the barrier between passes n - 1 times, then (1)-(4)) and 5 in a single-step launch (the profiling build counts both roles,
+//   tests/test_gpu_lattice_ahead.py compares them with this).  No fence
 //   between the passes: __syncthreads() at the hand-offs orders what changes hands there, and nothing changes hands in HBM inside a launch (below).
 //   What the missing barriers guarded, and what guards it now:
 //   * EB(GE_S): the arm wave neither reads nor writes it (it runs no broad-phase round); the lattice wave writes it on the first pass from the state it loaded, at every
@@ -1488,14 +1444,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // G = 16: 16 environments per workgroup (a quad per wave pair).  G = 8: 32 environments per workgroup (eight per wave pair; two per DPP row) -- the
 // mapping for more than 4096 envs/GPU, where 16-lane groups would need a second round of workgroups.
 template <bool MULTI, int G = 16, bool WARM = false>
-__global__ __launch_bounds__(128 * wpr<G>()) __attribute__((amdgpu_waves_per_eu(2, 2))) void usim_step32_kernel(const DevModel* __restrict__ Mp, const DevCfg* __restrict__ Cp, float* __restrict__ st, int n, int npad,
+__global__ __launch_bounds__(128 * SPLIT_WPR) __attribute__((amdgpu_waves_per_eu(2, 2))) void usim_step32_kernel(const DevModel* __restrict__ Mp, const DevCfg* __restrict__ Cp, float* __restrict__ st, int n, int npad,
                                                                                                                   const DevIO io, int flags, long long rstep) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // Model and configuration by POINTER to a constant block of the handle in HBM (usim_handle::d_consts), not by value: by value they are ~110 kernel-argument
     // dwords that the compiler loads once and keeps -- 186 of them spilled to VGPR lanes, every reload a v_readlane in the 256-step loop (round-4 review).
     // Through the pointer a field is a scalar load (SMEM, scalar cache) where it is used.
     const DevModel& M = *Mp; const DevCfg& C = *Cp;
-    constexpr int NT = 128 * wpr<G>();
+    constexpr int NT = 128 * SPLIT_WPR;
     typedef typename std::conditional<WARM, typename WarmOf<G>::type, NoWarm>::type WR;
     if (threadIdx.x < NT / 2) step16_body<1, 0, 1, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
     else step16_body<1, 0, 2, NT, MULTI, G, WR>(lds, M, C, st, n, npad, io, flags, rstep);
@@ -1504,11 +1460,11 @@ __global__ __launch_bounds__(128 * wpr<G>()) __attribute__((amdgpu_waves_per_eu(
 // the multi-step launch of usim_rollout_actions with the split kernel: usim_step32_kernel<true, G, WARM> whose two roles move io.act on between control steps (step16_body
 // ACTS: no barrier, no branch that differs between the roles -- the BARRIER INVARIANT above holds as it does there)
 template <int G = 16, bool WARM = false>
-__global__ __launch_bounds__(128 * wpr<G>()) __attribute__((amdgpu_waves_per_eu(2, 2))) void usim_step32_acts_kernel(const DevModel* __restrict__ Mp, const DevCfg* __restrict__ Cp, float* __restrict__ st, int n, int npad,
+__global__ __launch_bounds__(128 * SPLIT_WPR) __attribute__((amdgpu_waves_per_eu(2, 2))) void usim_step32_acts_kernel(const DevModel* __restrict__ Mp, const DevCfg* __restrict__ Cp, float* __restrict__ st, int n, int npad,
                                                                                                                        const DevIO io, int flags, long long rstep) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const DevModel& M = *Mp; const DevCfg& C = *Cp;
-    constexpr int NT = 128 * wpr<G>();
+    constexpr int NT = 128 * SPLIT_WPR;
     typedef typename std::conditional<WARM, typename WarmOf<G>::type, NoWarm>::type WR;
     if (threadIdx.x < NT / 2) step16_body<1, 0, 1, NT, true, G, WR, true>(lds, M, C, st, n, npad, io, flags, rstep);
     else step16_body<1, 0, 2, NT, true, G, WR, true>(lds, M, C, st, n, npad, io, flags, rstep);

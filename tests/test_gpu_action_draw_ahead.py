@@ -1,5 +1,5 @@
 """The random action of usim_rollout_random does not depend on where in a launch it is drawn.  In resident multi-step launches the arm wave of the split kernel
-draws the NEXT pass's action while it waits for the contact solve (csrc/usim_step16.h DRAW_AHEAD); the first pass of a launch, single-step launches and the
+draws the NEXT pass's action while it waits for the contact solve (csrc/usim_step16.h step16_one AHEAD); the first pass of a launch, single-step launches and the
 single-wave kernels draw in place.  So the rollout blocks must not depend on steps_per_launch, and the `act` rows must be the oracle's random_actions(k) for the same
 seed, environment offset and step index (which pins the counter against an off-by-one).
 

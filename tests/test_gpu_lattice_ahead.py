@@ -1,5 +1,5 @@
 """The split kernel with 16-lane groups in multi-step launches lets its lattice wave run from the integration of pass k straight into the right-hand side and the
-matrix-core solve of pass k + 1 (csrc/usim_step16.h LATTICE_AHEAD): it assumes that no episode of its wave ended, meets the arm wave at hand-off (1) only, and
+matrix-core solve of pass k + 1 (csrc/usim_step16.h lattice_ahead): it assumes that no episode of its wave ended, meets the arm wave at hand-off (1) only, and
 runs the two phases again where the arm wave reports a new episode.  Hand-off (4) and the barrier between the passes exist on the last pass of a launch only.
 None of that may show: the single-step launches (steps_per_launch 1) and the single-wave kernel (lanes_per_env 16) keep the code they had, and every launch
 length must give their bits -- obs, act, rew, done of every step and the state a rollout leaves behind (save_envs: scalars, lattice, warm rows).

@@ -26,9 +26,9 @@ for base, names, title in ((20, names_a, "arm wave"), (30, names_b, "lattice wav
         v = rows[:, base + i] - t0[:, 0]
         print(f"   {nm:36s} {np.median(v):9.0f}")
 # The step boundary (USIM_PROFILE_NSUB > 1: the stamps are those of the last pass of a launch): hand-off (1) of the last pass counted from hand-off (3) of the pass before it.
-# A library with LATTICE_AHEAD records that hand-off (3) (dbg[63] arm wave, dbg[62] lattice wave); for one without, the same path is pieced together from the stamps of one
+# A library whose lattice wave runs ahead (csrc/usim_step16.h lattice_ahead) records that hand-off (3) (dbg[63] arm wave, dbg[62] lattice wave); for an older one, the same path is pieced together from the stamps of one
 # pass, taken as periodic: hand-off (3) -> end of the pass, then start -> hand-off (1) (the barrier between the passes falls between the two pieces).
-# (With LATTICE_AHEAD the lattice wave's "start" lies BEFORE the arm wave's, the zero of this table: it enters the pass while the arm wave finishes the previous one; hand-off
+# (Running ahead, the lattice wave's "start" lies BEFORE the arm wave's, the zero of this table: it enters the pass while the arm wave finishes the previous one; hand-off
 #  (4) exists on the last pass of a launch only, which is the one shown.)
 if rows.shape[1] > 63 and (rows[:, 62:64] > 0).all():
     for col, title in ((63, "arm wave"), (62, "lattice wave")):

@@ -349,6 +349,21 @@ DI void delassus_block(const float (&w)[3][6], const float (&g)[3], const float 
         }
     }
 }
+// The same block with the two partial sums of an entry -- r1 over the even components, r2 over the odd ones -- as the two halves of one packed value: wp[d][p] =
+// (w[d][2p], w[d][2p + 1]), Lk[dd][p] likewise, which is how a record's words arrive from its 16-byte reads (every row of Lambda^-1 w^k starts at an even word).  Each
+// half is the chain of delassus_block on the same operands in the same order, then r1 + r2 and the coupling term: the same bits.  Stated on its own for the reason
+// cone_local_rows12 is: left to the vectoriser the entries are packed across rows, after moving the operands together.
+DI void delassus_block_pairs(const v2f (&wp)[3][3], const float (&g)[3], const v2f (&Lk)[3][3], const float (&gk)[3], float (&Bj)[3][3]) {
+    typedef LaneVec<v2f> P;
+#pragma unroll
+    for (int dd = 0; dd < 3; ++dd) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const v2f r = P::fma(wp[d][2], Lk[dd][2], P::fma(wp[d][1], Lk[dd][1], wp[d][0] * Lk[dd][0]));
+            Bj[d][dd] = fmaf(g[d], gk[dd], r.x + r.y);
+        }
+    }
+}
 // a lane's own diagonal block, regulariser included
 struct Sym3 { float b00, b01, b02, b11, b12, b22; };
 // B[k] WITHOUT the regulariser; written and read only under k < ncr (the iterations run exactly the wave's largest contact count: a slot beyond the count of some
@@ -360,7 +375,8 @@ struct Sym3 { float b00, b01, b02, b11, b12, b22; };
 // four products of an iteration and one rotation adds the halves (delassus_product).  A slot beyond an environment's count holds zeros (its lane published zero rows),
 // so its block is exactly zero.  Everything that leaves contact_solve is masked to lanes 0-7 or to lane k: forces stay zero in the clones (only lane k keeps an
 // increment), the wrench sum and the publications read lanes < MAXC.
-template <bool CLONE, int NB>
+// PAIRS: the blocks through delassus_block_pairs (contact_solve's SHORT).
+template <bool CLONE, bool PAIRS, int NB>
 DI void delassus_blocks(const float* lds, const int eb, const int gl, const int cl, const int ncr, const float (&w)[3][6], const float (&g)[3], const float (&Rd)[3],
                         const float (&Km)[MAXC], float (&B)[NB][3][3], Sym3& bd) {
     const bool upper = CLONE && gl >= 8 && ncr > 4;                      // this half forms the blocks of contacts 4-7 (ncr is wave-uniform)
@@ -368,18 +384,30 @@ DI void delassus_blocks(const float* lds, const int eb, const int gl, const int 
     bd = Sym3{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float4 rk[6];
     load_record(lds, eb, k0, rk);
+    v2f wp[3][3];
+    if constexpr (PAIRS) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { wp[d][0] = v2f{w[d][0], w[d][1]}; wp[d][1] = v2f{w[d][2], w[d][3]}; wp[d][2] = v2f{w[d][4], w[d][5]}; }
+    }
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
         if (j < ncr) {
             float Kmj = Km[j];
             if constexpr (CLONE) Kmj = upper ? Km[4 + j] : Km[j];
-            const float Lk[3][6] = {{rk[0].x, rk[0].y, rk[0].z, rk[0].w, rk[1].x, rk[1].y}, {rk[1].z, rk[1].w, rk[2].x, rk[2].y, rk[2].z, rk[2].w},
-                                    {rk[3].x, rk[3].y, rk[3].z, rk[3].w, rk[4].x, rk[4].y}};
             const float gk[3] = {rk[4].z * Kmj, rk[4].w * Kmj, rk[5].x * Kmj};
-            // (the record is unpacked here, before the next one's reads are issued into the same registers: delassus_block(w, g, rk, Kmj, B[j]) on a copy of the record
-            //  or on one of two buffers put 1 - 12 more spilled registers into the single-wave 16-lane kernels: DESIGN.md section 10)
-            if (j + 1 < NB) load_record(lds, eb, k0 + j + 1, rk);        // the next contact's record, in flight while this block is formed
-            delassus_block(w, g, Lk, gk, B[j]);
+            if constexpr (PAIRS) {
+                const v2f Lk[3][3] = {{{rk[0].x, rk[0].y}, {rk[0].z, rk[0].w}, {rk[1].x, rk[1].y}}, {{rk[1].z, rk[1].w}, {rk[2].x, rk[2].y}, {rk[2].z, rk[2].w}},
+                                      {{rk[3].x, rk[3].y}, {rk[3].z, rk[3].w}, {rk[4].x, rk[4].y}}};
+                if (j + 1 < NB) load_record(lds, eb, k0 + j + 1, rk);
+                delassus_block_pairs(wp, g, Lk, gk, B[j]);
+            } else {
+                const float Lk[3][6] = {{rk[0].x, rk[0].y, rk[0].z, rk[0].w, rk[1].x, rk[1].y}, {rk[1].z, rk[1].w, rk[2].x, rk[2].y, rk[2].z, rk[2].w},
+                                        {rk[3].x, rk[3].y, rk[3].z, rk[3].w, rk[4].x, rk[4].y}};
+                // (the record is unpacked here, before the next one's reads are issued into the same registers: delassus_block(w, g, rk, Kmj, B[j]) on a copy of the record
+                //  or on one of two buffers put 1 - 12 more spilled registers into the single-wave 16-lane kernels: DESIGN.md section 10)
+                if (j + 1 < NB) load_record(lds, eb, k0 + j + 1, rk);    // the next contact's record, in flight while this block is formed
+                delassus_block(w, g, Lk, gk, B[j]);
+            }
             // the lane's own diagonal block, if this half formed it (cl - k0 == j); otherwise the partner lane (the other half, same cl) did: one rotation below
             const bool me = (cl - k0) == j;
             bd.b00 = me ? B[j][0][0] : bd.b00; bd.b01 = me ? B[j][0][1] : bd.b01; bd.b02 = me ? B[j][0][2] : bd.b02;
@@ -565,6 +593,7 @@ DI void contact_wrench(const int gl, const float (&w)[3][6], const float (&g)[3]
 // WR = WarmRec: the solve starts from the kept record `wr` of the lane (matched by element against this pass's contact list) and leaves the new one in it.
 // SHORT: the shortened Jacobi pass of groups that CLONE -- three pieces, each switched by its own constant below (same bits with or without any of them; DESIGN.md
 // section 10).  The split kernel asks for it; the single-wave 16-lane kernels, which run at the register limit and spill more with any of the three, do not.
+// With it the Delassus blocks of the set-up are formed from packed pairs as well (BPAIR; same bits, the single-wave kernels keep their instruction streams).
 template <int G, bool PRE, bool SHORT, class WR>
 DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M, const DevCfg& C, const int nc, const int ncmax, const int* cel,
                       const float* Li, const float* alpha, const float* vs, const float mu, const float vz, const ContactRows& P, float* W, float* gf,
@@ -575,6 +604,7 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
     constexpr bool QUAD = CLONE && SHORT;                                // the summed directions in the quad layout: one DPP move per broadcast word (delassus_product)
     constexpr bool PAIR = CLONE && SHORT;                                // the tangent rows of a contact as one two-float value (cone_local_rows12)
     constexpr bool ONE = CLONE && SHORT;                                 // five to eight contacts: one instantiation of the iterations
+    constexpr bool BPAIR = CLONE && SHORT;                               // the Delassus blocks from packed pairs of row components (delassus_block_pairs; set-up, not the pass)
     typedef ContactLane<CLONE> VT;
     typedef LaneVec<VT> V;
     const int cl = CLONE ? (gl & 7) : gl;
@@ -604,7 +634,7 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
     float B[NB][3][3];
     Sym3 bd;
     delassus_publish(lds, eb, gl, Liw, g);
-    delassus_blocks<CLONE>(lds, eb, gl, cl, ncmax, w, g, Rd, Km, B, bd);
+    delassus_blocks<CLONE, BPAIR>(lds, eb, gl, cl, ncmax, w, g, Rd, Km, B, bd);
     USIM_CSTAMP(dbg, 2);
     VT fv[3] = {V::splat(0.f), V::splat(0.f), V::splat(0.f)}, lamv = V::splat(0.f);
     int myel = -1;

@@ -244,7 +244,7 @@ constexpr int SPLIT_WPR = 4;
 // group sizes (word offsets):
 constexpr int MB_POSE = X16_WORDS;                    // (before it: the 8 x 8 transpose scratch of the arm wave)  site pose 9 words; word 10: length of the broad-phase queue
 constexpr int MB_OP = MB_POSE + 12;                   // op-space quantities: 6 x 8 Lambda^-1, alpha 6, vs 6
-constexpr int MB_W = MB_OP + 64;                      // contact wrench 6, contact count, overflow flag, shell ids 8 (between the steps of a resident launch: the new episode's parameters)
+constexpr int MB_W = MB_OP + 64;                      // contact wrench 6, contact count, overflow flag, the contacts' element ids 8 (between the steps of a resident launch: the new episode's parameters)
 constexpr int MB_Q = MB_W + 16;                       // broad-phase queue (element ids; the spare last word takes the non-candidates' stores)
 constexpr int MB_GOAL = MB_Q + 100;                   // `fixed` mode with physics substeps: the goal anchored at the policy step (12 words)
 // Action drawn ahead (split kernel, resident launches of usim_rollout_random; AHEAD of step16_one): the arm wave draws the NEXT pass's random action in its idle window
@@ -473,7 +473,6 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         RSTAMP(0);
         if constexpr (LA) __builtin_amdgcn_s_setprio(1);                   // (first pass; later ones come here with it raised)
         float* const mb = &lds[mbo];
-        const int* tb_shell = reinterpret_cast<const int*>(lds + TB_SHELL);
         float dz, vz, az;
         torso_motion(C, tphys, dz, vz, az);
         if constexpr (LA) {
@@ -569,8 +568,12 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         int ncmax = 0;
         if constexpr (EARLY) { nc = nc_early; overflow = overflow_early; ncmax = ncmax_early; }
         else {
-#pragma unroll
-            for (int k = MAXC; k >= 1; --k) if (ncmax == 0 && __any(nc >= k)) ncmax = k;
+            // the wave's largest count: nc is uniform over a group, so it is the largest of the four groups' (four lane reads and three scalar maxima in place of eight
+            // votes with a branch each; the same value)
+            static_assert(G == 16, "one lane read per 16-lane group of the wave");
+            const int n0 = __builtin_amdgcn_readlane(nc, 0), n1 = __builtin_amdgcn_readlane(nc, 16), n2 = __builtin_amdgcn_readlane(nc, 32), n3 = __builtin_amdgcn_readlane(nc, 48);
+            const int n01 = n0 > n1 ? n0 : n1, n23 = n2 > n3 ? n2 : n3;
+            ncmax = n01 > n23 ? n01 : n23;
         }
         XSTAMP(1);
         float gf[MAXC], W[6] = {0, 0, 0, 0, 0, 0};
@@ -578,12 +581,21 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
 #pragma unroll
         for (int k = 0; k < MAXC; ++k) { const int ek = __float_as_int(EB(GE_CG + k * CG_WORDS + 6)); gf[k] = 0.f; cel[k] = EARLY ? cel_early[k] : ((k < nc) ? ek : 0); }      // (read, then select: no branch per slot)
         if (ncmax > 0) {
+            // 16-byte reads (the opaque mailbox offset hides the alignment that the static_assert at the layout guarantees): row a of Lambda^-1 is words 8 a .. 8 a + a,
+            // alpha and vs are the twelve words behind the six rows -- eleven reads instead of 33 words one or two at a time
             float alpha[6], vs[6], Lp[21];
+            const float4* const op = reinterpret_cast<const float4*>(&mb[MB_OP]);
 #pragma unroll
             for (int a = 0; a < 6; ++a) {
-                alpha[a] = mb[MB_OP + 48 + a]; vs[a] = mb[MB_OP + 54 + a];
+                const float4 lo = op[2 * a], hi = (a >= 4) ? op[2 * a + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float row[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
 #pragma unroll
-                for (int b = 0; b <= a; ++b) Lp[PK(a, b)] = mb[MB_OP + a * 8 + b];
+                for (int b = 0; b <= a; ++b) Lp[PK(a, b)] = row[b];
+            }
+            {
+                const float4 v0 = op[12], v1 = op[13], v2 = op[14];
+                alpha[0] = v0.x; alpha[1] = v0.y; alpha[2] = v0.z; alpha[3] = v0.w; alpha[4] = v1.x; alpha[5] = v1.y;
+                vs[0] = v1.z; vs[1] = v1.w; vs[2] = v2.x; vs[3] = v2.y; vs[4] = v2.z; vs[5] = v2.w;
             }
             XSTAMP(2);
             contact_solve<G, EARLY, true>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, P, W, gf, dbg, cy.wr);
@@ -592,8 +604,10 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         if (gl == 0) {
             *reinterpret_cast<float4*>(&mb[MB_W]) = make_float4(W[0], W[1], W[2], W[3]);
             *reinterpret_cast<float4*>(&mb[MB_W + 4]) = make_float4(W[4], W[5], __int_as_float(nc), __int_as_float(overflow));
-#pragma unroll
-            for (int k = 0; k < MAXC; ++k) { const int sh = tb_shell[cel[k]]; mb[MB_W + 8 + k] = __int_as_float((k < nc) ? sh : -1); }
+            // the contacts' elements as this wave holds them (0 beyond the count); the arm wave maps them to shell ids where the launch reports contacts
+            static_assert(MAXC == 8, "two 16-byte stores");
+            *reinterpret_cast<float4*>(&mb[MB_W + 8]) = make_float4(__int_as_float(cel[0]), __int_as_float(cel[1]), __int_as_float(cel[2]), __int_as_float(cel[3]));
+            *reinterpret_cast<float4*>(&mb[MB_W + 12]) = make_float4(__int_as_float(cel[4]), __int_as_float(cel[5]), __int_as_float(cel[6]), __int_as_float(cel[7]));
         }
         RSTAMP(5);
         USIM_BAR();                                                 // (3) contact wrench and contact list published
@@ -1069,8 +1083,16 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         const float4 w0 = *reinterpret_cast<const float4*>(&xl[MB_W]), w1 = *reinterpret_cast<const float4*>(&xl[MB_W + 4]);
         W[0] = w0.x; W[1] = w0.y; W[2] = w0.z; W[3] = w0.w; W[4] = w1.x; W[5] = w1.y;
         ncon = __float_as_int(w1.z); overflow = __float_as_int(w1.w);
+        if (io.contacts) {
+            // the contact list is reported: the elements the lattice side left behind the wrench (0 beyond the count: in range) -> shell ids (one uniform branch; rollout
+            // blocks report none and skip the reads and the look-ups)
+            const int* tb_shell = reinterpret_cast<const int*>(lds + TB_SHELL);
+            const float4 e0 = *reinterpret_cast<const float4*>(&xl[MB_W + 8]), e1 = *reinterpret_cast<const float4*>(&xl[MB_W + 12]);
+            const int el[MAXC] = {__float_as_int(e0.x), __float_as_int(e0.y), __float_as_int(e0.z), __float_as_int(e0.w),
+                                  __float_as_int(e1.x), __float_as_int(e1.y), __float_as_int(e1.z), __float_as_int(e1.w)};
 #pragma unroll
-        for (int k = 0; k < MAXC; ++k) con_shell[k] = __float_as_int(xl[MB_W + 8 + k]);
+            for (int k = 0; k < MAXC; ++k) { const int sh = tb_shell[el[k]]; con_shell[k] = (k < ncon) ? sh : -1; }
+        }
     } else if constexpr (TORSO != 0) {
         const int* tb_shell = reinterpret_cast<const int*>(lds + TB_SHELL);
         float dz, vz, az;

@@ -167,28 +167,38 @@ DI bool cone_local_rows12(const float b00, const v2f bt, const v2f bA, const v2f
 //      reference acceleration, regulariser; Km[c] = Linv[e_own][e_c] / m ----
 // The arm-independent half for the lane that holds contact cl (own: the slot is filled; a lane without a contact gets zeros): everything the rows need from the record,
 // the lattice tables and the element state.  It writes through references, so that contact_rows points it at the struct it hands over and contact_solve at its own locals.
+// FLAT (contact_solve's SHORT): no divergent region and no zeros to join behind it.  A lane without a contact runs the owning lanes' straight-line code on a zero
+// frame -- its record's normal, lever arm, element and depth and the two frame entries that are 1 at a zero normal are selected to zero (ten selects) --, so that w,
+// vrel0 and kdist follow as zeros (of either sign) through the unchanged arithmetic, g is selected to +0 (it is published), and Rd, Km, ae0 are finite values of
+// element 0 that nothing outside the lane reads (finite everywhere, exact zeros where they are summed).  An owning lane executes the
+// operations of the other form on the same operands in the same order.
+template <bool FLAT = false>
 DI void contact_row_geometry(const float* lds, const int eb, const int cl, const bool own, const DevModel& M, const DevCfg& C, const int nc, const int* cel, const float vz,
                              float (&w)[3][6], float (&g)[3], float (&Rd)[3], float (&Km)[MAXC], float (&vrel0)[3], float& ae0, float& kdist) {
+    if constexpr (!FLAT) {
 #pragma unroll
-    for (int c = 0; c < MAXC; ++c) Km[c] = 0.f;
+        for (int c = 0; c < MAXC; ++c) Km[c] = 0.f;
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        g[d] = 0.f; Rd[d] = 0.f; vrel0[d] = 0.f;
+        for (int d = 0; d < 3; ++d) {
+            g[d] = 0.f; Rd[d] = 0.f; vrel0[d] = 0.f;
 #pragma unroll
-        for (int a = 0; a < 6; ++a) w[d][a] = 0.f;
+            for (int a = 0; a < 6; ++a) w[d][a] = 0.f;
+        }
+        ae0 = 0.f; kdist = 0.f;
     }
-    ae0 = 0.f; kdist = 0.f;
-    if (own) {
-        const int b = GE_CG + cl * CG_WORDS;
-        f3 nn = mk(EB(b + 0), EB(b + 1), EB(b + 2)), rr = mk(EB(b + 3), EB(b + 4), EB(b + 5));
-        const int e = __float_as_int(EB(b + 6));
-        const float dist = EB(b + 7);
+    if (FLAT || own) {
+        const bool blank = FLAT && !own;                                  // FLAT, no contact in this lane: a zero frame
+        const auto z = [&](const float x) { return blank ? 0.f : x; };    // (the value is read or formed by every lane, then selected: no branch around it)
+        const int b = GE_CG + cl * CG_WORDS;                             // (cl < MAXC: a slot of the environment's record area, filled or stale)
+        f3 nn = mk(z(EB(b + 0)), z(EB(b + 1)), z(EB(b + 2))), rr = mk(z(EB(b + 3)), z(EB(b + 4)), z(EB(b + 5)));
+        const int eown = __float_as_int(EB(b + 6)), e = blank ? 0 : eown;
+        const float dist = z(EB(b + 7));
         // tangent frame without a case distinction (Frisvad 2012: continuous except at n.z = -1; contact normals point from the element towards the probe,
         // and no element sits above it): the iterate of a fixed number of row-by-row sweeps depends on the frame, so float32 and float64 must not be able
         // to choose different ones (oracle: same lines)
         const float aa = -rcp_(1.f + nn.z), bb = nn.x * nn.y * aa;
-        f3 t1 = mk(1.f + nn.x * nn.x * aa, bb, -nn.x);
-        f3 t2 = mk(bb, 1.f + nn.y * nn.y * aa, -nn.y);
+        f3 t1 = mk(z(1.f + nn.x * nn.x * aa), bb, -nn.x);               // (z: the entry is 1 at a zero normal)
+        f3 t2 = mk(bb, z(1.f + nn.y * nn.y * aa), -nn.y);
         f3 ax = mk(lds[TB_AXIS + 3 * e], lds[TB_AXIS + 3 * e + 1], lds[TB_AXIS + 3 * e + 2]);
         const float sde = EB(GE_SD + e);
         float xx = fminf(-dist * (1.0f / SI_WIDTH), 1.f);
@@ -205,23 +215,29 @@ DI void contact_row_geometry(const float* lds, const int eb, const int cl, const
             f3 dir = (d == 0) ? nn : (d == 1 ? t1 : t2);
             f3 rx = cross(rr, dir);
             w[d][0] = dir.x; w[d][1] = dir.y; w[d][2] = dir.z; w[d][3] = rx.x; w[d][4] = rx.y; w[d][5] = rx.z;
-            g[d] = -dot(dir, ax);
-            vrel0[d] = g[d] * sde - dir.z * vz;
+            const float gd = -dot(dir, ax);
+            g[d] = z(gd);                                                 // (published: +0 in a lane without a contact, whatever the signs of its zero frame)
+            vrel0[d] = gd * sde - dir.z * vz;
             Rd[d] = (d == 0) ? Rn * C.rn_scale : Rn * (1.0f / IMPRATIO);    // (two colliding probe geoms: two equal normal rows in parallel = half the regulariser)
         }
     }
 }
 // The arm-dependent half: Lambda^-1 w (Li: Lambda^-1, packed lower 6 x 6) and the residual of every row at zero force, from the site acceleration / velocity of the
 // unconstrained arm (alpha, vs).
+// FLAT: every lane runs the chains; a lane without a contact gets Lambda^-1 w = +0 exactly (fma chains from +0 over finite Lambda^-1 and zero w) and a residual that
+// stays in the lane.
+template <bool FLAT = false>
 DI void contact_row_residual(const bool own, const float* Li, const float* alpha, const float* vs, const float (&w)[3][6], const float (&g)[3], const float (&vrel0)[3],
                              const float ae0, const float kdist, float (&Liw)[3][6], float (&cres)[3]) {
+    if constexpr (!FLAT) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        cres[d] = 0.f;
+        for (int d = 0; d < 3; ++d) {
+            cres[d] = 0.f;
 #pragma unroll
-        for (int a = 0; a < 6; ++a) Liw[d][a] = 0.f;
+            for (int a = 0; a < 6; ++a) Liw[d][a] = 0.f;
+        }
     }
-    if (own) {
+    if (FLAT || own) {
         const float bcon = 2.0f / (SI_DMAX * SR_TC);
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
@@ -593,7 +609,8 @@ DI void contact_wrench(const int gl, const float (&w)[3][6], const float (&g)[3]
 // WR = WarmRec: the solve starts from the kept record `wr` of the lane (matched by element against this pass's contact list) and leaves the new one in it.
 // SHORT: the shortened Jacobi pass of groups that CLONE -- three pieces, each switched by its own constant below (same bits with or without any of them; DESIGN.md
 // section 10).  The split kernel asks for it; the single-wave 16-lane kernels, which run at the register limit and spill more with any of the three, do not.
-// With it the Delassus blocks of the set-up are formed from packed pairs as well (BPAIR; same bits, the single-wave kernels keep their instruction streams).
+// With it the Delassus blocks of the set-up are formed from packed pairs as well (BPAIR; same bits, the single-wave kernels keep their instruction streams), and the
+// rows are formed without a divergent region (FLAT: a lane without a contact runs them on a zero frame; same bits again).
 template <int G, bool PRE, bool SHORT, class WR>
 DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M, const DevCfg& C, const int nc, const int ncmax, const int* cel,
                       const float* Li, const float* alpha, const float* vs, const float mu, const float vz, const ContactRows& P, float* W, float* gf,
@@ -605,6 +622,7 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
     constexpr bool PAIR = CLONE && SHORT;                                // the tangent rows of a contact as one two-float value (cone_local_rows12)
     constexpr bool ONE = CLONE && SHORT;                                 // five to eight contacts: one instantiation of the iterations
     constexpr bool BPAIR = CLONE && SHORT;                               // the Delassus blocks from packed pairs of row components (delassus_block_pairs; set-up, not the pass)
+    constexpr bool FLAT = CLONE && SHORT;                                // the rows without a divergent region (contact_row_geometry, contact_row_residual; set-up, not the pass)
     typedef ContactLane<CLONE> VT;
     typedef LaneVec<VT> V;
     const int cl = CLONE ? (gl & 7) : gl;
@@ -627,8 +645,8 @@ DI void contact_solve(float* lds, const int eb, const int gl, const DevModel& M,
             for (int a = 0; a < 6; ++a) w[d][a] = P.w[d][a];
         }
         ae0 = P.ae0; kdist = P.kdist;
-    } else contact_row_geometry(lds, eb, cl, own, M, C, nc, cel, vz, w, g, Rd, Km, vrel0, ae0, kdist);
-    contact_row_residual(own, Li, alpha, vs, w, g, vrel0, ae0, kdist, Liw, cres);
+    } else contact_row_geometry<FLAT>(lds, eb, cl, own, M, C, nc, cel, vz, w, g, Rd, Km, vrel0, ae0, kdist);
+    contact_row_residual<FLAT>(own, Li, alpha, vs, w, g, vrel0, ae0, kdist, Liw, cres);
     USIM_STAMP(dbg, 9);
     USIM_CSTAMP(dbg, 1);
     float B[NB][3][3];

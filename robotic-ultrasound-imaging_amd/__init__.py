@@ -11,11 +11,11 @@ from .config import default_robosuite_kwargs, load_yaml, make_config
 from .spaces import Box
 from .vec_env import UltrasoundEnv, UltrasoundVecEnv
 
-from . import episode_log, error_metrics, evaluation, imitation, monitor, planner, policy, ppo  # noqa: E402  (checkpoint readers, on-device VecNormalize, MLP policy replay, MPPI planner, PPO learner, behaviour cloning + DAgger, episode statistics + evaluation, CSV dump, error metrics, their device-side evaluation runs)
+from . import episode_log, error_metrics, evaluation, imitation, learner, monitor, planner, policy, ppo  # noqa: E402  (checkpoint readers, on-device VecNormalize, MLP policy replay, MPPI planner, the learners' flat block and core, PPO learner, behaviour cloning + DAgger, episode statistics + evaluation, CSV dump, error metrics, their device-side evaluation runs)
 from .monitor import DeviceMonitor, evaluate_policy, write_scalar_csv  # noqa: E402
 from .evaluation import DeviceEpisodeMetrics, EpisodeRecorder, evaluate_episodes  # noqa: E402
 from .imitation import DAggerTrainer, DemoBuffer, NativeBC, PlannerExpert, PolicyExpert, distill  # noqa: E402
 
 __all__ = ["UltrasoundVecEnv", "UltrasoundEnv", "Box", "default_robosuite_kwargs", "load_yaml", "make_config", "policy", "planner", "ppo", "monitor", "DeviceMonitor",
-           "evaluate_policy", "write_scalar_csv", "episode_log", "error_metrics", "evaluation", "DeviceEpisodeMetrics", "EpisodeRecorder", "evaluate_episodes", "imitation", "DemoBuffer", "NativeBC",
+           "evaluate_policy", "write_scalar_csv", "episode_log", "error_metrics", "evaluation", "DeviceEpisodeMetrics", "EpisodeRecorder", "evaluate_episodes", "imitation", "learner", "DemoBuffer", "NativeBC",
            "PolicyExpert", "PlannerExpert", "DAggerTrainer", "distill", "_lib"]

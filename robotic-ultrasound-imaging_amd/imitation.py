@@ -1,6 +1,7 @@
 """Behaviour cloning and DAgger on the device: what the `imitation` package offers users of stable-baselines3 (bc.BC, dagger.SimpleDAggerTrainer), with the
 minibatch loss and gradient as one library call -- usim_bc_grad (include/usim.h; csrc/usim_ppo.hip: further instances of the PPO gradient kernel) -- and the
-optimiser step as usim_ppo_adam on the flat parameter block of ppo.flatten_parameters.  It connects the pieces that stand beside each other: a planner
+optimiser step as usim_ppo_adam on the flat parameter block of learner.flatten_parameters; the block, that step and the epoch loop are learner.FlatLearner's, the
+core ppo.NativePPO stands on as well.  It connects the pieces that stand beside each other: a planner
 (planner.MPPIPlanner) or a shipped checkpoint becomes a network that costs one forward pass per decision, with a critic where the expert has one, and
 ppo.NativePPO built afterwards on the same policy continues from the same words.
 
@@ -19,22 +20,12 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .learner import FlatLearner, _check_shapes
 from .policy import DeviceVecNormalize
-from .ppo import FIELDS, _check_shapes, _is_flat, flatten_parameters
 
 LOSSES = {"nll": _lib.BC_NLL, "mse": _lib.BC_MSE}
 STAT_NAMES = ("bc/loss", "bc/neglogp", "bc/action_mse", "bc/value_loss", "bc/entropy_loss", "bc/grad_norm", "bc/optimizer_steps")
 ROUND_NAMES = ("dagger/round", "dagger/beta", "dagger/rows", "dagger/expert_share")
-
-
-def _frozen_obs(vecnorm, obs):
-    """vecnorm.normalize_obs with the statistics only read, whatever vecnorm.training says"""
-    was = vecnorm.training
-    vecnorm.training = False
-    try:
-        return vecnorm.normalize_obs(obs)
-    finally:
-        vecnorm.training = was
 
 
 class DemoBuffer:
@@ -89,13 +80,13 @@ class DemoBuffer:
         return sl(self.obs), sl(self.act), (sl(self.value) if self.has_value else None)
 
 
-class NativeBC:
+class NativeBC(FlatLearner):
     """Behaviour cloning of the rows of a DemoBuffer into a policy.MlpActorCritic (19 -> 256 -> 128, A <= 8): per minibatch one usim_bc_grad and one
     usim_ppo_adam.  loss: "nll" (-log-prob of the expert's action: imitation's BC, trains log_std too) or "mse" (squared error of the mean; log_std then moves
     by the entropy term alone).  vf_coef > 0 with value targets in the buffer also regresses the critic on them; a buffer without value targets has no value
     term, whatever vf_coef says.  batch_size=None: one eighth of the buffer's rows at train() time.
 
-    The policy is flattened (ppo.flatten_parameters) if it is not flat yet -- as with ppo.NativePPO, BEFORE any collector that records parameter addresses
+    The policy is flattened (learner.flatten_parameters) if it is not flat yet -- as with ppo.NativePPO, BEFORE any collector that records parameter addresses
     (policy.FusedRollout) is built; a NativePPO constructed afterwards on the same policy trains the same words.  `vecnorm` is only read: train() normalises
     with its statistics as they are and never updates them; fit_normalizer() sets them from the buffer for demonstrations that come without statistics.
     Refusals are ValueErrors raised before any library call."""
@@ -109,38 +100,15 @@ class NativeBC:
             raise ValueError(f"policy shapes: act_dim {A} is not the buffer's {demos.act_dim}")
         if int(demos.obs_dim) != _lib.OBS_DIM:
             raise ValueError(f"the buffer holds observations of {demos.obs_dim} words, the policy reads {_lib.OBS_DIM}")
-        dev = torch.device(demos.device)
-        for p in policy.parameters():
-            if p.device != dev:
-                raise ValueError(f"policy is on device {p.device}, the buffer on {dev}")
-        if int(n_epochs) < 1:
-            raise ValueError("n_epochs must be at least 1")
         if batch_size is not None and int(batch_size) < 1:
             raise ValueError(f"batch_size {batch_size} outside 1 .. the buffer's rows")
-        theta = getattr(policy, "_flat_theta", None)
-        if theta is None or not _is_flat(policy, theta):
-            theta = flatten_parameters(policy)
-        self.policy, self.vecnorm, self.demos, self.loss, self.act_dim, self.device = policy, vecnorm, demos, loss, A, dev
-        self.learning_rate, self.batch_size, self.n_epochs = float(learning_rate), None if batch_size is None else int(batch_size), int(n_epochs)
-        self.ent_coef, self.vf_coef, self.max_grad_norm, self.adam_eps = float(ent_coef), float(vf_coef), float(max_grad_norm), float(adam_eps)
-        self.lib = _lib.load()
-        self.theta, self.params = theta, theta.numel()
-        z = lambda n, dtype=torch.float32: torch.zeros(n, dtype=dtype, device=dev)
-        self.grad, self.exp_avg, self.exp_avg_sq = z(self.params), z(self.params), z(self.params)
-        self.step_count = z(1, torch.int32)                                   # Adam's step, advanced on the device
-        self.stats, self.first_stats = z(_lib.PPO_STATS), z(_lib.PPO_STATS)   # of the last minibatch; of the first minibatch of the last train()
+        super().__init__(policy, A, demos.device, "buffer", demos.capacity, n_epochs=n_epochs, max_grad_norm=max_grad_norm, adam_eps=adam_eps, seed=seed)
+        self.vecnorm, self.demos, self.loss = vecnorm, demos, loss
+        self.learning_rate, self.batch_size = float(learning_rate), None if batch_size is None else int(batch_size)
+        self.ent_coef, self.vf_coef = float(ent_coef), float(vf_coef)
         self.first_minibatch = {}                                             # first_stats under the names of train()'s result
         self.last_extra = []
         self.history = []
-        self._work = z(int(self.lib.usim_ppo_work_floats(A)))
-        self._index = z(demos.capacity, torch.int32)
-        self.generator = torch.Generator(device=dev)
-        self.generator.manual_seed(int(seed))
-        ptr = {name: dict(policy.named_parameters())[path].data_ptr() for name, path in FIELDS}
-        self._net = _lib.UsimPolicyNet(*(ptr[name] for name, _ in FIELDS), None)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def minibatch_step(self, data, index, batch, lr=None):
         """one usim_bc_grad + one usim_ppo_adam on the rows `index` (an int32 device tensor, or None: rows 0 .. batch - 1) of `data` = (normalised observations
@@ -149,11 +117,8 @@ class NativeBC:
         value = data[2] if len(data) > 2 else None
         b = _lib.UsimBcBatch(obs.data_ptr(), act.data_ptr(), None if value is None else value.data_ptr(), None if index is None else index.data_ptr(),
                              obs.shape[0], int(batch), self.act_dim, LOSSES[self.loss], self.ent_coef, self.vf_coef)
-        stream = self._stream()
-        _lib.check(self.lib, self.lib.usim_bc_grad(C.byref(self._net), C.byref(b), self._work.data_ptr(), self.grad.data_ptr(), self.stats.data_ptr(), stream))
-        _lib.check(self.lib, self.lib.usim_ppo_adam(self.theta.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                                    self.step_count.data_ptr(), self.params, self.learning_rate if lr is None else float(lr), 0.9, 0.999,
-                                                    self.adam_eps, self.max_grad_norm, self.stats.data_ptr(), stream))
+        self._check(self.lib.usim_bc_grad(C.byref(self._net), C.byref(b), self._work.data_ptr(), self.grad.data_ptr(), self.stats.data_ptr(), self._stream()))
+        self.adam_step(self.learning_rate if lr is None else lr)
 
     def _named(self, s, steps):
         return dict(zip(STAT_NAMES, (s[5], -s[4], s[3], s[1], s[2], s[6], steps)))
@@ -170,16 +135,8 @@ class NativeBC:
         batch = N // 8 if self.batch_size is None else self.batch_size
         if not 1 <= batch <= N:
             raise ValueError(f"batch_size {batch} outside 1 .. the buffer's {N} rows")
-        data = (_frozen_obs(self.vecnorm, d.obs[:N]).contiguous(), d.act[:N]) + ((d.value[:N],) if d.has_value and self.vf_coef != 0.0 else ())
-        steps = 0
-        for _ in range(self.n_epochs):
-            self._index[:N].copy_(torch.randperm(N, device=self.device, generator=self.generator))
-            for i in range(0, N, batch):
-                n = min(batch, N - i)
-                self.minibatch_step(data, self._index[i:i + n], n)
-                if steps == 0:
-                    self.first_stats.copy_(self.stats)
-                steps += 1
+        data = (self.vecnorm.normalize_obs(d.obs[:N], update=False).contiguous(), d.act[:N]) + ((d.value[:N],) if d.has_value and self.vf_coef != 0.0 else ())
+        steps = self.run_epochs(N, batch, lambda index, n: self.minibatch_step(data, index, n))
         parts = (self.stats, self.first_stats) + (() if extra is None else (extra.reshape(-1).to(torch.float32),))
         s = torch.cat(parts).tolist()                                          # the one read
         n = _lib.PPO_STATS
@@ -208,7 +165,7 @@ class PolicyExpert:
 
     @torch.no_grad()
     def label(self, obs_raw):
-        mean, value = self.policy.forward(_frozen_obs(self.vecnorm, obs_raw))
+        mean, value = self.policy.forward(self.vecnorm.normalize_obs(obs_raw, update=False))
         return torch.max(torch.min(mean, self.high), self.low), value
 
 
@@ -274,7 +231,7 @@ class DAggerTrainer:
     def student_action(self, obs_raw):
         """the student's action on raw observations: the learner's policy under the learner's vecnorm (frozen), clipped to the action box"""
         L = self.learner
-        return L.policy.predict(_frozen_obs(L.vecnorm, obs_raw), self.student_deterministic, self.low, self.high, self.generator)
+        return L.policy.predict(L.vecnorm.normalize_obs(obs_raw, update=False), self.student_deterministic, self.low, self.high, self.generator)
 
     def round(self):
         beta = float(self.beta(self.round_index))

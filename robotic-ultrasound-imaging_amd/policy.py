@@ -197,8 +197,9 @@ class DeviceVecNormalize:
         m2 = var * count + bv * bn + delta * delta * count * bn / tot
         mean.copy_(new_mean); var.copy_(m2 / tot); count.copy_(tot)
 
-    def normalize_obs(self, obs):
-        if self.training:
+    def normalize_obs(self, obs, update=None):
+        """update: None -- the statistics take `obs` in first when self.training says so; False -- they are only read, whatever self.training says"""
+        if self.training if update is None else update:
             self._update(self.obs_mean, self.obs_var, self._obs_count, obs)
         out = (obs.to(torch.float64) - self.obs_mean) / torch.sqrt(self.obs_var + self.epsilon)
         return torch.clamp(out, -self.clip_obs, self.clip_obs).to(torch.float32)
@@ -282,6 +283,20 @@ class MlpActorCritic(torch.nn.Module):
         if low is not None:
             act = torch.max(torch.min(act, high), low)
         return act
+
+
+# the header's field order (usim_policy_net) as attribute paths of MlpActorCritic
+FIELDS = (("pi_w1", "policy_net.0.weight"), ("pi_b1", "policy_net.0.bias"), ("pi_w2", "policy_net.2.weight"), ("pi_b2", "policy_net.2.bias"),
+          ("act_w", "action_net.weight"), ("act_b", "action_net.bias"), ("vf_w1", "value_net_body.0.weight"), ("vf_b1", "value_net_body.0.bias"),
+          ("vf_w2", "value_net_body.2.weight"), ("vf_b2", "value_net_body.2.bias"), ("val_w", "value_net.weight"), ("val_b", "value_net.bias"),
+          ("log_std", "log_std"))
+
+
+def policy_net(policy, w2_packed=None):
+    """usim_policy_net of a MlpActorCritic: the addresses of its parameters as they are now, in FIELDS order, and of `w2_packed` (a tensor for usim_policy_pack's
+    output; None where no kernel reads it: the learners)"""
+    params = dict(policy.named_parameters())
+    return _lib.UsimPolicyNet(*(params[path].data_ptr() for _, path in FIELDS), None if w2_packed is None else w2_packed.data_ptr())
 
 
 @torch.no_grad()
@@ -403,11 +418,7 @@ def _rollout_step(env, policy, vecnorm, low, high, obs, episode_start, generator
 @torch.no_grad()
 def _bootstrap_value(policy, vecnorm, obs):
     """SB3 bootstraps with the value of the stored, already normalised `_last_obs`: the statistics are not updated a second time"""
-    was_training, vecnorm.training = vecnorm.training, False
-    try:
-        return policy.forward(vecnorm.normalize_obs(obs))[1]
-    finally:
-        vecnorm.training = was_training
+    return policy.forward(vecnorm.normalize_obs(obs, update=False))[1]
 
 
 @torch.no_grad()
@@ -560,14 +571,10 @@ class FusedRollout:
             if p_.device != dev or p_.dtype != torch.float32 or not p_.is_contiguous():
                 raise ValueError("policy parameters must be contiguous float32 tensors on the environment's device")
         ptr = lambda t: t.data_ptr()
-        pn, vb = policy.policy_net, policy.value_net_body
-        self._net = _lib.UsimPolicyNet(ptr(pn[0].weight), ptr(pn[0].bias), ptr(pn[2].weight), ptr(pn[2].bias), ptr(policy.action_net.weight), ptr(policy.action_net.bias),
-                                       ptr(vb[0].weight), ptr(vb[0].bias), ptr(vb[2].weight), ptr(vb[2].bias), ptr(policy.value_net.weight), ptr(policy.value_net.bias),
-                                       ptr(policy.log_std), None)
         # layer-2 weights of both networks in the order the matrix-core operands consume them (usim_policy_pack; include/usim.h): packed again before every eager
         # launch and as the first policy node of a recorded rollout, so a parameter update between rollouts is seen as before
         self._w2_packed = torch.zeros(_lib.POLICY_PACKED, dtype=torch.float32, device=dev)
-        self._net.w2_packed = self._w2_packed.data_ptr()
+        self._net = policy_net(policy, self._w2_packed)
         vn = vecnorm
         self._scratch = torch.zeros(_lib.POLICY_SCRATCH, dtype=torch.float64, device=dev)
         self._stats = _lib.UsimNormStats(ptr(vn.obs_mean), ptr(vn.obs_var), ptr(vn._obs_count), ptr(vn.ret_mean), ptr(vn.ret_var), ptr(vn._ret_count), ptr(vn.returns),

@@ -1,8 +1,8 @@
 """The PPO learner on the device: stable-baselines3's `PPO.train` (the `model.learn` of src/rl.py:143) as two library calls per minibatch -- usim_ppo_grad (loss,
 statistics and the gradient for every parameter of the shipped MlpPolicy) and usim_ppo_adam (clip_grad_norm_ + Adam.step) on ONE flat parameter block
-(include/usim.h; csrc/usim_ppo.hip).  The collector (policy.FusedRollout), the running statistics (policy.DeviceVecNormalize), the buffer
-(policy.DeviceRolloutBuffer) and the checkpoint writer (policy.save_sb3_zip) are the ones of policy.py: the module's parameters become views into the flat block,
-so all of them keep working on the same memory.
+(include/usim.h; csrc/usim_ppo.hip).  The block, the Adam call and the epoch loop are learner.py's (FlatLearner, shared with imitation.NativeBC).  The collector
+(policy.FusedRollout), the running statistics (policy.DeviceVecNormalize), the buffer (policy.DeviceRolloutBuffer) and the checkpoint writer (policy.save_sb3_zip)
+are the ones of policy.py: the module's parameters become views into the flat block, so all of them keep working on the same memory.
 
     policy = MlpActorCritic(19, env.action_dim).to(env.device)
     theta = flatten_parameters(policy)                     # BEFORE the collector is built: it records the parameters' addresses
@@ -26,143 +26,13 @@ import numpy as np
 import torch
 
 from . import _lib
+# (the flat block's functions are learner.py's; they stay available under the names this module has always offered)
+from .learner import FIELDS, FlatLearner, _check_shapes, _field_shapes, _is_flat, adam_state_from_flat, adam_state_to_flat  # noqa: F401
+from .learner import flatten_parameters, ppo_params, state_dict_to_flat  # noqa: F401
 from .policy import load_sb3_zip, load_vecnormalize_pkl, save_sb3_zip, save_vecnormalize_pkl
 
-# the header's field order (usim_policy_net) as attribute paths of policy.MlpActorCritic
-FIELDS = (("pi_w1", "policy_net.0.weight"), ("pi_b1", "policy_net.0.bias"), ("pi_w2", "policy_net.2.weight"), ("pi_b2", "policy_net.2.bias"),
-          ("act_w", "action_net.weight"), ("act_b", "action_net.bias"), ("vf_w1", "value_net_body.0.weight"), ("vf_b1", "value_net_body.0.bias"),
-          ("vf_w2", "value_net_body.2.weight"), ("vf_b2", "value_net_body.2.bias"), ("val_w", "value_net.weight"), ("val_b", "value_net.bias"),
-          ("log_std", "log_std"))
 STAT_NAMES = ("train/policy_gradient_loss", "train/value_loss", "train/entropy_loss", "train/approx_kl", "train/clip_fraction", "train/loss",
               "train/explained_variance")       # the first six: usim_ppo_grad's statistics of the last minibatch; the seventh: usim_explained_variance on the buffer
-_SB3_PREFIX = (("mlp_extractor.policy_net.", "policy_net."), ("mlp_extractor.value_net.", "value_net_body."))      # policy.pth's names -> the module's
-
-
-def ppo_params(act_dim):
-    """usim_ppo_params: floats of the flat parameter / gradient block"""
-    return 76032 + 130 * int(act_dim) + 129
-
-
-def _field_shapes(act_dim):
-    A = int(act_dim)
-    return ((256, 19), (256,), (128, 256), (128,), (A, 128), (A,), (256, 19), (256,), (128, 256), (128,), (1, 128), (1,), (A,))
-
-
-def _check_shapes(policy):
-    """-> act_dim; ValueError unless the module is the MlpPolicy the kernels implement: 19 -> 256 -> 128 -> A / 1, A <= 8"""
-    params = dict(policy.named_parameters())
-    if set(params) != {path for _, path in FIELDS}:
-        raise ValueError("policy shapes: not a policy.MlpActorCritic with two hidden layers per network")
-    A = int(params["log_std"].shape[0])
-    if not 1 <= A <= 8:
-        raise ValueError(f"policy shapes: act_dim {A} outside 1 .. 8")
-    for (name, path), shape in zip(FIELDS, _field_shapes(A)):
-        if tuple(params[path].shape) != shape:
-            raise ValueError(f"policy shapes: {path} is {tuple(params[path].shape)}, the learner's kernels implement 19 -> 256 -> 128 -> A / 1 ({name}: {shape})")
-    return A
-
-
-def flatten_parameters(policy):
-    """Re-seat the parameters of a policy.MlpActorCritic (19 -> 256 -> 128, A <= 8) as views into ONE contiguous float32 tensor in the order of include/usim.h
-    (pi_w1 pi_b1 pi_w2 pi_b2 act_w act_b vf_w1 vf_b1 vf_w2 vf_b2 val_w val_b log_std) and return that tensor.  The values are kept; the module, a collector built
-    AFTERWARDS and save_sb3_zip read and write the same memory as the learner.  Calling it again on a flattened module returns the same tensor."""
-    A = _check_shapes(policy)
-    params = dict(policy.named_parameters())
-    theta = getattr(policy, "_flat_theta", None)
-    if theta is not None and _is_flat(policy, theta):
-        return theta
-    first = params[FIELDS[0][1]]
-    theta = torch.empty(ppo_params(A), dtype=torch.float32, device=first.device)
-    o = 0
-    with torch.no_grad():
-        for (_, path), shape in zip(FIELDS, _field_shapes(A)):
-            p, n = params[path], 1
-            for s in shape:
-                n *= s
-            view = theta[o:o + n].view(shape)
-            view.copy_(p.detach().to(torch.float32))
-            p.data = view
-            o += n
-    assert o == theta.numel()
-    policy._flat_theta = theta
-    return theta
-
-
-def _is_flat(policy, theta):
-    params, o = dict(policy.named_parameters()), 0
-    for _, path in FIELDS:
-        p = params[path]
-        if p.device != theta.device or p.dtype != torch.float32 or p.data_ptr() != theta.data_ptr() + 4 * o:
-            return False
-        o += p.numel()
-    return o == theta.numel()
-
-
-def _field_offsets(act_dim):
-    """module path -> (offset, shape) in the flat block"""
-    out, o = {}, 0
-    for (_, path), shape in zip(FIELDS, _field_shapes(act_dim)):
-        out[path] = (o, shape)
-        o += math.prod(shape)
-    return out
-
-
-def adam_state_from_flat(exp_avg, exp_avg_sq, step, names, act_dim, lr=3e-4, eps=1e-5):
-    """flat Adam moments in FIELDS order + the step count -> the state dict of torch.optim.Adam as `policy.optimizer.pth` of an SB3 checkpoint holds it
-    (policy.adam_state_dict shows the layout): CPU tensors per parameter, numbered in the order `names` (module paths in state-dict order).  Device-free when its
-    inputs are; step 0 writes a fresh optimizer (empty state), as torch does before the first step."""
-    off, state = _field_offsets(act_dim), {}
-    if int(step) > 0:
-        for i, name in enumerate(names):
-            o, shape = off[name]
-            cut = lambda t: t[o:o + math.prod(shape)].view(shape).detach().cpu().clone()
-            state[i] = {"step": int(step), "exp_avg": cut(exp_avg), "exp_avg_sq": cut(exp_avg_sq)}
-    return {"state": state, "param_groups": [{"lr": float(lr), "betas": (0.9, 0.999), "eps": float(eps), "weight_decay": 0, "amsgrad": False,
-                                               "params": list(range(len(names)))}]}
-
-
-def adam_state_to_flat(opt, names, act_dim):
-    """the inverse of adam_state_from_flat: -> (exp_avg, exp_avg_sq [ppo_params(act_dim)] float32 CPU tensors in FIELDS order, step).  An empty state gives
-    zero moments and step 0; `step` may be an int or a 0-d tensor (newer torch writes tensors).  ValueError: a state that is not one entry per parameter, a
-    moment whose shape is not the parameter's, per-parameter steps that differ (the learner keeps ONE step count)."""
-    off = _field_offsets(act_dim)
-    m, v = torch.zeros(ppo_params(act_dim), dtype=torch.float32), torch.zeros(ppo_params(act_dim), dtype=torch.float32)
-    state = opt.get("state", {})
-    if len(state) == 0:
-        return m, v, 0
-    if sorted(state) != list(range(len(names))) or set(names) != set(off):
-        raise ValueError(f"optimizer state: {len(state)} entries for the learner's {len(names)} parameters")
-    steps = set()
-    for i, name in enumerate(names):
-        o, shape = off[name]
-        st = state[i]
-        steps.add(int(st["step"].item()) if torch.is_tensor(st["step"]) else int(st["step"]))
-        for key, dst in (("exp_avg", m), ("exp_avg_sq", v)):
-            t = torch.as_tensor(st[key])
-            if tuple(t.shape) != shape:
-                raise ValueError(f"optimizer state: {key} of {name} is {tuple(t.shape)}, the learner's parameter {shape}")
-            dst[o:o + math.prod(shape)].copy_(t.detach().to(device="cpu", dtype=torch.float32).reshape(-1))
-    if len(steps) != 1:
-        raise ValueError(f"optimizer state: per-parameter Adam steps differ ({sorted(steps)}); the learner keeps one step count")
-    return m, v, steps.pop()
-
-
-def state_dict_to_flat(sd, act_dim):
-    """policy.pth of an SB3 checkpoint (load_sb3_zip) -> the flat parameter block (float32, CPU); ValueError unless its names and shapes are the learner's"""
-    mapped = {}
-    for k, t in sd.items():
-        for a, b in _SB3_PREFIX:
-            k = k.replace(a, b)
-        mapped[k] = torch.as_tensor(t)
-    off = _field_offsets(act_dim)
-    if set(mapped) != set(off):
-        raise ValueError(f"checkpoint shapes: parameters {sorted(set(mapped) ^ set(off))} do not match the learner's policy")
-    theta = torch.empty(ppo_params(act_dim), dtype=torch.float32)
-    for name, (o, shape) in off.items():
-        if tuple(mapped[name].shape) != shape:
-            raise ValueError(f"checkpoint shapes: {name} is {tuple(mapped[name].shape)}, the learner's {shape}")
-        theta[o:o + math.prod(shape)].copy_(mapped[name].detach().to(device="cpu", dtype=torch.float32).reshape(-1))
-    return theta
 
 
 def _positive(name, x):
@@ -183,7 +53,7 @@ def _scheduled(name, x):
     return _positive(name, x)
 
 
-class NativePPO:
+class NativePPO(FlatLearner):
     """stable-baselines3's PPO update on the library's learner kernels, with SB3's defaults (what src/rl.py:143 runs with): learning_rate 3e-4, n_epochs 10,
     clip_range 0.2, ent_coef 0, vf_coef 0.5, max_grad_norm 0.5, per-minibatch advantage normalisation, Adam(eps 1e-5).
 
@@ -210,30 +80,13 @@ class NativePPO:
         batch_size = rollout // 8 if batch_size is None else int(batch_size)
         if not 1 <= batch_size <= rollout:
             raise ValueError(f"batch_size {batch_size} outside 1 .. the rollout's {rollout} samples")
-        if int(n_epochs) < 1:
-            raise ValueError("n_epochs must be at least 1")
-        for p in policy.parameters():
-            if p.device != dev:
-                raise ValueError(f"policy is on device {p.device}, the environment on {dev}")
-        theta = getattr(policy, "_flat_theta", None)
-        if theta is None or not _is_flat(policy, theta):
-            if collector is not None:
-                raise ValueError("flatten_parameters(policy) must be called before the collector is built: it has recorded the parameters' addresses")
-            theta = flatten_parameters(policy)
-        self.env, self.policy, self.vecnorm, self.buffer, self.collector = env, policy, vecnorm, buffer, collector
-        self.learning_rate, self.n_epochs, self.batch_size, self.rollout = learning_rate, int(n_epochs), batch_size, rollout
+        super().__init__(policy, A, dev, "environment", rollout, n_epochs=n_epochs, max_grad_norm=max_grad_norm, adam_eps=adam_eps, seed=seed, collector=collector)
+        self.env, self.vecnorm, self.buffer, self.collector = env, vecnorm, buffer, collector
+        self.learning_rate, self.batch_size, self.rollout = learning_rate, batch_size, rollout
         self.clip_range = clip_range if callable(clip_range) else float(clip_range)
-        self.ent_coef, self.vf_coef, self.max_grad_norm = float(ent_coef), float(vf_coef), float(max_grad_norm)
-        self.clip_range_vf, self.target_kl = clip_range_vf, target_kl
-        self.normalize_advantage, self.adam_eps, self.act_dim = bool(normalize_advantage), float(adam_eps), A
-        self.progress_remaining = 1.0
-        self.lib = _lib.load()
-        self.theta, self.params = theta, theta.numel()
+        self.ent_coef, self.vf_coef, self.normalize_advantage = float(ent_coef), float(vf_coef), bool(normalize_advantage)
+        self.clip_range_vf, self.target_kl, self.progress_remaining = clip_range_vf, target_kl, 1.0
         z = lambda n, dtype=torch.float32: torch.zeros(n, dtype=dtype, device=dev)
-        self.grad, self.exp_avg, self.exp_avg_sq = z(self.params), z(self.params), z(self.params)
-        self.step_count = z(1, torch.int32)                                   # Adam's step, advanced on the device
-        self.stats = z(_lib.PPO_STATS)
-        self.first_stats = z(_lib.PPO_STATS)                                  # the statistics of the first minibatch of the last update()
         self._ev = z(1)                                                       # train/explained_variance of the last update() (usim_explained_variance)
         self.gate = z(_lib.PPO_GATE_WORDS, torch.int32)                       # stop flag, gradient calls, optimizer steps of the current update(), 0
         self._std = z(1)                                                      # train/std of the last update(): mean(exp(log_std))
@@ -242,15 +95,6 @@ class NativePPO:
         self.set_evaluation(None)                                             # learn(): no periodic evaluation until set_evaluation(every, eval_env, ...)
         self.history = []                                                     # learn(): one dict of logger scalars per iteration
         self.num_timesteps = 0                                                # environment steps collected by learn() so far
-        self._work = z(int(self.lib.usim_ppo_work_floats(A)))
-        self._index = torch.zeros(rollout, dtype=torch.int32, device=dev)
-        self.generator = torch.Generator(device=dev)
-        self.generator.manual_seed(int(seed))
-        ptr = {name: dict(policy.named_parameters())[path].data_ptr() for name, path in FIELDS}
-        self._net = _lib.UsimPolicyNet(*(ptr[name] for name, _ in FIELDS), None)
-
-    def _check(self, rc):
-        _lib.check(self.lib, rc, None)
 
     def _flat(self, x):
         """a [T, n, ...] buffer tensor in SB3's swap_and_flatten order (environment-major), contiguous"""
@@ -281,11 +125,8 @@ class NativePPO:
         b = _lib.UsimPpoBatch(obs.data_ptr(), act.data_ptr(), lp.data_ptr(), adv.data_ptr(), ret.data_ptr(), None if index is None else index.data_ptr(),
                               obs.shape[0], int(batch), self.act_dim, int(self.normalize_advantage), self.current_clip_range(), self.ent_coef, self.vf_coef, 0.0,
                               data[5].data_ptr() if len(data) > 5 else None, self.gate.data_ptr(), cvf or 0.0, self.target_kl or 0.0)
-        stream = self.env._stream()
-        self._check(self.lib.usim_ppo_grad(C.byref(self._net), C.byref(b), self._work.data_ptr(), self.grad.data_ptr(), self.stats.data_ptr(), stream))
-        self._check(self.lib.usim_ppo_adam_gated(self.theta.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                                 self.step_count.data_ptr(), self.params, self.current_lr() if lr is None else float(lr), 0.9, 0.999,
-                                                 self.adam_eps, self.max_grad_norm, self.stats.data_ptr(), self.gate.data_ptr(), stream))
+        self._check(self.lib.usim_ppo_grad(C.byref(self._net), C.byref(b), self._work.data_ptr(), self.grad.data_ptr(), self.stats.data_ptr(), self._stream()))
+        self.adam_step(self.current_lr() if lr is None else lr, self.gate)
 
     def update(self):
         """PPO.train on the buffer as it is: n_epochs passes, each a torch.randperm on the device cut into minibatches of batch_size (the trailing partial one
@@ -298,18 +139,11 @@ class NativePPO:
         if not b.full:
             raise RuntimeError("rollout buffer is not full")
         values, returns = b.values.contiguous(), b.returns.contiguous()
-        self._check(self.lib.usim_explained_variance(values.data_ptr(), returns.data_ptr(), values.numel(), self._ev.data_ptr(), self.env._stream()))
+        self._check(self.lib.usim_explained_variance(values.data_ptr(), returns.data_ptr(), values.numel(), self._ev.data_ptr(), self._stream()))
         data = tuple(self._flat(x) for x in (b.observations, b.actions, b.log_probs, b.advantages, b.returns, b.values))
-        N, lr, first = self.rollout, self.current_lr(), True
+        lr = self.current_lr()
         self.gate.zero_()
-        for _ in range(self.n_epochs):
-            self._index.copy_(torch.randperm(N, device=self._index.device, generator=self.generator))
-            for i in range(0, N, self.batch_size):
-                n = min(self.batch_size, N - i)
-                self.minibatch_step(data, self._index[i:i + n], n, lr)
-                if first:
-                    self.first_stats.copy_(self.stats)
-                    first = False
+        self.run_epochs(self.rollout, self.batch_size, lambda index, n: self.minibatch_step(data, index, n, lr))
         if self.collector is not None and hasattr(self.collector, "pack"):
             self.collector.pack()
         torch.mean(torch.exp(self.policy.log_std.detach()), dim=0, keepdim=True, out=self._std)

@@ -49,7 +49,7 @@ def _check(name, got, want, bound):
 def test_three_minibatch_steps_against_the_references(usim, loss, valued):
     pr, bc = _learner(usim, seed=4, valued=valued, loss=loss, learning_rate=1e-3)
     d = bc.demos
-    obs_n = usim.imitation._frozen_obs(bc.vecnorm, d.obs[:ROWS]).contiguous()
+    obs_n = bc.vecnorm.normalize_obs(d.obs[:ROWS], update=False).contiguous()
     data = (obs_n, d.act[:ROWS]) + ((d.value[:ROWS],) if valued else ())
     perm = np.random.default_rng(9).permutation(ROWS).astype(np.int32)
     x, act, value = obs_n.cpu().numpy(), pr["act"], pr["value"]

@@ -1,6 +1,7 @@
 """usim_bc_grad on the host side -- declared in include/usim.h, bound by _lib.SYMBOLS, exported by the library built here, its argument checks answering
 USIM_ERR_INVALID before anything is enqueued (NULL or made-up pointers that no kernel may ever see) -- and the device-free side of imitation.py: DemoBuffer's
 ring on CPU tensors, every ValueError of NativeBC, PlannerExpert and DAggerTrainer with stand-in objects.  Runs without a GPU."""
+import copy
 import ctypes as C
 import re
 import subprocess
@@ -209,9 +210,30 @@ def test_native_bc_flattens_and_fit_normalizer_sets_the_statistics(usim, monkeyp
     o = obs.double()
     assert torch.equal(vn.obs_mean, o.mean(0)) and torch.equal(vn.obs_var, o.var(0, unbiased=False)) and float(vn._obs_count) == 40.0
     before = vn.obs_mean.clone()
-    out = usim.imitation._frozen_obs(vn, obs)                                 # normalising for train() reads the statistics and leaves them alone
+    out = vn.normalize_obs(obs, update=False)                                 # normalising for train() reads the statistics and leaves them alone
     assert torch.equal(vn.obs_mean, before) and float(vn._obs_count) == 40.0 and vn.training is True
     assert out.dtype == torch.float32 and float(out.abs().max()) <= 10.0
+
+
+def test_normalize_obs_update_false_only_reads_the_statistics(usim):
+    torch.manual_seed(5)
+    vn = usim.policy.DeviceVecNormalize(4, 19, device="cpu", training=True)
+    vn.normalize_obs(torch.randn(32, 19) * 2 + 0.5)                           # statistics that are not the identity
+    obs = torch.randn(8, 19) * 30                                             # (wide enough for the clip to act)
+    kept = (vn.obs_mean.clone(), vn.obs_var.clone(), vn._obs_count.clone())
+    frozen = copy.deepcopy(vn)
+    frozen.training = False
+    out = vn.normalize_obs(obs, update=False)
+    assert all(torch.equal(a, b) for a, b in zip((vn.obs_mean, vn.obs_var, vn._obs_count), kept)) and vn.training is True
+    assert out.dtype == torch.float32 and torch.equal(out, frozen.normalize_obs(obs)) and float(out.abs().max()) == 10.0
+    assert all(torch.equal(a, b) for a, b in zip((frozen.obs_mean, frozen.obs_var, frozen._obs_count), kept))
+    twin = copy.deepcopy(vn)
+    out_none, out_default = vn.normalize_obs(obs, update=None), twin.normalize_obs(obs)     # None: as self.training says -- today's call, which updates first
+    assert float(vn._obs_count) == float(kept[2]) + 8 and not torch.equal(vn.obs_mean, kept[0]) and not torch.equal(vn.obs_var, kept[1])
+    assert torch.equal(out_none, out_default) and torch.equal(vn.obs_mean, twin.obs_mean) and not torch.equal(out_none, out)
+    count = float(frozen._obs_count)
+    frozen.normalize_obs(obs, update=None)                                    # ... and leaves a frozen object alone
+    assert float(frozen._obs_count) == count and torch.equal(frozen.obs_mean, kept[0])
 
 
 # ---- PlannerExpert and DAggerTrainer with stand-ins ----

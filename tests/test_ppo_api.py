@@ -207,3 +207,53 @@ def test_flatten_parameters_on_a_cpu_module(usim):
         assert usim.ppo.flatten_parameters(m) is theta                    # idempotent
         sd = m.to_sb3_state_dict()                                        # the checkpoint writer reads the same memory
         assert torch.equal(sd["mlp_extractor.value_net.2.weight"], m.value_net_body[2].weight.detach())
+
+
+# ---- one construction of usim_policy_net, one learner core ----
+@pytest.mark.parametrize("A", [6, 7])
+def test_policy_net_holds_the_addresses_of_the_parameters_in_the_headers_order(usim, A):
+    m = _policy(usim, A)
+    packed = torch.zeros(8)
+    for flat in (False, True):                                            # before and after flatten_parameters (which re-seats every parameter)
+        if flat:
+            usim.ppo.flatten_parameters(m)
+        net, params = usim.policy.policy_net(m), dict(m.named_parameters())
+        for name, path in usim.ppo.FIELDS:
+            assert getattr(net, name) == params[path].data_ptr(), (flat, name)
+        ptr = lambda t: t.data_ptr()                                      # the construction FusedRollout spelled out attribute by attribute until now
+        pn, vb = m.policy_net, m.value_net_body
+        want = (ptr(pn[0].weight), ptr(pn[0].bias), ptr(pn[2].weight), ptr(pn[2].bias), ptr(m.action_net.weight), ptr(m.action_net.bias),
+                ptr(vb[0].weight), ptr(vb[0].bias), ptr(vb[2].weight), ptr(vb[2].bias), ptr(m.value_net.weight), ptr(m.value_net.bias), ptr(m.log_std))
+        names = [n for n, _ in usim._lib.UsimPolicyNet._fields_]
+        assert names[13:] == ["w2_packed"] and tuple(getattr(net, n) for n in names[:13]) == want and len(set(want)) == 13
+        assert net.w2_packed is None and usim.policy.policy_net(m, packed).w2_packed == packed.data_ptr()
+        assert tuple(getattr(usim.policy.policy_net(m, packed), n) for n in names[:13]) == want
+    assert usim.policy.FIELDS is usim.ppo.FIELDS is usim.learner.FIELDS
+
+
+class _NoCalls:
+    """stands where the library stands: any call is a failure of the test"""
+
+    def usim_ppo_work_floats(self, A):
+        return 16
+
+    def __getattr__(self, name):
+        raise AssertionError(f"{name} was called by a constructor")
+
+
+def test_native_ppo_and_native_bc_stand_on_one_core_and_one_block(usim, monkeypatch):
+    monkeypatch.setattr(usim._lib, "load", lambda: _NoCalls())
+    A, policy = 6, _policy(usim)
+    bc = usim.NativeBC(policy, usim.policy.DeviceVecNormalize(1, 19, device="cpu", training=False), usim.DemoBuffer(40, A, "cpu"), seed=3)
+    env = SimpleNamespace(action_dim=A, device="cpu", num_envs=8)
+    ppo = usim.ppo.NativePPO(env, policy, usim.policy.DeviceVecNormalize(8, 19, device="cpu"), usim.policy.DeviceRolloutBuffer(4, 8, 19, A, device="cpu"), seed=3)
+    core = usim.learner.FlatLearner
+    assert isinstance(bc, core) and isinstance(ppo, core) and usim.ppo.NativePPO.__mro__[1] is core and usim.NativeBC.__mro__[1] is core
+    assert ppo.theta is bc.theta and usim.ppo._is_flat(policy, ppo.theta) and ppo.params == bc.params == usim.ppo.ppo_params(A)
+    names = [n for n, _ in usim._lib.UsimPolicyNet._fields_]
+    assert [getattr(ppo._net, n) for n in names] == [getattr(bc._net, n) for n in names] and ppo._net.pi_w1 == ppo.theta.data_ptr()
+    for ln, rows in ((ppo, 32), (bc, 40)):                                # what the core allocates, under the names the tools and tests read
+        assert all(getattr(ln, k).shape == (ln.params,) and getattr(ln, k).dtype == torch.float32 and not getattr(ln, k).any() for k in ("grad", "exp_avg", "exp_avg_sq"))
+        assert ln.step_count.dtype == torch.int32 and ln.step_count.tolist() == [0] and ln._index.dtype == torch.int32 and ln._index.numel() == rows
+        assert ln.stats.numel() == ln.first_stats.numel() == usim._lib.PPO_STATS and ln._work.numel() == 16 and ln.act_dim == A and ln.device == torch.device("cpu")
+        assert ln.generator.initial_seed() == 3 and all(k in vars(ln) for k in ("theta", "params", "lib", "_net", "policy", "n_epochs", "adam_eps", "max_grad_norm"))

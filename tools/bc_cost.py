@@ -77,8 +77,7 @@ pb = L.UsimPpoBatch(obs.data_ptr(), act.data_ptr(), old_logp.data_ptr(), adv.dat
 def ppo_step():
     s = ref._stream()
     L.check(ref.lib, ref.lib.usim_ppo_grad(C.byref(ref._net), C.byref(pb), ref._work.data_ptr(), ref.grad.data_ptr(), ref.stats.data_ptr(), s))
-    L.check(ref.lib, ref.lib.usim_ppo_adam(ref.theta.data_ptr(), ref.grad.data_ptr(), ref.exp_avg.data_ptr(), ref.exp_avg_sq.data_ptr(), ref.step_count.data_ptr(),
-                                           ref.params, 3e-4, 0.9, 0.999, 1e-5, 0.5, ref.stats.data_ptr(), s))
+    ref.adam_step(3e-4)                                                   # (NativeBC's defaults: eps 1e-5, max_grad_norm 0.5)
 
 
 variants["usim_ppo_grad + usim_ppo_adam"] = ppo_step

@@ -3,7 +3,8 @@
 // 16-lane kernels of the rigid and soft torsos (usim_step16.h); synthetic_action serves the full-torso kernel and usim_random_actions_kernel.
 // The functions work on per-environment scalars; what is laid out per lane (joint words, the Philox evaluation) stays with the kernels.
 // Still one copy per kernel family: reset draws, observation, reward terms, bookkeeping, termination, episode record, bank park / adopt, and
-// (in step16_one) the synthetic-action decoding.  Moved into force-inlined functions they compute the same values, but the 16-lane kernels come
+// (in step16_one, the pass of the single-wave 16-lane kernels and of the split kernel's arm wave; its lattice wave, lattice_pass, has none of these) the synthetic-action
+// decoding.  Moved into force-inlined functions they compute the same values, but the 16-lane kernels come
 // out with a different instruction schedule and register allocation (the callee is simplified on its own before it is inlined; synthetic_action
 // in step16_one changes 7 of the 14), which needs an A/B of its own.
 #pragma once

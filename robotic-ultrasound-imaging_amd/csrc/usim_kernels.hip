@@ -227,6 +227,8 @@ DI bool collide_cull(const float* lds, const int e, const DevModel& M, const Dev
     const f3 v = d - ax * clampf(dot(d, ax), -ELEM_HL, ELEM_HL);                   // from the centre of the upper axis to the nearest point of the element's axis segment
     return dot(v, v) < C.probe_cull2c;
 }
+// (The round around it -- candidate test, ballot, prefix slot, spare word 99, count -- is written out in both waves of the split kernel, step16_one and lattice_pass.  As one
+//  function over a range of rounds it measured slower with 8-lane groups: config5 8192 24.67 -> 24.81 us/step, profiles/lattice_pass/ab.txt.)
 template <int G>
 DI void collide_queue(const float* lds, const float* queue, const int nq, float* recs, const int gl, const int gbase, const DevModel& M, const DevCfg& C,
                       const float* s_lds, const float dz, const f3 Kx, const f3 Ksx, const f3 Ksy, const f3 Ksz, int& nc) {

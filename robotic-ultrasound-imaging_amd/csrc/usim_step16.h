@@ -20,6 +20,8 @@
 // inertial parameters in the link frame -- the kernel is the same for every chain of up to seven joints.
 //
 // Lattice / contact phases (soft torso) are the ones of usim_kernels.hip and usim_contact.h (lattice_rhs, lattice_solve, collide_*; contact_solve): the G = 16 mapping is unchanged there.
+// A pass of a step kernel is step16_one (single-wave kernels; arm wave of the split kernel) or lattice_pass (lattice / contact wave of the split kernel); step16_body loops over
+// the passes of a launch.
 #pragma once
 #include <type_traits>
 
@@ -236,6 +238,7 @@ constexpr int X16_RIGID_STRIDE = 84;                  // rigid-torso launches: o
 // (kinematics ... controller, then acceleration, sensors, reward, bookkeeping), ROLE 2 the lattice / contact side (staging, right-hand side,
 // matrix-core solve, collision, contact solve, element integration).  They meet at workgroup barriers and hand over through per-environment
 // LDS mailboxes: site pose (1 -> 2), Lambda^-1 / alpha / vs (1 -> 2), contact wrench and contact list (2 -> 1).  ROLE 0 = one wave does both.
+// Two functions state a pass: step16_one for ROLE 0 and ROLE 1, lattice_pass for ROLE 2; step16_body calls the one or the other.
 //
 // waves per role in a workgroup of the split kernel: one 512-thread workgroup per CU (two 256-thread workgroups per CU, with barrier domains of their own, measured slower
 // for both group sizes: DESIGN.md section 4.8)
@@ -287,6 +290,8 @@ template <int ROLE, int G, bool RES> constexpr bool lattice_ahead() { return ROL
 // transition block); what a resident launch saves is waiting for the words it stored itself to come back.  The arm table (28 words per lane,
 // needed at the top of every step) is parked in LDS behind everything else during the first step and read from there afterwards: kept in
 // registers it would be live across the whole step (the split kernel spills at 256 registers).
+// Who carries what: a single wave (ROLE 0) all of it; the arm wave of the split kernel (ROLE 1) the joint words and `ep`, and of `s` -- 8-lane groups only -- a copy it
+// refreshes from LDS every pass to cull on; the lattice wave (lattice_pass) kst, kdmp, mu and t of `ep`, s, sd and wr, and nothing else.
 constexpr int ARM_LDS_WORDS = A16_LANES * AT_STRIDE;
 template <int TORSO, int ROLE, int G> constexpr int arm_lds_base();
 template <int NE, class WR = NoWarm>
@@ -303,10 +308,311 @@ template <int TORSO, int ROLE, int G> constexpr int arm_lds_base() {
 static_assert((arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS) * 4 <= 160 * 1024 && arm_lds_base<1, 1, 8>() % 4 == 0 && arm_lds_base<1, 1, 16>() % 4 == 0 && arm_lds_base<1, 0, 16>() % 4 == 0
               && arm_lds_base<0, 0, 16>() % 4 == 0, "arm table behind the LDS blocks of every 16-lane kernel");
 
+// One pass of the lattice / contact wave of the split kernel (ROLE 2; its partner, the arm wave, runs step16_one<1, 0, 1, ...>): the soft-torso step (TORSO 1, MODE 0) of the
+// wave's environments from staging the right-hand side to the integrated lattice.  Per environment it
+//   reads from HBM (first pass of a launch)   kst, kdmp, mu, t; its elements' s and sd; its warm record (WR = WarmRec)
+//   carries between the passes (RES)          the same, in `cy` (and nothing else of it)
+//   takes from the arm wave                   site pose and, with 8-lane groups, the queue's first part and EB(GE_S) -- behind (1); Lambda^-1, alpha, vs -- behind (2);
+//                                             the new-episode word in MB_W -- 8-lane groups: at the top of a pass, 16-lane resident launches (LA): behind (1)
+//   hands to the arm wave                     contact wrench, count, overflow flag and the contacts' elements in MB_W -- before (3)
+//   writes to HBM                             s and sd of its elements and the warm record -- before (4)
+// and meets the arm wave at the table copy and at hand-offs (1)-(4): BARRIER INVARIANT at usim_step32_kernel.  `more` = another pass of this launch follows this one.
+template <int NT, int G, bool RES, class WR>
+DI void lattice_pass(float* lds, const DevModel& M, const DevCfg& C, float* __restrict__ st, const int n, const int npad, const DevIO& io,
+                     const bool first_pass, const int sub, const bool more, int& nbar, Carry<(N_TOP + G - 1) / G, WR>& cy) {
+    constexpr bool WARM = !std::is_same<WR, NoWarm>::value;             // this wave solves the contacts: it loads, keeps and stores the lane's record of the kept list
+    constexpr int WPR = SPLIT_WPR, EPW = 64 / G, EPB = WPR * EPW;       // environments per wave / per workgroup (WPR waves per role)
+    constexpr unsigned GMASK = (G == 16) ? 0xffffu : 0xffu;
+    constexpr int NE = (N_TOP + G - 1) / G;
+    constexpr bool LA = lattice_ahead<2, G, RES>();
+    const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & (WPR - 1);      // wave within its role = quad of environments
+    const bool fresh = !RES || first_pass;                              // the state comes from HBM (first step of a launch; every single-step launch)
+    const int gl = lane & (G - 1), ge = lane / G;
+    const int gbase = lane - gl;
+    const int eb = wave * EPW + ge;
+    unsigned long long* const dbg = io.dbg;
+    const int env = blockIdx.x * EPB + eb;
+    const bool valid = env < n;
+    const bool store = valid && gl == 0;                                // [b], below
+    const int ei = valid ? env : n - 1;                                 // clamp so that every lane has something to read; stores are guarded
+#define LAT(w) st[(size_t)F_LAT * npad + (size_t)ei * LAT_ENV_WORDS + (w)]
+#define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
+    float* const warm_rows = st + warm_index(io.bank_row0, npad, (size_t)ei);      // (dereferenced by handles with warm rows only)
+    int mbo = x2_base<G>() + eb * X2_STRIDE;                            // the environment's mailbox block, its offset opaque: one address register (step16_one)
+    asm volatile("" : "+v"(mbo));
+
+    // ---------------- load: the environment's contact parameters and step count, this lane's elements and warm record ----------------
+    // BALLAST, marked [b]: statements of the arm wave that this prologue had while it was step16_one's.  Nothing in this function reads what they compute and the compiler
+    // deletes every one of them, but each, taken out of the source, changes the register allocation and the schedule of the twelve split kernels, and the prologue without
+    // them (one 16-byte load of kst, kdmp, mu, t; no arm table, joint words or other scalar words) measured 0.2 - 0.3 % slower with 8-lane groups at 8192 environments in two
+    // sessions (profiles/lattice_pass/ab.txt).  They stay, in their order, for a change that measures these kernels anyway to remove.
+    float* const xl = &lds[mbo];                                        // [b]
+    float* const goal_lds = xl + MB_GOAL;                               // [b]
+    float at[AT_STRIDE];                                                // [b] down to `jl`
+    {
+        constexpr int ARM_LDS = arm_lds_base<1, 2, G>();
+        const float4* ap = fresh ? reinterpret_cast<const float4*>(M.tables + TB_ARM + gl * AT_STRIDE) : reinterpret_cast<const float4*>(lds + ARM_LDS + gl * AT_STRIDE);
+        if (fresh) {
+#pragma unroll
+            for (int v = 0; v < AT_STRIDE / 4; ++v) { const float4 x = ap[v]; at[4 * v] = x.x; at[4 * v + 1] = x.y; at[4 * v + 2] = x.z; at[4 * v + 3] = x.w; }
+        } else {
+            const float4* lp = reinterpret_cast<const float4*>(lds + ARM_LDS + gl * AT_STRIDE);
+#pragma unroll
+            for (int v = 0; v < AT_STRIDE / 4; ++v) { const float4 x = lp[v]; at[4 * v] = x.x; at[4 * v + 1] = x.y; at[4 * v + 2] = x.z; at[4 * v + 3] = x.w; }
+        }
+    }
+    const float* const sp = st + scalar_index(0, (size_t)ei);
+    const bool jlane = at[AT_JOINT] != 0.f;
+    const int jl = jlane ? gl : NJ - 1;
+    float &dqj = cy.dqj, &qdj = cy.qdj, &q0j = cy.q0j;                  // [b]
+    Episode& E = cy.ep;
+    f3 &ts = E.ts, &te = E.te;                                          // [b]
+    float &u0 = E.u0, &vbar = E.vbar, &fzbar = E.fzbar, &fzprev = E.fzprev, &dfz = E.dfz, &kst = E.kst, &kdmp = E.kdmp, &mu = E.mu, &epret = E.epret;      // [b] but kst, kdmp, mu
+    int &t = E.t, &touched = E.touched, &episode = E.episode, &status = E.status;                                                                            // [b] but t
+    float (&s_pre)[NE] = cy.s, (&sd_pre)[NE] = cy.sd;
+    // resident launches: the arm side reports a new episode through the mailbox (MB_W: kst, kdmp, mu, 1): the lattice at rest, the episode's parameters, t = 0
+    auto adopt = [&](const float4 nx) {
+        kst = nx.x; kdmp = nx.y; mu = nx.z; t = 0;
+#pragma unroll
+        for (int i = 0; i < NE; ++i) { s_pre[i] = 0.f; sd_pre[i] = 0.f; }
+        warm_clear(cy.wr);                                               // an episode starts cold
+    };
+    if (fresh) {
+        dqj = sp[F_Q + jl]; qdj = sp[F_QD + jl]; q0j = sp[F_Q0 + jl];     // [b]
+        float sv[20];                                              // scalar words 20 .. 39: this wave reads kst, kdmp, mu and t of them
+        {
+            const float4* s4 = reinterpret_cast<const float4*>(sp + 20);
+#pragma unroll
+            for (int v = 0; v < 5; ++v) { const float4 x = s4[v]; sv[4 * v] = x.x; sv[4 * v + 1] = x.y; sv[4 * v + 2] = x.z; sv[4 * v + 3] = x.w; }
+        }
+#define SV(f) sv[(f) - 20]
+        ts = mk(SV(F_TS), SV(F_TS + 1), SV(F_TS + 2)); te = mk(SV(F_TE), SV(F_TE + 1), SV(F_TE + 2));                                  // [b]
+        u0 = SV(F_U0); vbar = SV(F_VBAR); fzbar = SV(F_FZBAR); fzprev = SV(F_FZPREV); dfz = SV(F_DFZ);                                 // [b]
+        kst = SV(F_KST); kdmp = SV(F_KDMP); mu = SV(F_MU); epret = SV(F_EPRET);                                                         // (epret: [b])
+        t = __float_as_int(SV(F_T)); touched = __float_as_int(SV(F_TOUCH)); episode = __float_as_int(SV(F_EPISODE)); status = __float_as_int(SV(F_STATUS));      // (all but t: [b])
+#undef SV
+#pragma unroll
+        for (int i = 0; i < NE; ++i) {
+            const int e = gl + i * G;
+            s_pre[i] = 0.f; sd_pre[i] = 0.f;
+            if (e < N_TOP) { s_pre[i] = LAT(LAT_S + e); sd_pre[i] = LAT(LAT_SD + e); }
+        }
+        if constexpr (WARM) warm_load(warm_rows, gl, cy.wr);
+    } else if constexpr (RES && !LA) {
+        // resident launch, 8-lane groups: the word is read here (16-lane groups, LA: behind hand-off (1), below)
+        const float4 nx = *reinterpret_cast<const float4*>(&lds[mbo + MB_W]);
+        if (nx.w != 0.f) adopt(nx);
+    }
+    if (!jlane) { dqj = 0.f; qdj = 0.f; q0j = 0.f; }                    // [b]
+    float qj = q0j + dqj;                                               // [b]
+    if (first_pass) {
+        // workgroup-resident copy of the lattice tables, this role's half of it (as in step16_one)
+        const float4* src = reinterpret_cast<const float4*>(M.tables);
+        float4* dst = reinterpret_cast<float4*>(lds);
+        constexpr int NV = TB_WORDS / 4, PER = (NV + NT - 1) / NT;
+        float4 tmp[PER];
+        int tix = threadIdx.x;
+        asm volatile("" : "+v"(tix));                                   // (keeps the copy's addresses from being formed ahead of the step loop and carried, spilled, through every step)
+#pragma unroll
+        for (int i = 0; i < PER; ++i) { int idx = tix + i * NT; tmp[i] = (idx < NV) ? src[idx] : make_float4(0, 0, 0, 0); }
+#pragma unroll
+        for (int i = 0; i < PER; ++i) { int idx = tix + i * NT; if (idx < NV) dst[idx] = tmp[i]; }
+        USIM_BAR();
+    }
+    // (`sub`, the physics substep of this pass: step16_one)
+    if (sub == 0) t += 1;
+    const int tphys = (t - 1) * C.substeps + sub;                       // physics steps since the episode began (prescribed torso drop)
+    const float dt = C.dt;
+#if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
+#define RSTAMP(k) do { if (dbg && blockIdx.x == 0 && (threadIdx.x & (64 * WPR - 1)) == 0) dbg[30 + (k)] = __builtin_readcyclecounter(); } while (0)
+#else
+#define RSTAMP(k) do { } while (0)
+#endif
+#define XSTAMP(k) RSTAMP(20 + (k))                                  /* dbg[50 ..] */
+    RSTAMP(0);
+    if constexpr (LA) __builtin_amdgcn_s_setprio(1);                   // (first pass; later ones come here with it raised)
+    float* const mb = &lds[mbo];
+    float dz, vz, az;
+    torso_motion(C, tphys, dz, vz, az);
+    if constexpr (LA) {
+        // this side owns EB(GE_S): from the state it loaded (first pass), from every integration, and zeros when it adopts a new episode
+        if (first_pass) {
+#pragma unroll
+            for (int i = 0; i < NE; ++i) { const int e = gl + i * G; if (e < N_TOP) EB(GE_S + e) = s_pre[i]; }
+        }
+    }
+    // (LA, not the first pass: this wave comes here straight from integrating the previous pass -- the arm wave may still be in its finish -- and assumes that no
+    //  episode of the wave ended)
+    lattice_rhs<G, NE>(lds, eb, gl, M, az, kst, kdmp, true, s_pre, sd_pre);
+    // The matrix-core solve a~ = Linv rhs needs nothing from the arm side: it runs here, where this wave used to wait for the site pose (hand-off (1)
+    // comes when the arm side has finished its kinematics and the broad phase), and leaves only the narrow phase for after the hand-off: one box,
+    // 14.38 -> 13.65 us/step at 4096 envs, 20.8 -> 20.2 at 8192 (8-lane groups).  Splitting the product around the hand-off so that both sides reach
+    // hand-offs (1) and (2) together (18 / 14 / 21 of the 25 k chunks before it, accumulators live across the barrier) is slower: 13.9 / 14.1 / 13.85,
+    // and with 8-lane groups the accumulators of both column sets spill (44 us).
+    lattice_solve<G>(lds, eb, gl, gbase);
+    RSTAMP(1);
+    USIM_BAR();                                                 // (1) the arm side has published the site pose
+    RSTAMP(2);
+    if constexpr (LA) {
+        __builtin_amdgcn_s_setprio(0);
+        if (!first_pass) {
+            // the arm side's word of the previous pass (written behind its reads of the wrench, read here before this pass's wrench is written): a new episode starts
+            // with the lattice at rest, its own parameters and t = 0 -- adopt it (t advances as at the top of the pass: once) and run the two phases again
+            const float4 nx = *reinterpret_cast<const float4*>(&mb[MB_W]);
+            const bool began = nx.w != 0.f;
+            if (__any(began)) {
+                if (began) {
+                    adopt(nx);
+                    if (sub == 0) t += 1;
+#pragma unroll
+                    for (int i = 0; i < NE; ++i) { const int e = gl + i * G; if (e < N_TOP) EB(GE_S + e) = 0.f; }
+                }
+                torso_motion(C, (t - 1) * C.substeps + sub, dz, vz, az);
+                lattice_rhs<G, NE>(lds, eb, gl, M, az, kst, kdmp, true, s_pre, sd_pre);
+                lattice_solve<G>(lds, eb, gl, gbase);
+            }
+        }
+    }
+    const f3 xs = mk(mb[MB_POSE], mb[MB_POSE + 1], mb[MB_POSE + 2]), sy = mk(mb[MB_POSE + 3], mb[MB_POSE + 4], mb[MB_POSE + 5]),
+             sz = mk(mb[MB_POSE + 6], mb[MB_POSE + 7], mb[MB_POSE + 8]);
+    const f3 sxc = cross(sy, sz);
+    int nq = __float_as_int(mb[MB_POSE + 10]);
+    // the rest of the broad phase (elements G arm_cull_rounds<G>() ..): appended to the arm side's part of the queue
+#pragma unroll
+    for (int i = arm_cull_rounds<G>(); i < NE; ++i) {
+        const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
+        const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz, xs, sz);
+        const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & GMASK;
+        mb[MB_Q + (cand ? nq + __popc(gm & ((1u << gl) - 1u)) : 99)] = __int_as_float(e);       // (as on the arm side: the spare last word takes the non-candidates)
+        nq += __popc(gm);
+    }
+    group_sync();
+#if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
+    // profiling build: queue length of every environment of the first lattice wave of workgroup 0 (dbg[54 ..]; collide_queue makes max ceil(nq / G) passes over the wave)
+    if (dbg && blockIdx.x == 0 && wave == 0 && gl == 0) dbg[54 + ge] = 1ull + (unsigned long long)nq;
+#endif
+    // narrow phase: the whole queue, against the element positions parked in the environment's block (by the arm side; LA: by this side)
+    int nc = 0;
+    collide_queue<G>(lds, mb + MB_Q, nq, &EB(GE_CG), gl, gbase, M, C, &EB(GE_S), dz, xs, sxc, sy, sz, nc);
+    // The contact list is complete here.  8-lane groups (EARLY) apply the slot rule and form the contact elements and the arm-independent half of every
+    // contact row (frame, lever arms, lattice coupling, regulariser) before hand-off (2), while the arm side still forms Lambda^-1; 16-lane groups do it
+    // after the hand-off.  One box, kernel us/step: 8-lane groups at 8192 envs 20.19 -> 19.97 (scratch 176 -> 112 bytes per lane); 16-lane groups at 4096
+    // envs 13.67 -> 13.82 (same scratch; what moves ahead of the barrier lengthens the path the arm wave waits for) -- only the 8-lane kernel does it.
+    constexpr bool EARLY = G == 8;
+    ContactRows P;
+    // (The early list lives in variables of its own and is adopted after the hand-off.  Forming it in nc / overflow / ncmax / cel directly, with the slot rule as
+    //  one lambda called on either side of the barrier, reads better and cost the 8-lane multi-step kernel two more spilled registers, 8 B of scratch and 0.6 % of
+    //  the 8192-environment step: DESIGN.md section 10.)
+    int nc_early = nc, overflow_early = 0, ncmax_early = 0, cel_early[MAXC];
+    if constexpr (EARLY) {
+        contact_overflow<G>(lds, eb, gl, gbase, nc_early);
+        if (nc_early > MAXC) { overflow_early = 1; nc_early = MAXC; }
+        group_sync();
+#pragma unroll
+        for (int k = MAXC; k >= 1; --k) if (ncmax_early == 0 && __any(nc_early >= k)) ncmax_early = k;
+#pragma unroll
+        for (int k = 0; k < MAXC; ++k) cel_early[k] = (k < nc_early) ? __float_as_int(EB(GE_CG + k * CG_WORDS + 6)) : 0;
+        if (ncmax_early > 0) contact_rows<G>(lds, eb, gl, M, C, nc_early, cel_early, vz, P);
+    }
+    RSTAMP(3);
+    USIM_BAR();                                                 // (2) ... and Lambda^-1, alpha = J qs, vs = J qd
+    RSTAMP(4);
+    if constexpr (LA) __builtin_amdgcn_s_setprio(1);
+    if constexpr (!EARLY) contact_overflow<G>(lds, eb, gl, gbase, nc);
+    int overflow = 0;
+    if (nc > MAXC) { overflow = 1; nc = MAXC; }
+    if constexpr (!EARLY) group_sync();
+    XSTAMP(0);
+    int ncmax = 0;
+    if constexpr (EARLY) { nc = nc_early; overflow = overflow_early; ncmax = ncmax_early; }
+    else {
+        // the wave's largest count: nc is uniform over a group, so it is the largest of the four groups' (four lane reads and three scalar maxima in place of eight
+        // votes with a branch each; the same value)
+        static_assert(G == 16, "one lane read per 16-lane group of the wave");
+        const int n0 = __builtin_amdgcn_readlane(nc, 0), n1 = __builtin_amdgcn_readlane(nc, 16), n2 = __builtin_amdgcn_readlane(nc, 32), n3 = __builtin_amdgcn_readlane(nc, 48);
+        const int n01 = n0 > n1 ? n0 : n1, n23 = n2 > n3 ? n2 : n3;
+        ncmax = n01 > n23 ? n01 : n23;
+    }
+    XSTAMP(1);
+    float gf[MAXC], W[6] = {0, 0, 0, 0, 0, 0};
+    int cel[MAXC];
+#pragma unroll
+    for (int k = 0; k < MAXC; ++k) { const int ek = __float_as_int(EB(GE_CG + k * CG_WORDS + 6)); gf[k] = 0.f; cel[k] = EARLY ? cel_early[k] : ((k < nc) ? ek : 0); }      // (read, then select: no branch per slot)
+    if (ncmax > 0) {
+        // 16-byte reads (the opaque mailbox offset hides the alignment that the static_assert at the layout guarantees): row a of Lambda^-1 is words 8 a .. 8 a + a,
+        // alpha and vs are the twelve words behind the six rows -- eleven reads instead of 33 words one or two at a time
+        float alpha[6], vs[6], Lp[21];
+        const float4* const op = reinterpret_cast<const float4*>(&mb[MB_OP]);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            const float4 lo = op[2 * a], hi = (a >= 4) ? op[2 * a + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float row[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
+#pragma unroll
+            for (int b = 0; b <= a; ++b) Lp[PK(a, b)] = row[b];
+        }
+        {
+            const float4 v0 = op[12], v1 = op[13], v2 = op[14];
+            alpha[0] = v0.x; alpha[1] = v0.y; alpha[2] = v0.z; alpha[3] = v0.w; alpha[4] = v1.x; alpha[5] = v1.y;
+            vs[0] = v1.z; vs[1] = v1.w; vs[2] = v2.x; vs[3] = v2.y; vs[4] = v2.z; vs[5] = v2.w;
+        }
+        XSTAMP(2);
+        contact_solve<G, EARLY, true>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, P, W, gf, dbg, cy.wr);
+        XSTAMP(3);
+    } else warm_clear(cy.wr);                                        // (no contact in the wave: nothing kept)
+    if (gl == 0) {
+        *reinterpret_cast<float4*>(&mb[MB_W]) = make_float4(W[0], W[1], W[2], W[3]);
+        *reinterpret_cast<float4*>(&mb[MB_W + 4]) = make_float4(W[4], W[5], __int_as_float(nc), __int_as_float(overflow));
+        // the contacts' elements as this wave holds them (0 beyond the count); the arm wave maps them to shell ids where the launch reports contacts
+        static_assert(MAXC == 8, "two 16-byte stores");
+        *reinterpret_cast<float4*>(&mb[MB_W + 8]) = make_float4(__int_as_float(cel[0]), __int_as_float(cel[1]), __int_as_float(cel[2]), __int_as_float(cel[3]));
+        *reinterpret_cast<float4*>(&mb[MB_W + 12]) = make_float4(__int_as_float(cel[4]), __int_as_float(cel[5]), __int_as_float(cel[6]), __int_as_float(cel[7]));
+    }
+    RSTAMP(5);
+    USIM_BAR();                                                 // (3) contact wrench and contact list published
+    RSTAMP(6);
+#if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
+    if (more && dbg && blockIdx.x == 0 && (threadIdx.x & (64 * WPR - 1)) == 0) dbg[62] = __builtin_readcyclecounter();      // hand-off (3) of the pass before the last one
+#endif
+    {
+        float acc_e[NE];
+#pragma unroll
+        for (int i = 0; i < NE; ++i) { const int e = gl + i * G; acc_e[i] = (e < N_TOP) ? EB(GE_A + e) : 0.f; }
+#pragma unroll
+        for (int k = 0; k < MAXC; ++k) {                              // (every slot, no test against the wave's contact count: slots beyond an environment's count carry gf = 0
+                                                                     //  and element 0, and eight uniform branches cost more than the multiply-adds they skip)
+#pragma unroll
+            for (int i = 0; i < NE; ++i) {
+                const int e = (gl + i * G < N_TOP) ? gl + i * G : N_TOP - 1;
+                acc_e[i] = fmaf(lds[TB_LINV + e * LROW + cel[k]], gf[k], acc_e[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NE; ++i) {
+            const int e = gl + i * G;
+            if (e >= N_TOP) continue;
+            const float sdn = sd_pre[i] + dt * acc_e[i];
+            const float sn = s_pre[i] + dt * sdn;
+            if (valid) { LAT(LAT_SD + e) = sdn; LAT(LAT_S + e) = sn; }
+            if constexpr (RES) { sd_pre[i] = sdn; s_pre[i] = sn; EB(GE_S + e) = sn; }     // resident launch: the next step's state; positions for the arm side's broad phase
+        }
+        if constexpr (WARM) { if (valid) warm_store(warm_rows, gl, cy.wr); }
+    }
+    RSTAMP(7);
+    if (!LA || !more) USIM_BAR();                               // (4) lattice stored: the arm side may now zero it for an episode that ended (LA: last pass of a launch only)
+    RSTAMP(8);
+#undef RSTAMP
+#undef XSTAMP
+#undef LAT
+#undef EB
+}
+
+// The 16-lane step of the single-wave kernels (ROLE 0: arm and lattice sides in one wave) and of the arm wave of the split kernel (ROLE 1; its lattice / contact wave runs
+// lattice_pass, above).
 // AHEAD (action drawn ahead; arm side of the split kernel in resident launches that draw their actions): `more` = another pass of this launch follows this one
 template <int TORSO, int MODE, int ROLE, int NT, int G = 16, bool RES = false, class WR = NoWarm, bool AHEAD = false>
 DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __restrict__ st, const int n, const int npad, const DevIO& io, const int flags, const long long rstep,
                    const bool first_pass, const int sub, const bool more, int& nbar, Carry<TORSO ? (N_TOP + G - 1) / G : 1, WR>& cy) {
+    static_assert(ROLE != 2, "the lattice / contact wave of the split kernel runs lattice_pass");
     static_assert(!AHEAD || (ROLE == 1 && RES), "action drawn ahead: the arm wave of a resident split launch");
     // warm start of the contact solve (WR = WarmRec): the side that solves the contacts loads the lane's record of the kept list with the state, hands it to
     // contact_solve and stores the new one with the lattice; the side that restarts an episode clears the environment's warm rows
@@ -373,7 +679,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         if (fresh) {
 #pragma unroll
             for (int v = 0; v < AT_STRIDE / 4; ++v) { const float4 x = ap[v]; at[4 * v] = x.x; at[4 * v + 1] = x.y; at[4 * v + 2] = x.z; at[4 * v + 3] = x.w; }
-            if constexpr (RES && ROLE != 2) {
+            if constexpr (RES) {
                 // (every wave writes the same words and reads them back itself: no hand-off involved)
                 if (lane < G) {
 #pragma unroll
@@ -415,25 +721,15 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         for (int i = 0; i < NE; ++i) {
             const int e = gl + i * G;
             s_pre[i] = 0.f; sd_pre[i] = 0.f;
-            if (TORSO && MODE == 0 && ROLE != 1 && e < N_TOP) { s_pre[i] = LAT(LAT_S + e); sd_pre[i] = LAT(LAT_SD + e); }
+            if (TORSO && MODE == 0 && ROLE == 0 && e < N_TOP) { s_pre[i] = LAT(LAT_S + e); sd_pre[i] = LAT(LAT_SD + e); }
             if (TORSO && MODE == 0 && ROLE == 1 && !LA && e < N_TOP) s_pre[i] = LAT(LAT_S + e);      // the arm side parks the positions for the narrow phase and, with 8-lane groups, culls on them (LA: the lattice side does both)
         }
-        if constexpr (WARM && MODE == 0 && ROLE != 1) warm_load(warm_rows, gl, cy.wr);
+        if constexpr (WARM && MODE == 0 && ROLE == 0) warm_load(warm_rows, gl, cy.wr);
     } else if constexpr (RES && ROLE == 1 && !LA) {
         // resident launch, arm side of 8-lane groups (the only one that culls): the element positions the lattice side integrated (or the zeros this side left
         // for a new episode) are in the environment's LDS block
 #pragma unroll
         for (int i = 0; i < NE; ++i) { const int e = gl + i * G; s_pre[i] = (e < N_TOP) ? EB(GE_S + e) : 0.f; }
-    } else if constexpr (RES && ROLE == 2 && !LA) {
-        // resident launch, lattice side of 8-lane groups: the arm side reports a new episode (lattice at rest, its parameters, t = 0) through the mailbox
-        // (16-lane groups, LA: read behind hand-off (1), below)
-        const float4 nx = *reinterpret_cast<const float4*>(&lds[mbo + MB_W]);
-        if (nx.w != 0.f) {
-            kst = nx.x; kdmp = nx.y; mu = nx.z; t = 0;
-#pragma unroll
-            for (int i = 0; i < NE; ++i) { s_pre[i] = 0.f; sd_pre[i] = 0.f; }
-            warm_clear(cy.wr);                                           // an episode starts cold
-        }
     }
     if (!jlane) { dqj = 0.f; qdj = 0.f; q0j = 0.f; }
     float qj = q0j + dqj;
@@ -463,187 +759,10 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     const int tphys = (MODE == 0) ? (t - 1) * C.substeps + sub : 0;     // physics steps since the episode began (prescribed torso drop)
     const float dt = C.dt, inv_h = rcp_((float)C.horizon);
 #if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
-#define RSTAMP(k) do { if (dbg && blockIdx.x == 0 && (threadIdx.x & (64 * WPR - 1)) == 0) dbg[(ROLE == 2 ? 30 : 20) + (k)] = __builtin_readcyclecounter(); } while (0)
+#define RSTAMP(k) do { if (dbg && blockIdx.x == 0 && (threadIdx.x & (64 * WPR - 1)) == 0) dbg[20 + (k)] = __builtin_readcyclecounter(); } while (0)      /* arm wave of the split kernel (lattice_pass: dbg[30 ..]) */
 #else
 #define RSTAMP(k) do { } while (0)
 #endif
-#define XSTAMP(k) RSTAMP(20 + (k))                                  /* lattice side only: dbg[50 ..] */
-    if constexpr (ROLE == 2) {
-        // ================= lattice / contact side of the split kernel =================
-        RSTAMP(0);
-        if constexpr (LA) __builtin_amdgcn_s_setprio(1);                   // (first pass; later ones come here with it raised)
-        float* const mb = &lds[mbo];
-        float dz, vz, az;
-        torso_motion(C, tphys, dz, vz, az);
-        if constexpr (LA) {
-            // this side owns EB(GE_S): from the state it loaded (first pass), from every integration, and zeros when it adopts a new episode
-            if (first_pass) {
-#pragma unroll
-                for (int i = 0; i < NE; ++i) { const int e = gl + i * G; if (e < N_TOP) EB(GE_S + e) = s_pre[i]; }
-            }
-        }
-        // (LA, not the first pass: this wave comes here straight from integrating the previous pass -- the arm wave may still be in its finish -- and assumes that no
-        //  episode of the wave ended)
-        lattice_rhs<G, NE>(lds, eb, gl, M, az, kst, kdmp, true, s_pre, sd_pre);
-        // The matrix-core solve a~ = Linv rhs needs nothing from the arm side: it runs here, where this wave used to wait for the site pose (hand-off (1)
-        // comes when the arm side has finished its kinematics and the broad phase), and leaves only the narrow phase for after the hand-off: one box,
-        // 14.38 -> 13.65 us/step at 4096 envs, 20.8 -> 20.2 at 8192 (8-lane groups).  Splitting the product around the hand-off so that both sides reach
-        // hand-offs (1) and (2) together (18 / 14 / 21 of the 25 k chunks before it, accumulators live across the barrier) is slower: 13.9 / 14.1 / 13.85,
-        // and with 8-lane groups the accumulators of both column sets spill (44 us).
-        lattice_solve<G>(lds, eb, gl, gbase);
-        RSTAMP(1);
-        USIM_BAR();                                                 // (1) the arm side has published the site pose
-        RSTAMP(2);
-        if constexpr (LA) {
-            __builtin_amdgcn_s_setprio(0);
-            if (!first_pass) {
-                // the arm side's word of the previous pass (written behind its reads of the wrench, read here before this pass's wrench is written): a new episode starts
-                // with the lattice at rest, its own parameters and t = 0 -- adopt it (t advances as at the top of the pass: once) and run the two phases again
-                const float4 nx = *reinterpret_cast<const float4*>(&mb[MB_W]);
-                const bool began = nx.w != 0.f;
-                if (__any(began)) {
-                    if (began) {
-                        kst = nx.x; kdmp = nx.y; mu = nx.z; t = 0;
-                        if (sub == 0) t += 1;
-#pragma unroll
-                        for (int i = 0; i < NE; ++i) { const int e = gl + i * G; s_pre[i] = 0.f; sd_pre[i] = 0.f; if (e < N_TOP) EB(GE_S + e) = 0.f; }
-                        warm_clear(cy.wr);                                   // an episode starts cold
-                    }
-                    torso_motion(C, (t - 1) * C.substeps + sub, dz, vz, az);
-                    lattice_rhs<G, NE>(lds, eb, gl, M, az, kst, kdmp, true, s_pre, sd_pre);
-                    lattice_solve<G>(lds, eb, gl, gbase);
-                }
-            }
-        }
-        const f3 xs = mk(mb[MB_POSE], mb[MB_POSE + 1], mb[MB_POSE + 2]), sy = mk(mb[MB_POSE + 3], mb[MB_POSE + 4], mb[MB_POSE + 5]),
-                 sz = mk(mb[MB_POSE + 6], mb[MB_POSE + 7], mb[MB_POSE + 8]);
-        const f3 sxc = cross(sy, sz);
-        int nq = __float_as_int(mb[MB_POSE + 10]);
-        // the rest of the broad phase (elements G arm_cull_rounds<G>() ..): appended to the arm side's part of the queue
-#pragma unroll
-        for (int i = arm_cull_rounds<G>(); i < NE; ++i) {
-            const int eraw = i * G + gl, e = eraw < N_TOP ? eraw : N_TOP - 1;
-            const bool cand = (eraw < N_TOP) && collide_cull(lds, e, M, C, s_pre[i], dz, xs, sz);
-            const unsigned gm = (unsigned)(__ballot(cand) >> gbase) & GMASK;
-            mb[MB_Q + (cand ? nq + __popc(gm & ((1u << gl) - 1u)) : 99)] = __int_as_float(e);       // (as on the arm side: the spare last word takes the non-candidates)
-            nq += __popc(gm);
-        }
-        group_sync();
-#if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
-        // profiling build: queue length of every environment of the first lattice wave of workgroup 0 (dbg[54 ..]; collide_queue makes max ceil(nq / G) passes over the wave)
-        if (dbg && blockIdx.x == 0 && wave == 0 && gl == 0) dbg[54 + ge] = 1ull + (unsigned long long)nq;
-#endif
-        // narrow phase: the whole queue, against the element positions parked in the environment's block (by the arm side; LA: by this side)
-        int nc = 0;
-        collide_queue<G>(lds, mb + MB_Q, nq, &EB(GE_CG), gl, gbase, M, C, &EB(GE_S), dz, xs, sxc, sy, sz, nc);
-        // The contact list is complete here.  8-lane groups (EARLY) apply the slot rule and form the contact elements and the arm-independent half of every
-        // contact row (frame, lever arms, lattice coupling, regulariser) before hand-off (2), while the arm side still forms Lambda^-1; 16-lane groups do it
-        // after the hand-off.  One box, kernel us/step: 8-lane groups at 8192 envs 20.19 -> 19.97 (scratch 176 -> 112 bytes per lane); 16-lane groups at 4096
-        // envs 13.67 -> 13.82 (same scratch; what moves ahead of the barrier lengthens the path the arm wave waits for) -- only the 8-lane kernel does it.
-        constexpr bool EARLY = G == 8;
-        ContactRows P;
-        // (The early list lives in variables of its own and is adopted after the hand-off.  Forming it in nc / overflow / ncmax / cel directly, with the slot rule as
-        //  one lambda called on either side of the barrier, reads better and cost the 8-lane multi-step kernel two more spilled registers, 8 B of scratch and 0.6 % of
-        //  the 8192-environment step: DESIGN.md section 10.)
-        int nc_early = nc, overflow_early = 0, ncmax_early = 0, cel_early[MAXC];
-        if constexpr (EARLY) {
-            contact_overflow<G>(lds, eb, gl, gbase, nc_early);
-            if (nc_early > MAXC) { overflow_early = 1; nc_early = MAXC; }
-            group_sync();
-#pragma unroll
-            for (int k = MAXC; k >= 1; --k) if (ncmax_early == 0 && __any(nc_early >= k)) ncmax_early = k;
-#pragma unroll
-            for (int k = 0; k < MAXC; ++k) cel_early[k] = (k < nc_early) ? __float_as_int(EB(GE_CG + k * CG_WORDS + 6)) : 0;
-            if (ncmax_early > 0) contact_rows<G>(lds, eb, gl, M, C, nc_early, cel_early, vz, P);
-        }
-        RSTAMP(3);
-        USIM_BAR();                                                 // (2) ... and Lambda^-1, alpha = J qs, vs = J qd
-        RSTAMP(4);
-        if constexpr (LA) __builtin_amdgcn_s_setprio(1);
-        if constexpr (!EARLY) contact_overflow<G>(lds, eb, gl, gbase, nc);
-        int overflow = 0;
-        if (nc > MAXC) { overflow = 1; nc = MAXC; }
-        if constexpr (!EARLY) group_sync();
-        XSTAMP(0);
-        int ncmax = 0;
-        if constexpr (EARLY) { nc = nc_early; overflow = overflow_early; ncmax = ncmax_early; }
-        else {
-            // the wave's largest count: nc is uniform over a group, so it is the largest of the four groups' (four lane reads and three scalar maxima in place of eight
-            // votes with a branch each; the same value)
-            static_assert(G == 16, "one lane read per 16-lane group of the wave");
-            const int n0 = __builtin_amdgcn_readlane(nc, 0), n1 = __builtin_amdgcn_readlane(nc, 16), n2 = __builtin_amdgcn_readlane(nc, 32), n3 = __builtin_amdgcn_readlane(nc, 48);
-            const int n01 = n0 > n1 ? n0 : n1, n23 = n2 > n3 ? n2 : n3;
-            ncmax = n01 > n23 ? n01 : n23;
-        }
-        XSTAMP(1);
-        float gf[MAXC], W[6] = {0, 0, 0, 0, 0, 0};
-        int cel[MAXC];
-#pragma unroll
-        for (int k = 0; k < MAXC; ++k) { const int ek = __float_as_int(EB(GE_CG + k * CG_WORDS + 6)); gf[k] = 0.f; cel[k] = EARLY ? cel_early[k] : ((k < nc) ? ek : 0); }      // (read, then select: no branch per slot)
-        if (ncmax > 0) {
-            // 16-byte reads (the opaque mailbox offset hides the alignment that the static_assert at the layout guarantees): row a of Lambda^-1 is words 8 a .. 8 a + a,
-            // alpha and vs are the twelve words behind the six rows -- eleven reads instead of 33 words one or two at a time
-            float alpha[6], vs[6], Lp[21];
-            const float4* const op = reinterpret_cast<const float4*>(&mb[MB_OP]);
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                const float4 lo = op[2 * a], hi = (a >= 4) ? op[2 * a + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float row[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
-#pragma unroll
-                for (int b = 0; b <= a; ++b) Lp[PK(a, b)] = row[b];
-            }
-            {
-                const float4 v0 = op[12], v1 = op[13], v2 = op[14];
-                alpha[0] = v0.x; alpha[1] = v0.y; alpha[2] = v0.z; alpha[3] = v0.w; alpha[4] = v1.x; alpha[5] = v1.y;
-                vs[0] = v1.z; vs[1] = v1.w; vs[2] = v2.x; vs[3] = v2.y; vs[4] = v2.z; vs[5] = v2.w;
-            }
-            XSTAMP(2);
-            contact_solve<G, EARLY, true>(lds, eb, gl, M, C, nc, ncmax, cel, Lp, alpha, vs, mu, vz, P, W, gf, dbg, cy.wr);
-            XSTAMP(3);
-        } else warm_clear(cy.wr);                                        // (no contact in the wave: nothing kept)
-        if (gl == 0) {
-            *reinterpret_cast<float4*>(&mb[MB_W]) = make_float4(W[0], W[1], W[2], W[3]);
-            *reinterpret_cast<float4*>(&mb[MB_W + 4]) = make_float4(W[4], W[5], __int_as_float(nc), __int_as_float(overflow));
-            // the contacts' elements as this wave holds them (0 beyond the count); the arm wave maps them to shell ids where the launch reports contacts
-            static_assert(MAXC == 8, "two 16-byte stores");
-            *reinterpret_cast<float4*>(&mb[MB_W + 8]) = make_float4(__int_as_float(cel[0]), __int_as_float(cel[1]), __int_as_float(cel[2]), __int_as_float(cel[3]));
-            *reinterpret_cast<float4*>(&mb[MB_W + 12]) = make_float4(__int_as_float(cel[4]), __int_as_float(cel[5]), __int_as_float(cel[6]), __int_as_float(cel[7]));
-        }
-        RSTAMP(5);
-        USIM_BAR();                                                 // (3) contact wrench and contact list published
-        RSTAMP(6);
-#if defined(USIM_TSTAMP) || defined(USIM_TSTAMP_NOWAIT)
-        if (more && dbg && blockIdx.x == 0 && (threadIdx.x & (64 * WPR - 1)) == 0) dbg[62] = __builtin_readcyclecounter();      // hand-off (3) of the pass before the last one
-#endif
-        {
-            float acc_e[NE];
-#pragma unroll
-            for (int i = 0; i < NE; ++i) { const int e = gl + i * G; acc_e[i] = (e < N_TOP) ? EB(GE_A + e) : 0.f; }
-#pragma unroll
-            for (int k = 0; k < MAXC; ++k) {                              // (every slot, no test against the wave's contact count: slots beyond an environment's count carry gf = 0
-                                                                         //  and element 0, and eight uniform branches cost more than the multiply-adds they skip)
-#pragma unroll
-                for (int i = 0; i < NE; ++i) {
-                    const int e = (gl + i * G < N_TOP) ? gl + i * G : N_TOP - 1;
-                    acc_e[i] = fmaf(lds[TB_LINV + e * LROW + cel[k]], gf[k], acc_e[i]);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < NE; ++i) {
-                const int e = gl + i * G;
-                if (e >= N_TOP) continue;
-                const float sdn = sd_pre[i] + dt * acc_e[i];
-                const float sn = s_pre[i] + dt * sdn;
-                if (valid) { LAT(LAT_SD + e) = sdn; LAT(LAT_S + e) = sn; }
-                if constexpr (RES) { sd_pre[i] = sdn; s_pre[i] = sn; EB(GE_S + e) = sn; }     // resident launch: the next step's state; positions for the arm side's broad phase
-            }
-            if constexpr (WARM) { if (valid) warm_store(warm_rows, gl, cy.wr); }
-        }
-        RSTAMP(7);
-        if (!LA || !more) USIM_BAR();                               // (4) lattice stored: the arm side may now zero it for an episode that ended (LA: last pass of a launch only)
-        RSTAMP(8);
-        return;
-    }
     const int comp = gl & 3;                                             // task lanes: component of the position (quad 0) / orientation (quad 1) block
     const bool blk = (gl & 4) != 0;
     const bool is_task = (gl < 8) && comp != 3;
@@ -793,7 +912,6 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         }
     };
     if constexpr (MODE == 0) {
-    if constexpr (ROLE != 2) {
     if (flags & LF_RANDOM_ACT) {
         if (AHEAD && !first_pass) {
             // drawn during the previous pass of this launch (below, before hand-off (3)), or held over the physics substeps of a control step
@@ -818,7 +936,6 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     } else {
 #pragma unroll
         for (int a = 0; a < 7; ++a) if (a < C.adim) act[a] = finite_or_zero(io.act[(size_t)ei * C.adim + a]);
-    }
     }
     }
     // =================================================================================================================
@@ -1365,7 +1482,6 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     USIM_STAMP(dbg, 16);
     if constexpr (ROLE == 1) RSTAMP(9);
 #undef RSTAMP
-#undef XSTAMP
 #undef LAT
 #undef EB
 }
@@ -1388,7 +1504,8 @@ DI void step16_body(float* lds, const DevModel& M, const DevCfg& C, float* __res
     for (int ks = 0; ks < nsub; ++ks) {
         // (the launches of usim_rollout_actions -- ACTS -- never draw: they keep the code they had)
         constexpr bool AHEAD = ROLE == 1 && MULTI && MODE == 0 && !ACTS;
-        step16_one<TORSO, MODE, ROLE, NT, G, MULTI && MODE == 0, WR, AHEAD>(lds, M, C, st, n, npad, io, flags, cstep, ks == 0, sub, ks + 1 < nsub, nbar, cy);
+        if constexpr (ROLE == 2) lattice_pass<NT, G, MULTI && MODE == 0, WR>(lds, M, C, st, n, npad, io, ks == 0, sub, ks + 1 < nsub, nbar, cy);
+        else step16_one<TORSO, MODE, ROLE, NT, G, MULTI && MODE == 0, WR, AHEAD>(lds, M, C, st, n, npad, io, flags, cstep, ks == 0, sub, ks + 1 < nsub, nbar, cy);
         const bool ctrl_done = sub == S - 1;                             // this pass completed a control step
         if (ctrl_done) { sub = 0; ++cstep; } else ++sub;
         if (ks + 1 < nsub) {
@@ -1436,8 +1553,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 // soft-torso step with two waves per quad of environments: waves 0-3 of the workgroup run the arm side, waves 4-7 the lattice / contact side
 // (wave w and wave w + 4 land on the same SIMD and fill each other's stalls: at 4096 envs/GPU a single wave issues only ~55 % of its cycles)
 // BARRIER INVARIANT (outside the HIP programming model; holds on gfx950 because s_barrier counts waves, not program points): the two roles
-// execute __syncthreads() at DIFFERENT program points, so both must execute exactly the same NUMBER of barriers on every path -- per step: the
-// table copy (first step of a launch), hand-offs (1)-(4) of step16_one, and the one between consecutive steps of a multi-step launch.  An
+// execute __syncthreads() at DIFFERENT program points -- the arm wave's in step16_one<1, 0, 1, ...>, the lattice wave's in lattice_pass, the one between the passes, for both,
+// in step16_body -- so both must execute exactly the same NUMBER of barriers on every path -- per step: the table copy (first step of a launch: at the end of either
+// function's load section), hand-offs (1)-(4) (marked `// (1)` .. `// (4)` at the USIM_BAR() of either function; lattice_pass has no other barrier and no return), and
+// the one between consecutive steps of a multi-step launch.  An
 // early return, a barrier under a branch that is not uniform over the whole workgroup, or a fifth hand-off on one side only would hang the
 // GPU instead of failing a test.  The profiling build counts the barriers of both roles (USIM_BAR: ticks[46] / ticks[47] of usim_profile_step) and
 // tests/test_gpu_properties.py compares them; the split-vs-single-wave bit-exactness tests cover ragged workgroups and slot overflow.

@@ -70,7 +70,7 @@ template <int G, bool WARM, Launch L> constexpr Row split_row() {               
     if constexpr (L == Launch::STEP) f = usim_step32_kernel<false, G, WARM>;
     else if constexpr (L == Launch::MULTI) f = usim_step32_kernel<true, G, WARM>;
     else f = usim_step32_acts_kernel<G, WARM>;
-    return {G == 16 ? Mapping::SPLIT16 : Mapping::SPLIT8, WARM, L, {nullptr, f, (64 / G) * SPLIT_WPR, 128 * SPLIT_WPR, arm_lds_base<1, 1, G>() + ARM_LDS_WORDS}};
+    return {G == 16 ? Mapping::SPLIT16 : Mapping::SPLIT8, WARM, L, {nullptr, f, (64 / G) * SPLIT_WPR, 128 * SPLIT_WPR, arm_lds_base<1, 1, G, L != Launch::STEP>() + ARM_LDS_WORDS}};
 }
 
 // Every step kernel of the library, once.  The compiler emits the kernels in the order in which they are named here: the order is the one the code object has always

@@ -254,10 +254,24 @@ constexpr int MB_GOAL = MB_Q + 100;                   // `fixed` mode with physi
 // between precompute() and hand-off (3) and keeps the seven words in its own mailbox block (written and read by the same wave), so that the Philox rounds leave the
 // chain behind hand-off (1).
 constexpr int MB_ACT = MB_GOAL + 12;                  // the action of the running control step / of the next one (7 words + 1)
-constexpr int X2_STRIDE = MB_ACT + 8;
+// Report written late (split kernel, 16-lane groups, resident launches; arm_report_late below): what the arm wave needs to write the report of pass k during pass k + 1
+// is parked here.  Only the arm wave touches the area, and every word is written and read by lanes of the environment's own group: no hand-off involved.
+constexpr int MB_REP = MB_ACT + 8;
+constexpr int REP_LINK = 0;                           // lane NJ - 1's words of the probe torque sensor: al, ao, s_xso, s_rc, s_wwrc, s_nw, s_arm, X, Y, Z (30 words + 2)   -- parked in the wait
+constexpr int REP_SITE = 32;                          // site frame sx, sy, sz (9 words), obs[9 .. 18] (10 words) + 1                                                       -- parked in the wait
+constexpr int REP_W = 52;                             // contact wrench (6), hand velocity (3), reward, episode return, t, status, done | need << 1, contact count + 1 pad    -- parked behind the state part
+constexpr int REP_SHELL = 68;                         // shell ids of the contacts (launches that report contacts)                                                            -- parked behind the state part
+constexpr int REP_AQ = 76;                            // site acceleration of the constrained arm, component a from task lane a (6 words + 2)                                  -- parked behind the state part
+constexpr int REP_WORDS = 84;
+// which split kernels those are: G lanes per environment, RES = resident (multi-step) launch
+template <int G, bool RES> constexpr bool report_late() { return G == 16 && RES; }
+// words of an environment's mailbox block: the kernels that write the report late (REP) have the area behind MB_ACT, the others keep the block they had
+template <bool REP> constexpr int x2_stride() { return MB_REP + (REP ? REP_WORDS : 0); }
 template <int G> constexpr int x2_base() { return TB_WORDS + (64 * SPLIT_WPR / G) * GE_STRIDE; }
-static_assert(x2_base<16>() % 4 == 0 && x2_base<8>() % 4 == 0 && X2_STRIDE % 4 == 0 && MB_OP % 4 == 0 && MB_W % 4 == 0 && MB_ACT % 4 == 0, "mailbox block: 16-byte accesses");
-static_assert((x2_base<8>() + 32 * X2_STRIDE) * 4 <= 160 * 1024, "split kernel with 8-lane groups: LDS of a CU");
+static_assert(x2_base<16>() % 4 == 0 && x2_base<8>() % 4 == 0 && x2_stride<false>() % 4 == 0 && x2_stride<true>() % 4 == 0 && MB_OP % 4 == 0 && MB_W % 4 == 0 && MB_ACT % 4 == 0
+              && MB_REP % 4 == 0 && REP_SITE % 4 == 0 && REP_W % 4 == 0 && REP_SHELL % 4 == 0 && REP_AQ % 4 == 0 && REP_WORDS % 4 == 0, "mailbox block: 16-byte accesses");
+static_assert((x2_base<8>() + 32 * x2_stride<false>()) * 4 <= 160 * 1024, "split kernel with 8-lane groups: LDS of a CU");
+static_assert(OBS_DIM == 19 && MAXC == 8 && REP_AQ + 8 == REP_WORDS, "layout of the report area");
 // Collision in the split kernel: the broad phase (collide_cull) leaves the ids of the elements that can touch the probe (ascending) in the environment's queue, and the
 // lattice side evaluates the whole queue after hand-off (1) (collide_queue), typically in one pass of its lanes.  Who culls:
 //   8-lane groups:  the arm side, which has the site pose first, runs 7 of the 13 rounds before hand-off (1), while the lattice side still stages its right-hand side and
@@ -293,7 +307,7 @@ template <int ROLE, int G, bool RES> constexpr bool lattice_ahead() { return ROL
 // Who carries what: a single wave (ROLE 0) all of it; the arm wave of the split kernel (ROLE 1) the joint words and `ep`, and of `s` -- 8-lane groups only -- a copy it
 // refreshes from LDS every pass to cull on; the lattice wave (lattice_pass) kst, kdmp, mu and t of `ep`, s, sd and wr, and nothing else.
 constexpr int ARM_LDS_WORDS = A16_LANES * AT_STRIDE;
-template <int TORSO, int ROLE, int G> constexpr int arm_lds_base();
+template <int TORSO, int ROLE, int G, bool RES = false> constexpr int arm_lds_base();
 template <int NE, class WR = NoWarm>
 struct Carry {
     float dqj, qdj, q0j;
@@ -302,11 +316,12 @@ struct Carry {
     WR wr;                                                               // kept contact list of the lane (warm start; NoWarm: nothing)
 };
 
-template <int TORSO, int ROLE, int G> constexpr int arm_lds_base() {
-    return ROLE != 0 ? x2_base<G>() + (64 * SPLIT_WPR / G) * X2_STRIDE : (TORSO ? SOFT16_LDS_WORDS : 16 * X16_RIGID_STRIDE);
+template <int TORSO, int ROLE, int G, bool RES> constexpr int arm_lds_base() {                    // (RES: the split kernels' mailbox blocks depend on it, x2_stride)
+    return ROLE != 0 ? x2_base<G>() + (64 * SPLIT_WPR / G) * x2_stride<report_late<G, RES>()>() : (TORSO ? SOFT16_LDS_WORDS : 16 * X16_RIGID_STRIDE);
 }
 static_assert((arm_lds_base<1, 1, 8>() + ARM_LDS_WORDS) * 4 <= 160 * 1024 && arm_lds_base<1, 1, 8>() % 4 == 0 && arm_lds_base<1, 1, 16>() % 4 == 0 && arm_lds_base<1, 0, 16>() % 4 == 0
-              && arm_lds_base<0, 0, 16>() % 4 == 0, "arm table behind the LDS blocks of every 16-lane kernel");
+              && arm_lds_base<0, 0, 16>() % 4 == 0 && arm_lds_base<1, 1, 16, true>() % 4 == 0 && arm_lds_base<1, 1, 8, true>() == arm_lds_base<1, 1, 8>()
+              && (arm_lds_base<1, 1, 16, true>() + ARM_LDS_WORDS) * 4 <= 160 * 1024, "arm table behind the LDS blocks of every 16-lane kernel");
 
 // One pass of the lattice / contact wave of the split kernel (ROLE 2; its partner, the arm wave, runs step16_one<1, 0, 1, ...>): the soft-torso step (TORSO 1, MODE 0) of the
 // wave's environments from staging the right-hand side to the integrated lattice.  Per environment it
@@ -338,7 +353,7 @@ DI void lattice_pass(float* lds, const DevModel& M, const DevCfg& C, float* __re
 #define LAT(w) st[(size_t)F_LAT * npad + (size_t)ei * LAT_ENV_WORDS + (w)]
 #define EB(off) lds[TB_WORDS + eb * GE_STRIDE + (off)]
     float* const warm_rows = st + warm_index(io.bank_row0, npad, (size_t)ei);      // (dereferenced by handles with warm rows only)
-    int mbo = x2_base<G>() + eb * X2_STRIDE;                            // the environment's mailbox block, its offset opaque: one address register (step16_one)
+    int mbo = x2_base<G>() + eb * x2_stride<report_late<G, RES>()>();                            // the environment's mailbox block, its offset opaque: one address register (step16_one)
     asm volatile("" : "+v"(mbo));
 
     // ---------------- load: the environment's contact parameters and step count, this lane's elements and warm record ----------------
@@ -350,7 +365,7 @@ DI void lattice_pass(float* lds, const DevModel& M, const DevCfg& C, float* __re
     float* const goal_lds = xl + MB_GOAL;                               // [b]
     float at[AT_STRIDE];                                                // [b] down to `jl`
     {
-        constexpr int ARM_LDS = arm_lds_base<1, 2, G>();
+        constexpr int ARM_LDS = arm_lds_base<1, 2, G, RES>();
         const float4* ap = fresh ? reinterpret_cast<const float4*>(M.tables + TB_ARM + gl * AT_STRIDE) : reinterpret_cast<const float4*>(lds + ARM_LDS + gl * AT_STRIDE);
         if (fresh) {
 #pragma unroll
@@ -630,6 +645,14 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & (WPR - 1);      // wave within its role = quad of environments
     // resident state (see Carry): every role of a multi-step launch.  (Before the lattice wave of 16-lane groups ran ahead it reloaded its state every pass instead.)
     constexpr bool LA = lattice_ahead<ROLE, G, RES>();
+    // The report written late (arm wave of the split kernel, 16-lane groups, resident launches).  Behind hand-off (3) a pass has a STATE part -- what the next pass's
+    // kinematics and the lattice wave wait for: the wrench, qacc, the Euler step, the bookkeeping scalars, reward / done / status, the adoption of a bank episode, the
+    // new-episode word -- and a REPORT: the probe torque sensor, the observation row, every global store of the transition and the store of the state words.  The arm wave is
+    // the late one from hand-off (3) to hand-off (2) of the next pass and idle between (2) and (3), so where another pass follows (`defer`) it parks what the report needs in
+    // its own words of the mailbox block (MB_REP) and writes the report in the next pass's wait, before that pass's precompute() and action draw.  The last pass of a
+    // launch writes the pending report there and its own in place, as ever; a launch of one pass is the code it was.  Same operands, same operations, same order: same bits.
+    constexpr bool DEF = ROLE == 1 && report_late<G, RES>();
+    const bool defer = DEF && more;
     const bool fresh = !RES || first_pass;                              // the state comes from HBM (first step of a launch; every single-step launch)
     const int gl = lane & (G - 1), ge = lane / G;
     const int gbase = lane - gl;
@@ -657,7 +680,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     // The mailbox block sits beyond the 64 KB an LDS instruction's immediate offset reaches.  Left to itself the compiler forms one address register per mailbox WORD
     // (block + constant, hoisted out of the step loop) and spills them around the contact solve: 74 registers, two scratch round trips per step in the resident
     // kernel.  The block's offset is therefore made opaque: one address register, the words at immediate offsets from it.
-    int mbo = X2_BASE + eb * X2_STRIDE;
+    int mbo = X2_BASE + eb * x2_stride<ROLE != 0 && report_late<G, RES>()>();
     if constexpr (ROLE != 0) asm volatile("" : "+v"(mbo));
     float* const xl = (ROLE != 0) ? &lds[mbo]
                                   : (TORSO ? &lds[TB_WORDS + eb * GE_STRIDE + GE_WS] : &lds[eb * X16_RIGID_STRIDE]);   // transpose scratch of this environment
@@ -674,7 +697,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
     // ---------------- load: this lane's link record, its joint state, the environment's scalars ----------------
     float at[AT_STRIDE];
     {
-        constexpr int ARM_LDS = arm_lds_base<TORSO, ROLE, G>();
+        constexpr int ARM_LDS = arm_lds_base<TORSO, ROLE, G, RES>();
         const float4* ap = fresh ? reinterpret_cast<const float4*>(M.tables + TB_ARM + gl * AT_STRIDE) : reinterpret_cast<const float4*>(lds + ARM_LDS + gl * AT_STRIDE);
         if (fresh) {
 #pragma unroll
@@ -1181,7 +1204,120 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         RSTAMP(3);
         USIM_BAR();                                                 // (2)
         RSTAMP(4);
+        if constexpr (DEF) {
+            if (!first_pass) {
+                // ================= the report of the pass before (see DEF above), from the words it parked and the state words this wave still holds =================
+                const float* const rp = xl + MB_REP;
+                const bool tr = sub == 0;                                // that pass completed a control step: a transition is pending (and this pass has advanced t)
+                const float4* const wk = reinterpret_cast<const float4*>(&rp[REP_W]);
+                const float4 w0 = wk[0], w1 = wk[1], w2 = wk[2], w3 = wk[3];
+                const int pflags = tr ? __float_as_int(w3.y) : 0;
+                const bool pdone = (pflags & 1) != 0, pneed = (pflags & 2) != 0;
+                if (tr) {
+                    // the rows of that pass: one rollout row back where the launch writes a block (step16_body moved `io` on)
+                    float* p_obs = io.obs; float* p_rew = io.rew; uint8_t* p_done = io.done; float* p_term = io.term_obs; int* p_con = io.contacts;
+                    float* p_ret = io.ep_ret; int* p_len = io.ep_len;
+                    if (io.block) {
+                        const size_t rows = (size_t)n;
+                        p_obs -= rows * OBS_DIM; p_rew -= rows; p_done -= rows;
+                        if (p_term) p_term -= rows * OBS_DIM;
+                        if (p_con) p_con -= rows * (1 + MAXC);
+                        if (p_ret) p_ret -= rows;
+                        if (p_len) p_len -= rows;
+                    }
+                    // probe torque sensor: the last link's lane's operands, read by every lane of the group
+                    const float4* const lk = reinterpret_cast<const float4*>(&rp[REP_LINK]);
+                    const float4 k0 = lk[0], k1 = lk[1], k2 = lk[2], k3 = lk[3], k4 = lk[4], k5 = lk[5], k6 = lk[6], k7 = lk[7];
+                    const f3 p_al = mk(k0.x, k0.y, k0.z), p_ao = mk(k0.w, k1.x, k1.y), p_xso = mk(k1.z, k1.w, k2.x), p_rc = mk(k2.y, k2.z, k2.w), p_wwrc = mk(k3.x, k3.y, k3.z);
+                    const f3 p_nw = mk(k3.w, k4.x, k4.y), p_arm = mk(k4.z, k4.w, k5.x), pX = mk(k5.y, k5.z, k5.w), pY = mk(k6.x, k6.y, k6.z), pZ = mk(k6.w, k7.x, k7.y);
+                    const float4* const sk = reinterpret_cast<const float4*>(&rp[REP_SITE]);
+                    const float4 s0 = sk[0], s1 = sk[1], s2 = sk[2], s3 = sk[3], s4 = sk[4];
+                    const f3 p_sx = mk(s0.x, s0.y, s0.z), p_sy = mk(s0.w, s1.x, s1.y), p_sz = mk(s1.z, s1.w, s2.x);
+                    const float4 q0 = *reinterpret_cast<const float4*>(&rp[REP_AQ]), q1 = *reinterpret_cast<const float4*>(&rp[REP_AQ + 4]);
+                    const f3 alq = mk(q0.w, q1.x, q1.y);
+                    const f3 alt = p_al + alq;
+                    const f3 a7 = p_ao + mk(q0.x, q0.y, q0.z) - cross(alq, p_xso);
+                    const f3 ac = a7 + cross(alt, p_rc) + p_wwrc;
+                    const f3 il = mk(dot(pX, alt), dot(pY, alt), dot(pZ, alt));      // (rot_inertia on the parked frame)
+                    const f3 it = symmul(M.pI7, il);
+                    const f3 N = (pX * it.x + pY * it.y + pZ * it.z) + p_nw;
+                    const f3 Fp = ac * PROBE_MASS;
+                    const f3 tw = N + cross(p_arm, Fp) - mk(w0.w, w1.x, w1.y);
+                    const float po[OBS_DIM] = {w0.x, w0.y, w0.z, dot(p_sx, tw), dot(p_sy, tw), dot(p_sz, tw), w1.z, w1.w, w2.x, s2.y, s2.z, s2.w,
+                                               s3.x, s3.y, s3.z, s3.w, s4.x, s4.y, s4.z};
+                    if (store) {
+                        p_rew[ei] = w2.y;
+                        if (io.status_out) io.status_out[ei] = __float_as_int(w3.x);
+                        p_done[ei] = pdone ? 1 : 0;
+                        if (p_con) {
+                            const float4 h0 = *reinterpret_cast<const float4*>(&rp[REP_SHELL]), h1 = *reinterpret_cast<const float4*>(&rp[REP_SHELL + 4]);
+                            const int sh[MAXC] = {__float_as_int(h0.x), __float_as_int(h0.y), __float_as_int(h0.z), __float_as_int(h0.w),
+                                                  __float_as_int(h1.x), __float_as_int(h1.y), __float_as_int(h1.z), __float_as_int(h1.w)};
+                            p_con[(size_t)ei * (1 + MAXC)] = __float_as_int(w3.z);
+#pragma unroll
+                            for (int k = 0; k < MAXC; ++k) p_con[(size_t)ei * (1 + MAXC) + 1 + k] = sh[k];
+                        }
+                        if (pdone) {
+                            if (p_term) {
+#pragma unroll
+                                for (int a = 0; a < OBS_DIM; ++a) p_term[(size_t)ei * OBS_DIM + a] = po[a];
+                            }
+                            if (p_ret) p_ret[ei] = w2.z;
+                            if (p_len) p_len[ei] = __float_as_int(w2.w);
+                        }
+                        if (p_obs) {
+                            if (!pneed) {
+#pragma unroll
+                                for (int a = 0; a < OBS_DIM; ++a) p_obs[(size_t)ei * OBS_DIM + a] = po[a];
+                            } else {
+                                // the episode ended and the bank's next one was adopted (`episode` is its index): its observation
+                                const int sl = episode & (BANK_DEPTH - 1);
+#pragma unroll
+                                for (int a = 0; a < OBS_DIM; ++a) p_obs[(size_t)ei * OBS_DIM + a] = BK(sl, BOBS + a);
+                            }
+                        }
+                    }
+                }
+                // the state words as that pass left them: nothing has touched them since but t (advanced at the top of a pass that begins a control step)
+                if (valid) {
+                    float* const so = st + scalar_index(0, (size_t)ei);
+                    if (jlane) {
+                        so[F_Q + gl] = dqj; so[F_QD + gl] = qdj;
+                        if (pneed) so[F_Q0 + gl] = q0j;
+                    }
+                    if (gl == 0) {
+                        float4* s4 = reinterpret_cast<float4*>(so);
+                        if (pneed) {
+                            so[F_TS] = ts.x; so[F_TS + 1] = ts.y; so[F_TS + 2] = ts.z;
+                            s4[6] = make_float4(te.x, te.y, te.z, u0);
+                        }
+                        s4[7] = make_float4(vbar, fzbar, fzprev, dfz);
+                        s4[8] = make_float4(kst, kdmp, mu, __int_as_float(tr ? t - 1 : t));
+                        s4[9] = make_float4(__int_as_float(touched), __int_as_float(episode), epret, __int_as_float(status));
+                    }
+                }
+                RSTAMP(29);                                              // dbg[49]: the late report written
+            }
+        }
         precompute();                                                    // ... while the lattice side solves the contacts
+        if constexpr (DEF) {
+            if (defer && last_sub) {
+                // what this pass's report needs and the contact wrench does not change: parked here, where it costs the chain nothing
+                float* const rp = xl + MB_REP;
+                if (gl == NJ - 1) {
+                    float4* const lk = reinterpret_cast<float4*>(&rp[REP_LINK]);
+                    lk[0] = make_float4(al.x, al.y, al.z, ao.x); lk[1] = make_float4(ao.y, ao.z, s_xso.x, s_xso.y); lk[2] = make_float4(s_xso.z, s_rc.x, s_rc.y, s_rc.z);
+                    lk[3] = make_float4(s_wwrc.x, s_wwrc.y, s_wwrc.z, s_nw.x); lk[4] = make_float4(s_nw.y, s_nw.z, s_arm.x, s_arm.y); lk[5] = make_float4(s_arm.z, X.x, X.y, X.z);
+                    lk[6] = make_float4(Y.x, Y.y, Y.z, Z.x); lk[7] = make_float4(Z.y, Z.z, 0.f, 0.f);
+                }
+                if (gl == 0) {
+                    float4* const sk = reinterpret_cast<float4*>(&rp[REP_SITE]);
+                    sk[0] = make_float4(sx.x, sx.y, sx.z, sy.x); sk[1] = make_float4(sy.y, sy.z, sz.x, sz.y);
+                    sk[2] = make_float4(sz.z, fzbar - 5.0f, dfz - 0.0f, vbar - 0.04f);      // obs[9 .. 11]: the bookkeeping scalars as the report finds them behind hand-off (3)
+                    sk[3] = make_float4(obs[12], obs[13], obs[14], obs[15]); sk[4] = make_float4(obs[16], obs[17], obs[18], 0.f);
+                }
+            }
+        }
         if constexpr (AHEAD) {
             // ... and, in what is left of the wait, the action of the next control step (this pass completes one and another pass of the launch follows; after a
             // substep that does not complete one the kept action stays).  Same counters and decoding as in place: every bit of `act` is what it was.
@@ -1294,6 +1430,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         }
         // link accelerations from the site Jacobian: alpha = alpha_bias + Jw qacc, a(o) = a_bias + Jv qacc - (Jw qacc) x (x - o).  Every lane
         // evaluates the sensor on its own link's registers; the last link's lane holds the probe's.
+        if (!defer) {
         float aq[6];
         static_for<6>([&](auto Ac) { constexpr int a = decltype(Ac)::value; aq[a] = rbc<G, TASK_LANE[a]>(aq_t); });
         const f3 alq = mk(aq[3], aq[4], aq[5]);
@@ -1304,6 +1441,11 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         const f3 Fp = ac * PROBE_MASS;
         const f3 tw = N + cross(s_arm, Fp) - mk(W[3], W[4], W[5]);
         tq[0] = rbc<G, NJ - 1>(dot(sx, tw)); tq[1] = rbc<G, NJ - 1>(dot(sy, tw)); tq[2] = rbc<G, NJ - 1>(dot(sz, tw));
+        } else {
+            // report written late: the sensor is evaluated there, from task lane a's component a of the site acceleration
+            tq[0] = 0.f; tq[1] = 0.f; tq[2] = 0.f;
+            if (is_task) xl[MB_REP + REP_AQ + (blk ? 3 + comp : comp)] = aq_t;
+        }
         USIM_STAMP(dbg, 13);
         hv = mk(0, 0, 0);
         if constexpr (MODE == 0) {
@@ -1391,7 +1533,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             const float chk = rbc<G, 7>(prefix_sum<G>(fabsf(qj) + 1e-3f * fabsf(qdj)));
             if (!(chk < 1.0e3f)) { status |= 4; done = true; epret -= reward; reward = 0.f; if (!(epret == epret)) epret = 0.f; }
         }
-        if (store) {
+        if (store && !defer) {
             io.rew[ei] = reward;
             if (io.status_out) io.status_out[ei] = status;
             io.done[ei] = done ? 1 : 0;
@@ -1410,9 +1552,24 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
             }
         }
         need = done && auto_reset;
-        if (store && io.obs && !need) {
+        if (store && io.obs && !need && !defer) {
 #pragma unroll
             for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = obs[a];
+        }
+        if constexpr (DEF) {
+            // report written late: what depends on the contact wrench and on this pass's bookkeeping, as the stores above would have found it (before the adoption of a
+            // bank episode resets the episode scalars)
+            if (defer && gl == 0) {
+                float4* const wk = reinterpret_cast<float4*>(&xl[MB_REP + REP_W]);
+                wk[0] = make_float4(W[0], W[1], W[2], W[3]); wk[1] = make_float4(W[4], W[5], hv.x, hv.y);
+                wk[2] = make_float4(hv.z, reward, epret, __int_as_float(t));
+                wk[3] = make_float4(__int_as_float(status), __int_as_float((done ? 1 : 0) | (need ? 2 : 0)), __int_as_float(ncon), 0.f);
+                if (io.contacts) {
+                    float4* const hk = reinterpret_cast<float4*>(&xl[MB_REP + REP_SHELL]);
+                    hk[0] = make_float4(__int_as_float(con_shell[0]), __int_as_float(con_shell[1]), __int_as_float(con_shell[2]), __int_as_float(con_shell[3]));
+                    hk[1] = make_float4(__int_as_float(con_shell[4]), __int_as_float(con_shell[5]), __int_as_float(con_shell[6]), __int_as_float(con_shell[7]));
+                }
+            }
         }
         }
     }
@@ -1426,7 +1583,7 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         ts = mk(BK(sl, BTS), BK(sl, BTS + 1), BK(sl, BTS + 2)); te = mk(BK(sl, BTE), BK(sl, BTE + 1), BK(sl, BTE + 2));
         u0 = BK(sl, BU0); kst = BK(sl, BKST); kdmp = BK(sl, BKDMP); mu = BK(sl, BMU); fzbar = BK(sl, BFZ);
         episode_begin(E, BKI(sl, BSTATUS));
-        if (store && io.obs) {
+        if (store && io.obs && !defer) {                                 // (report written late: the bank's row is read there)
 #pragma unroll
             for (int a = 0; a < OBS_DIM; ++a) io.obs[(size_t)ei * OBS_DIM + a] = BK(sl, BOBS + a);
         }
@@ -1457,9 +1614,10 @@ DI void step16_one(float* lds, const DevModel& M, const DevCfg& C, float* __rest
         if (gl == 0) *reinterpret_cast<float4*>(&xl[MB_W]) = make_float4(kst, kdmp, mu, (MODE == 0 && need) ? 1.f : 0.f);
     }
     USIM_STAMP(dbg, 15);
+    if constexpr (DEF) { if (more) RSTAMP(28); }                         // dbg[48]: the state part of the pass before the last one done (its report is written late)
 
-    // ---------------- store state: joint words by their lanes, the scalar quads by the group's first lane ----------------
-    if (valid && (MODE == 0 || (need && !refill))) {
+    // ---------------- store state: joint words by their lanes, the scalar quads by the group's first lane (report written late: in the next pass's wait) ----------------
+    if (valid && (MODE == 0 || (need && !refill)) && !defer) {
         float* const so = st + scalar_index(0, (size_t)ei);
         if (jlane) {
             so[F_Q + gl] = dqj; so[F_QD + gl] = qdj;
@@ -1578,8 +1736,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 //     set to its first value again on adoption, never advanced twice.
 //   * MB_W: wrench (lattice wave writes before (3), arm wave reads behind (3)), then the new-episode word (arm wave writes behind those reads, lattice wave reads behind
 //     (1) of the next pass, before it writes the next wrench): every change of hands has a hand-off in between.  MB_POSE is written before (1) of pass k + 1 and was
-//     read between (1) and (2) of pass k; MB_OP is written between (1) and (2) and read between (2) and (3); MB_Q belongs to the lattice wave; the transpose scratch, MB_GOAL
-//     and MB_ACT to the arm wave: hand-off (3) of pass k lies between every such pair.
+//     read between (1) and (2) of pass k; MB_OP is written between (1) and (2) and read between (2) and (3); MB_Q belongs to the lattice wave; the transpose scratch, MB_GOAL,
+//     MB_ACT and MB_REP (the report written late: parked in pass k, read in the wait of pass k + 1 by the same groups' lanes) to the arm wave: hand-off (3) of pass k lies
+//     between every such pair.
 //   * zeroing on reset: the arm wave zeroes the lattice and clears the warm rows in HBM behind (4), so on the last pass only; on the others the lattice wave's next
 //     integration and warm_store overwrite every one of those words from the registers and the record it cleared on adoption.  What a launch leaves in HBM is unchanged.
 // G = 16: 16 environments per workgroup (a quad per wave pair).  G = 8: 32 environments per workgroup (eight per wave pair; two per DPP row) -- the

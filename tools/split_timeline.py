@@ -38,6 +38,15 @@ else:
     for base, title, last in ((20, "arm wave", 9), (30, "lattice wave", 8)):
         v = (rows[:, base + last] - rows[:, base + 6]) + (rows[:, base + 2] - rows[:, base])
         print(f"== step boundary, {title}: hand-off (3) -> end of the pass + start -> hand-off (1) passed   {np.median(v):9.0f}   (pieced together; excludes the wait at the barrier between the passes)")
+# The report written late (csrc/usim_step16.h, DEF of step16_one; 16-lane groups, USIM_PROFILE_NSUB > 1): dbg[48] = the arm wave's state part of the pass before the last
+# one done (counted from that pass's hand-off (3), dbg[63]), dbg[49] = that pass's report written in the last pass's wait (counted from the last pass's hand-off (2)).
+if rows.shape[1] > 63 and (rows[:, 48:50] > 0).all() and (rows[:, 63] > 0).all():
+    print(f"== report written late, arm wave: hand-off (3) of the pass before -> its state part done   {np.median(rows[:, 48] - rows[:, 63]):9.0f}")
+    print(f"                                  state part done -> hand-off (1) passed                  {np.median(rows[:, 22] - rows[:, 48]):9.0f}")
+    print(f"                                  hand-off (2) passed -> the pending report written       {np.median(rows[:, 49] - rows[:, 24]):9.0f}")
+    print(f"                                  the pending report written -> precompute + draw done    {np.median(rows[:, 25] - rows[:, 49]):9.0f}")
+else:
+    print("== report written late: not recorded (a library without it, 8-lane groups or a launch of one pass)")
 print(f"   (contact_solve entered at {np.median(rows[:, 40] - t0[:, 0]):.0f}, left at {np.median(rows[:, 44] - t0[:, 0]):.0f}: median ticks since the step's start; ncmax of this quad varies)")
 for i, nm in enumerate(["contact list ready", "ncmax known", "before contact_solve", "after contact_solve"]):
     print(f"   x{i} {nm:32s} {np.median(rows[:, 50 + i] - t0[:, 0]):9.0f}")

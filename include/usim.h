@@ -466,6 +466,58 @@ int usim_plan_sample(float* mean_dev, const float* sigma_dev, const float* act_l
 int usim_plan_update(const float* cand_dev, const float* ret_dev, const float* act_low_dev, const float* act_high_dev, int groups, int per_group, int horizon, int act_dim,
                      float temperature, float* plan_dev, float* next_mean_dev, float* act_dev, int32_t* best_dev, float* weight_dev, void* stream);
 
+/* ---- the guided planner: a critic's value behind the horizon, the actor's action as the tail of the nominal, cross-entropy refits inside a control step
+ * (csrc/usim_score.hip, csrc/usim_plan.hip; planner.py MPPIPlanner(critic=, tail_action=, iterations=)).  The four calls keep the contract
+ * of usim_plan_*: no handle; kernel launches on `stream` and nothing else -- no allocation, no synchronisation, capture-safe --; float32 in an order fixed by the code,
+ * no floating-point atomics, nothing ordered by arrival, so the result is a function of the inputs alone and the result of a group (of an environment, for the score)
+ * does not depend on the others.  USIM_ERR_INVALID before anything is enqueued: a NULL required pointer, a size <= 0 (or G K, G H beyond INT_MAX), act_dim outside
+ * 1 .. 8, a scalar that is not finite or outside the range stated below.
+ *
+ * usim_score_block_tail: usim_score_block -- the same loop, the same bits for return_dev and length_dev -- and then, for an environment with NO done inside the block,
+ *     return_dev[i] = fmaf(disc_T, s * tail_dev[i], return_dev[i])
+ *   disc_T is the loop's own running discount after its nsteps steps (disc = 1; disc *= gamma per step, float32);  s = (float)sqrt(*ret_var_dev + epsilon), the sum
+ *   and the root in float64 -- a critic trained under VecNormalize's norm_reward speaks in units of normalised return, s takes its value back to raw reward
+ *   (usim_norm_stats.ret_var / .epsilon); ret_var_dev == NULL: s = 1 (epsilon is then unused).  tail_dev [n] of an environment that ended inside the block -- on its
+ *   last step included -- is never read: a NaN there has no effect.  A non-finite tail of a survivor makes its return non-finite (usim_plan_update gives such a
+ *   candidate weight 0).  tail_dev == NULL: usim_score_block.  gamma and epsilon must be finite, epsilon >= 0; length_dev may be NULL.
+ *
+ * usim_plan_sample_elem: usim_plan_sample with sigma_elem_dev [G][H][A] in place of sigma_dev [A]: the sample is fmaf(sigma_elem[g][t][a], e, m).  Noise keys, smoothing,
+ *   restart handling (sigma_elem_dev is not touched by a restart) and clip are usim_plan_sample's; with sigma_elem[g][t][a] = sigma[a] so are the bits.
+ *
+ * usim_plan_refit: one cross-entropy refit of (mean_dev, sigma_elem_dev), both [G][H][A] and updated in place, per group g from cand_dev [H][n][A] and ret_dev [n]:
+ *   the ELITE SET is the min(elites, number of finite returns) candidates with the largest finite returns under the total order "larger return, then lower index"
+ *   (+0 and -0 are equal); a candidate with a non-finite return is never elite.  elite_dev [G][elites] int32 (may be NULL) receives the group's elite indices k in
+ *   ASCENDING candidate index, padded with -1.  With E elites x_1 .. x_E = cand[t][g K + k][a] taken in that ascending order, per word (t, a), float32:
+ *     s = s + x_i from 0;  m = s / E;   q = fmaf(d_i, d_i, q) from 0 with d_i = x_i - m;  sd = sqrtf(q / E)     (the population variance about m)
+ *     mean[g][t][a]  = clip(fmaf(momentum, mean_old, c m), low[a], high[a])        c = (float)(1 - (double)momentum), rounded once on the host
+ *     sigma[g][t][a] = fmaxf(fmaf(momentum, sigma_old, c sd), sigma_min)           a non-finite word of mean_old counts as 0, as in the sampler
+ *   A group without a finite return keeps its mean and sigma bit for bit and gets all -1.  elites in 1 .. K, momentum in [0, 1), sigma_min > 0 and finite.
+ *   K <= USIM_PLAN_REFIT_MAX_K = 4096, a larger per_group is refused: one workgroup per group ranks the group ONCE -- its K returns in LDS (9 K bytes with the list and
+ *   the flags: 36 KB at the limit), every candidate's rank by counting, K^2 / 256 comparisons per thread (65536 at the limit, about 0.1 ms) -- and then reduces the
+ *   H A words, one thread per word; twice the K would quadruple the ranking time of a launch that runs between 18 us simulator steps.
+ *
+ * usim_plan_tail: the actor's action at each candidate's final observation as that candidate's step H, into the LAST step of the shifted nominal:
+ *     x_k = pol_act_dev[g K + k]   where length_dev[g K + k] == H and done_last_dev[g K + k] == 0  (the candidate played all H steps and did not end on the last one)
+ *     x_k = cand[H - 1][g K + k]   otherwise (its own last action, what usim_plan_update keeps there)
+ *   length_dev [n] int32 is usim_score_block's, which is H both for a survivor and for an episode that ended on step H; done_last_dev [n] uint8 is the slice
+ *   done[H - 1] of the rollout block and tells them apart.  pol_act_dev [n][A] of a candidate that ended is never read.
+ *   temperature > 0:  next_mean[g][H - 1][a] = clip(sum_k w_k x_k[a], low[a], high[a])  with w = weight_dev [n] as usim_plan_update wrote it, in that kernel's three
+ *   stages (thread j of 256 takes k = j, j + 256, ... ascending, acc = fmaf(w_k, x_k, acc) from 0; the butterfly 32 .. 1 inside a wave; ((w0 + w1) + w2) + w3);
+ *   a candidate with w_k == 0 is skipped -- the same bits for every finite x_k, and a non-finite action without weight does not reach the nominal.
+ *   temperature == 0:  next_mean[g][H - 1] = x_best, best = best_dev[g], bit for bit (no clip); a best_dev[g] outside [0, K) writes nothing.
+ *   No other word of next_mean_dev is written; call it after the usim_plan_update that wrote next_mean_dev, on the same stream.  All pointers are required. */
+#define USIM_PLAN_REFIT_MAX_K 4096
+int usim_score_block_tail(const float* rew_block_dev, const uint8_t* done_block_dev, int nsteps, int n, float gamma, const float* tail_dev, const double* ret_var_dev,
+                          double epsilon, float* return_dev, int32_t* length_dev, void* stream);
+int usim_plan_sample_elem(float* mean_dev, const float* sigma_elem_dev, const float* act_low_dev, const float* act_high_dev, const uint8_t* restart_dev, int groups,
+                          int per_group, int horizon, int act_dim, float smoothing, uint64_t seed, uint32_t counter, const uint32_t* counter_base_dev, float* cand_dev,
+                          void* stream);
+int usim_plan_refit(const float* cand_dev, const float* ret_dev, const float* act_low_dev, const float* act_high_dev, int groups, int per_group, int horizon, int act_dim,
+                    int elites, float momentum, float sigma_min, float* mean_dev, float* sigma_elem_dev, int32_t* elite_dev, void* stream);
+int usim_plan_tail(const float* cand_dev, const float* weight_dev, const int32_t* best_dev, const int32_t* length_dev, const uint8_t* done_last_dev,
+                   const float* pol_act_dev, const float* act_low_dev, const float* act_high_dev, int groups, int per_group, int horizon, int act_dim, float temperature,
+                   float* next_mean_dev, void* stream);
+
 /* ---- the caller's side of env.step() on the device: SB3 VecNormalize + MlpPolicy forward + sampling + rollout-buffer
  * writes + GAE, fused into a few kernels per rollout step (csrc/usim_policy.hip).  Everything is a device pointer into the CALLER's tensors
  * (torch parameters, policy.DeviceVecNormalize statistics, policy.DeviceRolloutBuffer slices); the library keeps no copy. ---- */

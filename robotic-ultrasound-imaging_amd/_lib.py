@@ -29,6 +29,7 @@ PACK_EPISODE_WORDS = 23            # USIM_PACK_EPISODE_WORDS: env index, ep_leng
 MONITOR_HEADER_WORDS = 16          # USIM_MONITOR_HEADER_WORDS: episodes, length_sum, return_sum, truncated, launches (64 bits each), six zero words
 MONITOR_ROW_WORDS = 4              # USIM_MONITOR_ROW_WORDS: ep_return bits, ep_length, environment index, launch number
 MONITOR_MAX_WINDOW = 1 << 20       # USIM_MONITOR_MAX_WINDOW
+PLAN_REFIT_MAX_K = 4096            # USIM_PLAN_REFIT_MAX_K: candidates per group usim_plan_refit ranks
 METRICS = 13                       # USIM_METRICS: the metrics of error_metrics.METRICS, in that order
 METRICS_HEADER_WORDS = 64          # USIM_METRICS_HEADER_WORDS: episodes, launches, length_sum, nonfinite (64 bits each), total[13], total_sq[13] (float64), four zero words
 METRICS_ROW_WORDS = 32             # USIM_METRICS_ROW_WORDS: 13 float64 metrics, environment index, episode length, launch number, three zero words
@@ -182,6 +183,13 @@ SYMBOLS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_plan_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_score_block_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_plan_sample_elem": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64,
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_plan_refit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_plan_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_float, C.c_void_p, C.c_void_p]),
     "usim_ppo_params": (C.c_int, [C.c_int]),
     "usim_ppo_work_floats": (C.c_int64, [C.c_int]),
     "usim_ppo_grad": (C.c_int, [C.POINTER(UsimPolicyNet), C.POINTER(UsimPpoBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -20,6 +20,10 @@
 //      numbers, so all lanes end with the same bits; best: the pair (value, index) under "larger value, then lower index", a total order)
 //   3. the four waves' results meet through LDS as ((w0 + w1) + w2) + w3
 // The same three stages serve the argmax, the normaliser sum_k exp((ret_k - ret_best) / temperature) and the A weighted sums of the slab.
+//
+// The guided planner adds three launches (include/usim.h states their arithmetic): usim_plan_sample_elem, the sampler with one standard deviation per element of the
+// nominal (the same kernel body, a template parameter); usim_plan_refit, a cross-entropy refit of the nominal and those deviations from a group's elite candidates,
+// between the rounds of one control step; usim_plan_tail, the last step of the shifted nominal from the actor's actions, after usim_plan_update.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -35,6 +39,8 @@ constexpr int PN_WAVES = PN_WG / 64;
 constexpr int PN_MAXA = 8;                                       // act_dim <= 8: four Philox blocks per (candidate, step), eight accumulators per thread
 constexpr uint32_t PLAN_TAG = 0x504c414eu;                       // fourth counter word of the planner's noise ("PLAN"; the policy's is "POLY")
 
+// ELEM: sigma is [G][H][A], one standard deviation per element of the nominal (usim_plan_sample_elem), not [A]; nothing else differs
+template <bool ELEM>
 __global__ __launch_bounds__(PN_WG) void usim_plan_sample_kernel(float* __restrict__ mean, const float* __restrict__ sigma, const float* __restrict__ act_low,
                                                                  const float* __restrict__ act_high, const uint8_t* __restrict__ restart, int per_group, int horizon,
                                                                  int adim, size_t words, float smooth, float fresh, uint32_t key0, uint32_t key1, uint32_t ctr0,
@@ -46,7 +52,9 @@ __global__ __launch_bounds__(PN_WG) void usim_plan_sample_kernel(float* __restri
     const uint32_t ctr = ctr0 + (ctr_base ? *ctr_base : 0u);      // call counter: host part + a device word (a recorded graph advances the latter)
     const bool fresh_nominal = restart && restart[g] != 0;       // the group's environment has just started an episode: nominal 0, also written back (by candidate 0)
     float* mrow = mean + (size_t)g * horizon * adim + a;
-    const float sg = sigma[a], lo = act_low[a], hi = act_high[a];
+    const float* srow = ELEM ? sigma + (size_t)g * horizon * adim + a : sigma + a;
+    const float lo = act_low[a], hi = act_high[a];
+    float sg = ELEM ? 0.f : srow[0];
     float e = 0.f;
     for (int t = 0; t < horizon; ++t) {
         float m = 0.f;
@@ -64,6 +72,7 @@ __global__ __launch_bounds__(PN_WG) void usim_plan_sample_kernel(float* __restri
             const float xi = (a & 1) ? rad * __sinf(ang) : rad * __cosf(ang);
             e = t == 0 ? xi : fmaf(smooth, e, fresh * xi);
         }
+        if (ELEM) sg = srow[(size_t)t * adim];
         cand[(size_t)t * words + i] = fminf(fmaxf(fmaf(sg, e, m), lo), hi);
     }
 }
@@ -167,6 +176,124 @@ __global__ __launch_bounds__(PN_WG) void usim_plan_update_kernel(const float* __
     if (tid < adim) plan_store(fminf(fmaxf(mine, act_low[tid]), act_high[tid]), g, t, tid, horizon, adim, plan, next_mean, act);
 }
 
+// ---- usim_plan_refit: one cross-entropy refit of (mean, sigma_elem) per group; one workgroup per group ranks its K returns ONCE, then reduces the H A words ----
+// key[k] is the return, -inf for a non-finite one (it then loses against every finite return and is never elite itself).  Rank of a finite candidate = how many
+// candidates come before it under "larger return, then lower index" (`better`, a total order): every thread takes candidates tid, tid + 256, ... and walks all K keys,
+// which every lane reads at the same LDS address (a broadcast) -- K^2 / 256 comparisons per thread, 65536 at the largest K.  Elite <=> rank < elites, so exactly
+// min(elites, finite returns) candidates are.  The place of an elite in the list is the number of elites below its index: the list ascends in candidate index, whatever
+// order the threads run in.  The count meets in an LDS INTEGER atomic (an integer sum does not depend on the order of arrival).
+// Then thread j takes the words w = j, j + 256, ... of the group's [H][A] block (w = t A + a) and walks the list in ascending order, all in float32:
+//   s = s + x from 0;  m = s / E;  d = x - m, q = fmaf(d, d, q) from 0;  sd = sqrtf(q / E)
+//   mean = clip(fmaf(momentum, mean_old, c m), low, high);  sigma = fmaxf(fmaf(momentum, sigma_old, c sd), sigma_min),  c = (float)(1 - (double)momentum) from the host
+// Every word is read and written by one thread, so the update is in place.  LDS: 4 K bytes of keys, 4 K of list, K of flags = 36 KB at K = 4096.
+constexpr int PN_REFIT_MAXK = USIM_PLAN_REFIT_MAX_K;
+
+__global__ __launch_bounds__(PN_WG) void usim_plan_refit_kernel(const float* __restrict__ cand, const float* __restrict__ ret, const float* __restrict__ act_low,
+                                                                const float* __restrict__ act_high, int per_group, int horizon, int adim, size_t n, int elites,
+                                                                float momentum, float fresh, float sigma_min, float* __restrict__ mean, float* __restrict__ sigma,
+                                                                int32_t* __restrict__ elite_out) {
+    __shared__ float key[PN_REFIT_MAXK];
+    __shared__ int list[PN_REFIT_MAXK];
+    __shared__ uint8_t flag[PN_REFIT_MAXK];
+    __shared__ int count;
+    const int tid = threadIdx.x, K = per_group, g = (int)blockIdx.x;
+    const size_t first = (size_t)g * K;
+    if (tid == 0) count = 0;
+    for (int k = tid; k < K; k += PN_WG) {
+        const float v = ret[first + k];
+        key[k] = isfinite(v) ? v : -INFINITY;
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int k = tid; k < K; k += PN_WG) {
+        const float v = key[k];
+        int rank = 0;
+        for (int j = 0; j < K; ++j) rank += better(key[j], j, v, k) ? 1 : 0;
+        const bool elite = v != -INFINITY && rank < elites;
+        flag[k] = elite ? 1 : 0;
+        mine += elite ? 1 : 0;
+    }
+    if (mine) atomicAdd(&count, mine);
+    __syncthreads();
+    for (int k = tid; k < K; k += PN_WG) {
+        if (!flag[k]) continue;
+        int place = 0;
+        for (int j = 0; j < k; ++j) place += flag[j];
+        list[place] = k;                                         // place < count <= min(elites, K)
+    }
+    __syncthreads();
+    const int E = count;
+    if (elite_out)
+        for (int p = tid; p < elites; p += PN_WG) elite_out[(size_t)g * elites + p] = p < E ? list[p] : -1;
+    if (E == 0) return;                                          // no finite return: mean and sigma stay as they are
+
+    const int words = horizon * adim;
+    const float fe = (float)E;
+    for (int w = tid; w < words; w += PN_WG) {
+        const int t = w / adim, a = w - t * adim;
+        const float* __restrict__ col = cand + ((size_t)t * n + first) * adim + a;      // cand[t][g K + k][a] = col[k A]
+        float s = 0.f;
+        for (int p = 0; p < E; ++p) s += col[(size_t)list[p] * adim];
+        const float m = s / fe;
+        float q = 0.f;
+        for (int p = 0; p < E; ++p) {
+            const float d = col[(size_t)list[p] * adim] - m;
+            q = fmaf(d, d, q);
+        }
+        const float sd = sqrtf(q / fe);
+        const size_t word = (size_t)g * words + w;
+        float mo = mean[word];
+        if (!isfinite(mo)) mo = 0.f;                             // as the sampler reads the nominal
+        mean[word] = fminf(fmaxf(fmaf(momentum, mo, fresh * m), act_low[a]), act_high[a]);
+        sigma[word] = fmaxf(fmaf(momentum, sigma[word], fresh * sd), sigma_min);
+    }
+}
+
+// ---- usim_plan_tail: the last step of the shifted nominal from the actor's action at each candidate's final observation; one workgroup per group ----
+// x_k = pol_act[g K + k] where the candidate played all H steps without a done (length == H and done_last == 0), else its own last action cand[H - 1][g K + k].  The
+// weights are those usim_plan_update wrote, and the sum runs in that kernel's three stages (file header).  A candidate of weight 0 is skipped: fmaf(0, x, acc) = acc
+// for every finite x, and a non-finite action of a candidate that carries no weight must not reach the nominal.
+__global__ __launch_bounds__(PN_WG) void usim_plan_tail_kernel(const float* __restrict__ cand, const float* __restrict__ weight, const int32_t* __restrict__ best,
+                                                               const int32_t* __restrict__ length, const uint8_t* __restrict__ done_last,
+                                                               const float* __restrict__ pol_act, const float* __restrict__ act_low, const float* __restrict__ act_high,
+                                                               int per_group, int horizon, int adim, size_t n, float temperature, float* __restrict__ next_mean) {
+    __shared__ float slab_sum[PN_MAXA][PN_WAVES];
+    const int tid = threadIdx.x, K = per_group, g = (int)blockIdx.x;
+    const size_t first = (size_t)g * K;
+    const float* __restrict__ last = cand + ((size_t)(horizon - 1) * n + first) * adim;  // cand[H - 1][g K .. g K + K)
+    const float* __restrict__ pol = pol_act + first * adim;
+    float* __restrict__ out = next_mean + ((size_t)g * horizon + (horizon - 1)) * adim;
+
+    if (temperature == 0.f) {                                    // a selection: the best candidate's x as it is
+        const int k = best[g];
+        if (tid < adim && k >= 0 && k < K) {                     // (an index from device memory: outside the group nothing is written)
+            const bool whole = length[first + k] == horizon && done_last[first + k] == 0;
+            out[tid] = (whole ? pol : last)[(size_t)k * adim + tid];
+        }
+        return;
+    }
+
+    float acc[PN_MAXA];
+#pragma unroll
+    for (int a = 0; a < PN_MAXA; ++a) acc[a] = 0.f;
+    for (int k = tid; k < K; k += PN_WG) {
+        const float w = weight[first + k];
+        if (w == 0.f) continue;
+        const bool whole = length[first + k] == horizon && done_last[first + k] == 0;
+        const float* __restrict__ row = (whole ? pol : last) + (size_t)k * adim;
+#pragma unroll
+        for (int a = 0; a < PN_MAXA; ++a)
+            if (a < adim) acc[a] = fmaf(w, row[a], acc[a]);
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int a = 0; a < PN_MAXA; ++a) {
+        const float v = wg_sum(acc[a], slab_sum[a]);
+        if (a == tid) mine = v;
+    }
+    if (tid < adim) out[tid] = fminf(fmaxf(mine, act_low[tid]), act_high[tid]);
+}
+
 }  // namespace usim
 
 static bool plan_shape_ok(int groups, int per_group, int horizon, int act_dim) {
@@ -182,7 +309,7 @@ extern "C" int usim_plan_sample(float* mean_dev, const float* sigma_dev, const f
     if (!(smoothing >= 0.f && smoothing < 1.f)) return USIM_ERR_INVALID;                    // (a NaN fails both comparisons)
     const float fresh = (float)sqrt(1.0 - (double)smoothing * (double)smoothing);           // the weight of the new draw, rounded once
     const size_t words = (size_t)groups * per_group * act_dim;
-    hipLaunchKernelGGL(usim_plan_sample_kernel, dim3((unsigned)((words + PN_WG - 1) / PN_WG)), dim3(PN_WG), 0, (hipStream_t)stream, mean_dev, sigma_dev, act_low_dev,
+    hipLaunchKernelGGL(usim_plan_sample_kernel<false>, dim3((unsigned)((words + PN_WG - 1) / PN_WG)), dim3(PN_WG), 0, (hipStream_t)stream, mean_dev, sigma_dev, act_low_dev,
                        act_high_dev, restart_dev, per_group, horizon, act_dim, words, smoothing, fresh, (uint32_t)seed, (uint32_t)(seed >> 32), counter,
                        counter_base_dev, cand_dev);
     return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
@@ -196,5 +323,45 @@ extern "C" int usim_plan_update(const float* cand_dev, const float* ret_dev, con
     if (!(temperature >= 0.f) || !isfinite(temperature)) return USIM_ERR_INVALID;
     hipLaunchKernelGGL(usim_plan_update_kernel, dim3((unsigned)groups * (unsigned)horizon), dim3(PN_WG), 0, (hipStream_t)stream, cand_dev, ret_dev, act_low_dev,
                        act_high_dev, per_group, horizon, act_dim, (size_t)groups * per_group, temperature, plan_dev, next_mean_dev, act_dev, best_dev, weight_dev);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+extern "C" int usim_plan_sample_elem(float* mean_dev, const float* sigma_elem_dev, const float* act_low_dev, const float* act_high_dev, const uint8_t* restart_dev,
+                                     int groups, int per_group, int horizon, int act_dim, float smoothing, uint64_t seed, uint32_t counter,
+                                     const uint32_t* counter_base_dev, float* cand_dev, void* stream) {
+    using namespace usim;
+    if (!mean_dev || !sigma_elem_dev || !act_low_dev || !act_high_dev || !cand_dev || !plan_shape_ok(groups, per_group, horizon, act_dim)) return USIM_ERR_INVALID;
+    if (!(smoothing >= 0.f && smoothing < 1.f)) return USIM_ERR_INVALID;
+    const float fresh = (float)sqrt(1.0 - (double)smoothing * (double)smoothing);
+    const size_t words = (size_t)groups * per_group * act_dim;
+    hipLaunchKernelGGL(usim_plan_sample_kernel<true>, dim3((unsigned)((words + PN_WG - 1) / PN_WG)), dim3(PN_WG), 0, (hipStream_t)stream, mean_dev, sigma_elem_dev,
+                       act_low_dev, act_high_dev, restart_dev, per_group, horizon, act_dim, words, smoothing, fresh, (uint32_t)seed, (uint32_t)(seed >> 32), counter,
+                       counter_base_dev, cand_dev);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+extern "C" int usim_plan_refit(const float* cand_dev, const float* ret_dev, const float* act_low_dev, const float* act_high_dev, int groups, int per_group, int horizon,
+                               int act_dim, int elites, float momentum, float sigma_min, float* mean_dev, float* sigma_elem_dev, int32_t* elite_dev, void* stream) {
+    using namespace usim;
+    if (!cand_dev || !ret_dev || !act_low_dev || !act_high_dev || !mean_dev || !sigma_elem_dev || !plan_shape_ok(groups, per_group, horizon, act_dim))
+        return USIM_ERR_INVALID;
+    if (per_group > PN_REFIT_MAXK || elites < 1 || elites > per_group || (int64_t)horizon * act_dim > INT_MAX) return USIM_ERR_INVALID;
+    if (!(momentum >= 0.f && momentum < 1.f) || !(sigma_min > 0.f) || !isfinite(sigma_min)) return USIM_ERR_INVALID;       // (a NaN fails the comparisons)
+    const float fresh = (float)(1.0 - (double)momentum);         // the weight of the elites' moments, rounded once
+    hipLaunchKernelGGL(usim_plan_refit_kernel, dim3((unsigned)groups), dim3(PN_WG), 0, (hipStream_t)stream, cand_dev, ret_dev, act_low_dev, act_high_dev, per_group,
+                       horizon, act_dim, (size_t)groups * per_group, elites, momentum, fresh, sigma_min, mean_dev, sigma_elem_dev, elite_dev);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+extern "C" int usim_plan_tail(const float* cand_dev, const float* weight_dev, const int32_t* best_dev, const int32_t* length_dev, const uint8_t* done_last_dev,
+                              const float* pol_act_dev, const float* act_low_dev, const float* act_high_dev, int groups, int per_group, int horizon, int act_dim,
+                              float temperature, float* next_mean_dev, void* stream) {
+    using namespace usim;
+    if (!cand_dev || !weight_dev || !best_dev || !length_dev || !done_last_dev || !pol_act_dev || !act_low_dev || !act_high_dev || !next_mean_dev ||
+        !plan_shape_ok(groups, per_group, horizon, act_dim))
+        return USIM_ERR_INVALID;
+    if (!(temperature >= 0.f) || !isfinite(temperature)) return USIM_ERR_INVALID;
+    hipLaunchKernelGGL(usim_plan_tail_kernel, dim3((unsigned)groups), dim3(PN_WG), 0, (hipStream_t)stream, cand_dev, weight_dev, best_dev, length_dev, done_last_dev,
+                       pol_act_dev, act_low_dev, act_high_dev, per_group, horizon, act_dim, (size_t)groups * per_group, temperature, next_mean_dev);
     return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
 }

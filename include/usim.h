@@ -611,6 +611,39 @@ int usim_policy_bootstrap(const usim_policy_net* net, const usim_norm_stats* st,
 int usim_policy_gae(const float* rewards_dev, const float* values_dev, const float* episode_starts_dev, const float* last_values_dev, const uint8_t* last_done_dev,
                     int T, int n, float gamma, float gae_lambda, float* advantages_dev, float* returns_dev, void* stream);
 
+/* ---- policy populations: K networks ("members") in one rollout (population.py).  n = K G environments, member k owning environments
+ * [k G, (k + 1) G) of every [n]... buffer; K = members, G = envs_per_member, A = act_dim, P = usim_ppo_params(A).  The three calls take no handle, are kernel launches on
+ * `stream` and nothing else (capture-safe: no allocation, no synchronisation, no host read of device memory) and use no floating-point atomics.  Shared layout:
+ *   theta_dev   [K][stride] floats: row k is member k's flat parameter block in the field order of usim_ppo_params (pi_w1 pi_b1 pi_w2 pi_b2 act_w act_b vf_w1 vf_b1
+ *               vf_w2 vf_b2 val_w val_b log_std); stride >= P and a multiple of 4 (words behind P in a row are never read)
+ *   packed_dev  [K][USIM_POLICY_PACKED] floats on the 16-byte grid: row k is what usim_policy_pack writes for member k
+ *   st          a usim_norm_stats whose pointers hold K consecutive copies of what they hold for one network: obs_mean / obs_var [K][19]; obs_count, ret_mean, ret_var,
+ *               ret_count [K]; returns [n] (member k's accumulators are its environments'); scratch [K][USIM_POLICY_SCRATCH], zero-initialised once; clip_obs,
+ *               clip_reward, gamma and epsilon are shared by all members
+ * Each call computes, bit for bit -- every output word and every word of the statistics --, what K calls of its single-network counterpart compute, call k made with
+ * member k's network and statistics, the slices [k G, (k + 1) G) of every per-environment buffer, n = G and (usim_policy_step) env_offset + k G.  A member reads and
+ * writes its own rows only: a NaN in another member's observations, weights or statistics does not reach it.  Any G >= 1: a member's last workgroup handles its tail as
+ * the single-network call handles n % 32.
+ * USIM_ERR_INVALID before anything is enqueued: a NULL required pointer (named per call below), members or envs_per_member <= 0, K G beyond INT_MAX,
+ * members > USIM_POLICY_MAX_MEMBERS (the member is a grid axis), act_dim outside 1 .. 8 (usim_policy_step itself accepts 1 .. 7: at 8 the equality above has no
+ * single-network side), stride < P or not a multiple of 4, packed_dev off the 16-byte grid.
+ *
+ * usim_policy_pack_multi: one launch, grid (64, K).  Required: theta_dev, packed_dev.  Pack again after every change of any member's weights.
+ * usim_policy_step_multi: usim_policy_step for every member -- grid (ceil(G / 32), 2, K), preceded when training == 1 by the statistics launch, grid (32, K).
+ *   obs_dev [n][19], prev_done_dev [n] or NULL, act_low_dev / act_high_dev [A] (shared), out: [n]... buffers as for usim_policy_step.  Required: theta_dev, packed_dev,
+ *   st with obs_mean and obs_var (training == 1: obs_count and scratch too), obs_dev, act_low_dev, act_high_dev, out, out->act_env_dev.  There is no multi form of
+ *   usim_policy_step_fused (its cross-workgroup wait would have to become per member) nor of usim_policy_bootstrap; usim_policy_gae is per environment and serves as it is.
+ * usim_policy_reward_multi: usim_policy_reward for every member in one launch -- grid (33, K) with next_obs_dev [n][19] while training, else (1, K).  raw_sum_dev: [K]
+ *   doubles or NULL, member k's sum of raw rewards is added to word k.  Required: st with ret_var (training: ret_mean, ret_count, returns; with next_obs_dev also obs_mean,
+ *   obs_var, obs_count, scratch), rew_dev, done_dev, nrew_dev. ---- */
+#define USIM_POLICY_MAX_MEMBERS 65535
+int usim_policy_pack_multi(const float* theta_dev, int stride, int members, int act_dim, float* packed_dev, void* stream);
+int usim_policy_step_multi(const float* theta_dev, int stride, const float* packed_dev, const usim_norm_stats* st, const float* obs_dev, const uint8_t* prev_done_dev,
+                           int members, int envs_per_member, int act_dim, const float* act_low_dev, const float* act_high_dev, uint64_t seed, uint32_t counter,
+                           const uint32_t* counter_base_dev, int env_offset, int training, int deterministic, const usim_policy_out* out, void* stream);
+int usim_policy_reward_multi(const usim_norm_stats* st, const float* rew_dev, const uint8_t* done_dev, int members, int envs_per_member, int training, int norm_reward,
+                             float* nrew_dev, double* raw_sum_dev, const float* next_obs_dev, void* stream);
+
 /* ---- the learner: one PPO minibatch step on the device (csrc/usim_ppo.hip; ppo.py NativePPO) -- the loss of stable-baselines3's
  * PPO.train on one minibatch of the rollout buffer with its gradient for every parameter of the usim_policy_net above (A <= 8), and clip_grad_norm_ +
  * torch.optim.Adam.step on one flat parameter block.  Both calls check their arguments before anything is enqueued (USIM_ERR_INVALID: a NULL required pointer, act_dim

@@ -15,7 +15,10 @@ from . import episode_log, error_metrics, evaluation, imitation, learner, monito
 from .monitor import DeviceMonitor, evaluate_policy, write_scalar_csv  # noqa: E402
 from .evaluation import DeviceEpisodeMetrics, EpisodeRecorder, evaluate_episodes  # noqa: E402
 from .imitation import DAggerTrainer, DemoBuffer, NativeBC, PlannerExpert, PolicyExpert, distill  # noqa: E402
+from . import population  # noqa: E402  (K policies in one rollout: evaluated and trained side by side)
+from .population import PolicyPopulation, PopulationPPO, PopulationRollout, PopulationVecNormalize, evaluate_population  # noqa: E402
 
 __all__ = ["UltrasoundVecEnv", "UltrasoundEnv", "Box", "default_robosuite_kwargs", "load_yaml", "make_config", "policy", "planner", "ppo", "monitor", "DeviceMonitor",
            "evaluate_policy", "write_scalar_csv", "episode_log", "error_metrics", "evaluation", "DeviceEpisodeMetrics", "EpisodeRecorder", "evaluate_episodes", "imitation", "learner", "DemoBuffer", "NativeBC",
-           "PolicyExpert", "PlannerExpert", "DAggerTrainer", "distill", "_lib"]
+           "PolicyExpert", "PlannerExpert", "DAggerTrainer", "distill", "population", "PolicyPopulation", "PopulationVecNormalize",
+           "PopulationRollout", "PopulationPPO", "evaluate_population", "_lib"]

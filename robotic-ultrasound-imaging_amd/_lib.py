@@ -15,7 +15,8 @@ MAXC = 8
 NSCALAR = 40
 POLICY_PACKED = 2 * 128 * 256      # USIM_POLICY_PACKED
 POLICY_SCRATCH = 1280              # USIM_POLICY_SCRATCH
-POLICY_FUSED_ROW = 48              # doubles per row of usim_policy_fused.work_dev (one row of partial sums per 32 environments)
+POLICY_MAX_MEMBERS = 65535         # USIM_POLICY_MAX_MEMBERS: members of a policy population (a grid axis)
+POLICY_FUSED_ROW = 48             # doubles per row of usim_policy_fused.work_dev (one row of partial sums per 32 environments)
 PPO_STATS = 8                      # USIM_PPO_STATS
 PPO_WORKGROUPS = 128               # USIM_PPO_WORKGROUPS: gradient workgroups per network (tiles of 32 minibatch rows at this stride)
 PPO_GATE_WORDS = 4                 # USIM_PPO_GATE_WORDS: stop flag, gradient calls evaluated, optimizer steps applied, 0
@@ -170,6 +171,11 @@ SYMBOLS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_policy_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "usim_policy_pack_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "usim_policy_step_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(UsimNormStats), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(UsimPolicyOut), C.c_void_p]),
+    "usim_policy_reward_multi": (C.c_int, [C.POINTER(UsimNormStats), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     "usim_pack_step": (C.c_int, [C.POINTER(UsimStepIO), C.c_int, C.c_void_p, C.c_void_p]),
     "usim_score_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "usim_monitor_words": (C.c_int, [C.c_int]),

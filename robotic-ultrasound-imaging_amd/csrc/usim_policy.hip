@@ -17,6 +17,8 @@
 //   [usim_step]
 // and, where the caller asks for it, one more small launch per step:
 //   usim_policy_bootstrap   += gamma V(terminal observation) on the rewards of the environments that ended at the time limit (see the kernel)
+// and for K networks over K G environments (population.py) the same workgroups with the member on one more grid axis:
+//   usim_policy_pack_multi / usim_policy_step_multi / usim_policy_reward_multi   K single-network calls on the members' slices in one launch each, bit for bit
 // The weights are read from the caller's tensors (torch parameters: an optimiser step is seen by the next call); nothing is copied.
 // Numerics: same formulas as policy.DeviceVecNormalize / MlpActorCritic; sums are ordered differently from PyTorch's kernels, so results agree to
 // rounding (tests/test_gpu_policy_replay.py: 1e-5 on means / values / log-probs, 1e-12 relative on the float64 statistics), not bit for bit.
@@ -154,7 +156,7 @@ DI float tanh_(float x) { const float e = __builtin_amdgcn_exp2f(x * 2.885390081
 // float16 matrix-core products per tile -- hi hi + hi lo + lo hi, float32 accumulate, 2^-22 relative per product against 2^-24 -- at 8 cycles per 16 x 16 x 16
 // instead of four float32 instructions of 32 cycles each: 3.7 us of the launch become 0.8.
 DI int pl_packed_index(int net, int wave, int tile, int s, int lane) { return (((net * 4 + wave) * 2 + tile) * (PL_H1 / 16) + s) * 64 + lane; }
-__global__ __launch_bounds__(256) void usim_policy_pack_kernel(const float* __restrict__ pi_w2, const float* __restrict__ vf_w2, float4* __restrict__ packed) {
+DI void pack_body(const float* __restrict__ pi_w2, const float* __restrict__ vf_w2, float4* __restrict__ packed) {
     const int idx = blockIdx.x * 256 + threadIdx.x;                    // one float4 per thread: 2 * 4 * 2 * 16 * 64 = 16384
     if (idx >= 2 * 4 * 2 * (PL_H1 / 16) * 64) return;
     const int lane = idx & 63, s = (idx >> 6) & 15, tile = (idx >> 10) & 1, wave = (idx >> 11) & 3, net = idx >> 13;
@@ -165,6 +167,9 @@ __global__ __launch_bounds__(256) void usim_policy_pack_kernel(const float* __re
     split_h(w.x, a, b); u.h.hi[0] = a; u.h.lo[0] = b; split_h(w.y, a, b); u.h.hi[1] = a; u.h.lo[1] = b;
     split_h(w.z, a, b); u.h.hi[2] = a; u.h.lo[2] = b; split_h(w.w, a, b); u.h.hi[3] = a; u.h.lo[3] = b;
     packed[idx] = u.f;
+}
+__global__ __launch_bounds__(256) void usim_policy_pack_kernel(const float* __restrict__ pi_w2, const float* __restrict__ vf_w2, float4* __restrict__ packed) {
+    pack_body(pi_w2, vf_w2, packed);
 }
 
 constexpr int PL_ROW = 48, PL_SG = 13;                          // doubles per workspace row (38 observation moments, 3 reward moments); segments of the final sum
@@ -180,13 +185,16 @@ static_assert(sizeof(FusedTab) <= PL_TM * PL_H2S * sizeof(float), "partial sums 
 
 // Diagnostics (never in the shipped library): -DUSIM_POLICY_CUT=1 / 2 / 3 ends the kernel before layer 1 / before layer 2 / before the heads, -DUSIM_POLICY_NOLOAD replaces the
 // layer-2 weight reads by constants -- the kernel's time by phase under rocprofv3.
+// The workgroup's work is a device function: the single-network kernels below call it with their arguments as they are, the population kernel
+// (usim_policy_act_multi_kernel) with the pointers of the member its blockIdx.z names.  It reads blockIdx.x (the 32 environments), blockIdx.y (the network)
+// and, FUSED only, gridDim.x; everything else comes through its arguments.
 template <bool FUSED>
-__global__ __launch_bounds__(256, 2) void usim_policy_act_kernel(PolicyNet P, NormStats S, const float* __restrict__ obs,
-                                                              const uint8_t* __restrict__ prev_done, int n, int adim, const float* __restrict__ act_low,
-                                                              const float* __restrict__ act_high, uint32_t key0, uint32_t key1, uint32_t ctr0, const uint32_t* __restrict__ ctr_base, int env_offset,
-                                                              int deterministic, float* __restrict__ nobs_out, float* __restrict__ act_out,
-                                                              float* __restrict__ act_env, float* __restrict__ value_out, float* __restrict__ logp_out,
-                                                              float* __restrict__ start_out, FusedArgs F) {
+DI void policy_act_body(PolicyNet P, NormStats S, const float* __restrict__ obs,
+                        const uint8_t* __restrict__ prev_done, int n, int adim, const float* __restrict__ act_low,
+                        const float* __restrict__ act_high, uint32_t key0, uint32_t key1, uint32_t ctr0, const uint32_t* __restrict__ ctr_base, int env_offset,
+                        int deterministic, float* __restrict__ nobs_out, float* __restrict__ act_out,
+                        float* __restrict__ act_env, float* __restrict__ value_out, float* __restrict__ logp_out,
+                        float* __restrict__ start_out, FusedArgs F) {
     __shared__ FusedLds FL;
     __shared__ __attribute__((aligned(16))) float xs[PL_TM][PL_KPAD];
     __shared__ __attribute__((aligned(16))) _Float16 h1h[PL_TM][PL_H1 + 8], h1l[PL_TM][PL_H1 + 8];      // layer-1 activations, split (split_h); row stride 528 bytes
@@ -491,6 +499,64 @@ __global__ __launch_bounds__(256, 2) void usim_policy_act_kernel(PolicyNet P, No
         if (env < n && o == 0 && value_out) value_out[env] = acc + ph[0];
     }
 }
+template <bool FUSED>
+__global__ __launch_bounds__(256, 2) void usim_policy_act_kernel(PolicyNet P, NormStats S, const float* __restrict__ obs,
+                                                              const uint8_t* __restrict__ prev_done, int n, int adim, const float* __restrict__ act_low,
+                                                              const float* __restrict__ act_high, uint32_t key0, uint32_t key1, uint32_t ctr0, const uint32_t* __restrict__ ctr_base, int env_offset,
+                                                              int deterministic, float* __restrict__ nobs_out, float* __restrict__ act_out,
+                                                              float* __restrict__ act_env, float* __restrict__ value_out, float* __restrict__ logp_out,
+                                                              float* __restrict__ start_out, FusedArgs F) {
+    policy_act_body<FUSED>(P, S, obs, prev_done, n, adim, act_low, act_high, key0, key1, ctr0, ctr_base, env_offset, deterministic, nobs_out, act_out, act_env, value_out,
+                           logp_out, start_out, F);
+}
+
+// ---- policy populations: K networks over n = K G environments, member k owning environments [k G, (k + 1) G).  The unit of work above is already 32 environments x
+//      one network, and a workgroup reads its weights once whichever network they are: the member is one more grid axis (blockIdx.z for the policy launch, blockIdx.y
+//      for the statistics and reward launches), and a workgroup forms its member's pointers from the bases -- scalar additions, uniform over the workgroup -- and runs the
+//      single-network body on them with n = G.  A member's last workgroup therefore handles its tail as the single-network launch handles n % 32, and a call computes
+//      the bits of K single-network calls on the slices (tests/test_gpu_population_kernels.py). ----
+// the flat parameter block of include/usim.h (usim_ppo_params: the field order of usim_policy_net) as a PolicyNet
+DI PolicyNet member_net(const float* t, int adim, const float4* packed) {
+    PolicyNet P;
+    P.pi_w1 = t; t += PL_H1 * PL_OBS; P.pi_b1 = t; t += PL_H1; P.pi_w2 = t; t += PL_H2 * PL_H1; P.pi_b2 = t; t += PL_H2;
+    P.act_w = t; t += adim * PL_H2; P.act_b = t; t += adim;
+    P.vf_w1 = t; t += PL_H1 * PL_OBS; P.vf_b1 = t; t += PL_H1; P.vf_w2 = t; t += PL_H2 * PL_H1; P.vf_b2 = t; t += PL_H2;
+    P.val_w = t; t += PL_H2; P.val_b = t; t += 1; P.log_std = t;
+    P.w2_packed = packed;
+    return P;
+}
+// the statistics of member k out of K-major ones: [K][19] moments, [K] counts and return moments, returns [K G]; the four constants are shared
+DI NormStats member_stats(NormStats S, int k, int G) {
+    S.obs_mean += k * PL_OBS; S.obs_var += k * PL_OBS; S.obs_count += k;
+    S.ret_mean += k; S.ret_var += k; S.ret_count += k;
+    if (S.returns) S.returns += (size_t)k * G;
+    return S;
+}
+template <class T> DI T* member_rows(T* p, int k, int G, int width) { return p ? p + (size_t)k * G * width : nullptr; }     // rows [k G, (k + 1) G) of a [K G][width] buffer (NULL stays NULL)
+
+constexpr int PL_PACKED4 = 2 * 4 * 2 * (PL_H1 / 16) * 64;            // float4 words of one network pair's packed layer-2 weights (USIM_POLICY_PACKED / 4)
+__global__ __launch_bounds__(256) void usim_policy_pack_multi_kernel(const float* __restrict__ theta, int stride, int adim, float4* __restrict__ packed) {
+    const PolicyNet P = member_net(theta + (size_t)blockIdx.y * stride, adim, nullptr);
+    pack_body(P.pi_w2, P.vf_w2, packed + (size_t)blockIdx.y * PL_PACKED4);
+}
+__global__ __launch_bounds__(PL_ST) void usim_policy_obs_stats_multi_kernel(const float* __restrict__ obs, int G, NormStats S, double* __restrict__ scratch) {
+    __shared__ ObsStatsLds L;
+    const int k = blockIdx.y;
+    double* part = scratch + (size_t)k * USIM_POLICY_SCRATCH;
+    obs_stats_body(L, member_rows(obs, k, G, PL_OBS), G, member_stats(S, k, G), part, reinterpret_cast<unsigned int*>(part + PL_SB * PL_OBS * 2));
+}
+__global__ __launch_bounds__(256, 2) void usim_policy_act_multi_kernel(const float* __restrict__ theta, int stride, const float4* __restrict__ packed, NormStats S,
+                                                                    const float* __restrict__ obs, const uint8_t* __restrict__ prev_done, int G, int adim,
+                                                                    const float* __restrict__ act_low, const float* __restrict__ act_high, uint32_t key0, uint32_t key1,
+                                                                    uint32_t ctr0, const uint32_t* __restrict__ ctr_base, int env_offset, int deterministic,
+                                                                    float* __restrict__ nobs_out, float* __restrict__ act_out, float* __restrict__ act_env,
+                                                                    float* __restrict__ value_out, float* __restrict__ logp_out, float* __restrict__ start_out) {
+    const int k = blockIdx.z;
+    const PolicyNet P = member_net(theta + (size_t)k * stride, adim, packed + (size_t)k * PL_PACKED4);
+    policy_act_body<false>(P, member_stats(S, k, G), member_rows(obs, k, G, PL_OBS), member_rows(prev_done, k, G, 1), G, adim, act_low, act_high, key0, key1, ctr0, ctr_base,
+                           env_offset + k * G, deterministic, member_rows(nobs_out, k, G, PL_OBS), member_rows(act_out, k, G, adim), member_rows(act_env, k, G, adim),
+                           member_rows(value_out, k, G, 1), member_rows(logp_out, k, G, 1), member_rows(start_out, k, G, 1), FusedArgs{});
+}
 
 // VecNormalize.step_wait after the env step: returns = gamma returns + reward; RunningMeanStd.update(returns); normalised, clipped reward; returns
 // reset where an episode ended.  One workgroup, one pass over the batch (sum r, sum r^2, sum of the raw rewards reduced together).
@@ -537,6 +603,20 @@ __global__ __launch_bounds__(1024) void usim_policy_post_kernel(const float* __r
     __shared__ union { ObsStatsLds a; RewardLds b; } L;
     if (blockIdx.x < PL_SB) obs_stats_body(L.a, next_obs, n, S, part, arrived);
     else reward_body(L.b, rew, done, n, S, training, norm_reward, nrew_out, raw_sum);
+}
+// The population's reward launch, with the member on blockIdx.y.  with_obs: the grid of usim_policy_post_kernel per member (PL_SB statistics workgroups, then the
+// reward workgroup); without: one reward workgroup per member, as usim_policy_reward_kernel.  raw_sum [K] (or NULL).
+__global__ __launch_bounds__(1024) void usim_policy_post_multi_kernel(const float* __restrict__ rew, const uint8_t* __restrict__ done, int G, NormStats S, int training,
+                                                                      int norm_reward, float* __restrict__ nrew_out, double* __restrict__ raw_sum,
+                                                                      const float* __restrict__ next_obs, double* __restrict__ scratch, int with_obs) {
+    __shared__ union { ObsStatsLds a; RewardLds b; } L;
+    const int k = blockIdx.y;
+    const NormStats M = member_stats(S, k, G);
+    if (with_obs && blockIdx.x < PL_SB) {
+        double* part = scratch + (size_t)k * USIM_POLICY_SCRATCH;
+        obs_stats_body(L.a, member_rows(next_obs, k, G, PL_OBS), G, M, part, reinterpret_cast<unsigned int*>(part + PL_SB * PL_OBS * 2));
+    } else
+        reward_body(L.b, member_rows(rew, k, G, 1), member_rows(done, k, G, 1), G, M, training, norm_reward, member_rows(nrew_out, k, G, 1), raw_sum ? raw_sum + k : nullptr);
 }
 
 // RolloutBuffer.compute_returns_and_advantage: one thread per environment walks its column of the [T][n] buffers backwards
@@ -737,6 +817,49 @@ int usim_policy_reward(const usim_norm_stats* st, const float* rew_dev, const ui
                            next_obs_dev, st->scratch, reinterpret_cast<unsigned int*>(st->scratch + PL_SB * PL_OBS * 2));
     } else
     hipLaunchKernelGGL(usim_policy_reward_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, rew_dev, done_dev, n, S, training, norm_reward, nrew_dev, raw_sum_dev);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+// ---- populations (the contracts are include/usim.h's): every argument is checked before the first launch ----
+static bool members_ok(int members, int envs_per_member) {            // K, G >= 1, K G within int, K within a grid axis
+    return members > 0 && envs_per_member > 0 && (int64_t)members * envs_per_member <= INT32_MAX && members <= USIM_POLICY_MAX_MEMBERS;
+}
+static bool theta_ok(const float* theta_dev, int stride, int act_dim) {
+    return theta_dev && act_dim >= 1 && act_dim <= 8 && stride >= usim_ppo_params(act_dim) && stride % 4 == 0;
+}
+
+int usim_policy_pack_multi(const float* theta_dev, int stride, int members, int act_dim, float* packed_dev, void* stream) {
+    if (!theta_ok(theta_dev, stride, act_dim) || !members_ok(members, 1) || !packed_dev || (reinterpret_cast<uintptr_t>(packed_dev) & 15)) return USIM_ERR_INVALID;
+    hipLaunchKernelGGL(usim_policy_pack_multi_kernel, dim3(USIM_POLICY_PACKED / 4 / 256, members), dim3(256), 0, (hipStream_t)stream, theta_dev, stride, act_dim,
+                       reinterpret_cast<float4*>(packed_dev));
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+int usim_policy_step_multi(const float* theta_dev, int stride, const float* packed_dev, const usim_norm_stats* st, const float* obs_dev, const uint8_t* prev_done_dev,
+                           int members, int envs_per_member, int act_dim, const float* act_low_dev, const float* act_high_dev, uint64_t seed, uint32_t counter,
+                           const uint32_t* counter_base_dev, int env_offset, int training, int deterministic, const usim_policy_out* out, void* stream) {
+    if (!theta_ok(theta_dev, stride, act_dim) || !members_ok(members, envs_per_member) || !packed_dev || (reinterpret_cast<uintptr_t>(packed_dev) & 15)) return USIM_ERR_INVALID;
+    if (!st || !st->obs_mean || !st->obs_var || !obs_dev || !act_low_dev || !act_high_dev || !out || !out->act_env_dev) return USIM_ERR_INVALID;
+    const NormStats S = norm_stats(*st);
+    const int G = envs_per_member;
+    if (training == 1) {
+        if (!st->scratch || !st->obs_count) return USIM_ERR_INVALID;
+        hipLaunchKernelGGL(usim_policy_obs_stats_multi_kernel, dim3(PL_SB, members), dim3(PL_ST), 0, (hipStream_t)stream, obs_dev, G, S, st->scratch);
+    }
+    hipLaunchKernelGGL(usim_policy_act_multi_kernel, dim3((G + PL_TM - 1) / PL_TM, 2, members), dim3(256), 0, (hipStream_t)stream, theta_dev, stride,
+                       reinterpret_cast<const float4*>(packed_dev), S, obs_dev, prev_done_dev, G, act_dim, act_low_dev, act_high_dev, (uint32_t)seed, (uint32_t)(seed >> 32), counter,
+                       counter_base_dev, env_offset, deterministic, out->nobs_dev, out->act_dev, out->act_env_dev, out->value_dev, out->logp_dev, out->episode_start_dev);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+int usim_policy_reward_multi(const usim_norm_stats* st, const float* rew_dev, const uint8_t* done_dev, int members, int envs_per_member, int training, int norm_reward,
+                             float* nrew_dev, double* raw_sum_dev, const float* next_obs_dev, void* stream) {
+    if (!st || !rew_dev || !done_dev || !nrew_dev || !members_ok(members, envs_per_member)) return USIM_ERR_INVALID;
+    if (!st->ret_var || (training && (!st->ret_mean || !st->ret_count || !st->returns))) return USIM_ERR_INVALID;
+    const int with_obs = next_obs_dev && training;
+    if (with_obs && (!st->scratch || !st->obs_mean || !st->obs_var || !st->obs_count)) return USIM_ERR_INVALID;
+    hipLaunchKernelGGL(usim_policy_post_multi_kernel, dim3(with_obs ? PL_SB + 1 : 1, members), dim3(1024), 0, (hipStream_t)stream, rew_dev, done_dev, envs_per_member,
+                       norm_stats(*st), training, norm_reward, nrew_dev, raw_sum_dev, next_obs_dev, st->scratch, with_obs);
     return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
 }
 

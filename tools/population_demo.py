@@ -1,0 +1,117 @@
+#!/usr/bin/env python
+"""Policy populations at work (population.py).  Two uses:
+
+  python tools/population_demo.py rank FOLDER [--envs-per-member 64] [--episodes 10]
+      every NAME.zip in FOLDER that has its vec_normalize_NAME.pkl beside it -- the checkpoints a training run leaves behind (src/rl.py:133, forty per run) -- becomes
+      one member; evaluate_population plays `--episodes` deterministic episodes per member in ONE run and the ranking by mean return is printed
+
+  python tools/population_demo.py train [--members 4] [--envs-per-member 4096] [--steps 128] [--iterations 10] [--sequential] [--save FOLDER]
+      K seeds of `tracking` trained side by side (PopulationRollout + PopulationPPO, SB3's initialisation per member); every iteration prints each member's raw reward
+      per step and rollout/ep_rew_mean.  --sequential: the same K runs one after the other (policy.FusedRollout(fused_stats=False) + ppo.NativePPO on shard
+      environments: the runs the population equals bit for bit) -- the wall time to compare with"""
+import argparse
+import importlib
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+usim = importlib.import_module("robotic-ultrasound-imaging_amd")
+P, M = usim.policy, usim.population
+DEV = "cuda:0"
+
+
+def sb3_init(policy):
+    for m in policy.modules():                                      # SB3: orthogonal init, gain sqrt(2) (0.01 for the action head, 1 for the value head)
+        if isinstance(m, torch.nn.Linear):
+            torch.nn.init.orthogonal_(m.weight, gain=2 ** 0.5); torch.nn.init.zeros_(m.bias)
+    torch.nn.init.orthogonal_(policy.action_net.weight, gain=0.01); torch.nn.init.orthogonal_(policy.value_net.weight, gain=1.0)
+    return policy
+
+
+def rank(a):
+    folder = Path(a.folder)
+    names = [z.stem for z in sorted(folder.glob("*.zip")) if (folder / f"vec_normalize_{z.stem}.pkl").exists()]
+    if not names:
+        sys.exit(f"no NAME.zip with a vec_normalize_NAME.pkl in {folder}")
+    K, G = len(names), a.envs_per_member
+    pop = M.PolicyPopulation.from_checkpoints([folder / f"{n}.zip" for n in names], device=DEV)
+    first = P.load_vecnormalize_pkl(folder / f"vec_normalize_{names[0]}.pkl")
+    vn = M.PopulationVecNormalize(K, G, device=DEV, training=False, norm_reward=False, **{k: first[k] for k in ("clip_obs", "clip_reward", "gamma", "epsilon")})
+    for k, n in enumerate(names):
+        vn.load_member(k, folder / f"vec_normalize_{n}.pkl")
+    env = usim.UltrasoundVecEnv(K * G, device=DEV, seed=3, **usim.default_robosuite_kwargs())
+    torch.cuda.synchronize(); t0 = time.time()
+    res = M.evaluate_population(env, pop, vn, n_eval_episodes=a.episodes)
+    dt = time.time() - t0
+    print(f"{K} checkpoints x {a.episodes} episodes on {K} x {G} environments in one run: {dt:.2f} s")
+    for place, k in enumerate(sorted(range(K), key=lambda k: -res[k][0])):
+        print(f"{place + 1:3d}. {names[k]:40s} mean return {res[k][0]:10.3f}  std {res[k][1]:8.3f}")
+    env.close()
+
+
+def train(a):
+    K, G, T = a.members, a.envs_per_member, a.steps
+    kw = usim.default_robosuite_kwargs()
+    torch.manual_seed(0)
+    src = [sb3_init(P.MlpActorCritic(19, 6)) for _ in range(K)]
+    if not a.sequential:
+        env = usim.UltrasoundVecEnv(K * G, device=DEV, seed=3, **kw)
+        pop = M.PolicyPopulation.from_policies(src, device=DEV)
+        vn = M.PopulationVecNormalize(K, G, device=DEV)
+        buf = P.DeviceRolloutBuffer(T, K * G, 19, env.action_dim, device=DEV)
+        env.attach_monitor(usim.DeviceMonitor(env, window=100 * K))           # before the collector is built; the ring is shared by the members
+        coll = M.PopulationRollout(env, pop, vn, buf, seed=0)
+        ppo = M.PopulationPPO(env, pop, vn, buf, coll, seeds=list(range(K)), n_epochs=4)
+        torch.cuda.synchronize(); t0 = time.time()
+        for it in range(a.iterations):
+            ppo.learn(1)
+            raw = (coll.raw_reward_sum / (T * G)).tolist()
+            print(f"iter {it:3d}  " + "  ".join(f"[{k}] r/step {raw[k]:6.3f} ep_rew {ppo.history[k][-1]['rollout/ep_rew_mean']:8.2f}" for k in range(K)), flush=True)
+        torch.cuda.synchronize()
+        print(f"population: {K} members x {G} environments x {T} steps x {a.iterations} iterations in {time.time() - t0:.2f} s (wall, set-up and capture excluded)")
+        if a.save:
+            for z, p in ppo.save_checkpoint(a.save, [f"seed_{k}" for k in range(K)]):
+                print("wrote", z, p)
+        env.close()
+        return
+    total = 0.0
+    for k in range(K):
+        env = usim.UltrasoundVecEnv(G, device=DEV, seed=3, env_offset=k * G, **kw)
+        policy = src[k].to(DEV)
+        usim.ppo.flatten_parameters(policy)
+        vn = P.DeviceVecNormalize(G, device=DEV)
+        buf = P.DeviceRolloutBuffer(T, G, 19, env.action_dim, device=DEV)
+        env.attach_monitor(usim.DeviceMonitor(env))
+        coll = P.FusedRollout(env, policy, vn, buf, seed=0, fused_stats=False)
+        ppo = usim.ppo.NativePPO(env, policy, vn, buf, coll, seed=k, n_epochs=4)
+        torch.cuda.synchronize(); t0 = time.time()
+        ppo.learn(a.iterations)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        total += dt
+        print(f"run {k}: {G} environments x {T} steps x {a.iterations} iterations in {dt:.2f} s; r/step {float(coll.raw_reward_sum) / (T * G):6.3f} "
+              f"ep_rew {ppo.history[-1]['rollout/ep_rew_mean']:8.2f}", flush=True)
+        env.close()
+    print(f"sequential: {K} runs in {total:.2f} s (wall, set-up and capture excluded)")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    r = sub.add_parser("rank")
+    r.add_argument("folder"); r.add_argument("--envs-per-member", type=int, default=64); r.add_argument("--episodes", type=int, default=10)
+    t = sub.add_parser("train")
+    t.add_argument("--members", type=int, default=4); t.add_argument("--envs-per-member", type=int, default=4096); t.add_argument("--steps", type=int, default=128)
+    t.add_argument("--iterations", type=int, default=10); t.add_argument("--sequential", action="store_true"); t.add_argument("--save", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("population_demo.py needs a GPU; the simulator has no CPU fallback")
+    (rank if a.cmd == "rank" else train)(a)
+
+
+if __name__ == "__main__":
+    main()

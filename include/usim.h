@@ -709,6 +709,53 @@ int usim_ppo_adam(float* theta_dev, const float* grad_dev, float* m_dev, float* 
 int usim_ppo_adam_gated(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int params,
                         float lr, float beta1, float beta2, float eps, float max_grad_norm, float* stats_dev, int32_t* gate_dev, void* stream);
 
+/* ---- population learners: K PPO minibatch steps in one gradient call and one Adam call (population.py PopulationPPO(concurrent=True)).
+ * The member is one more grid axis of the learner's kernels, as in usim_policy_step_multi, in the same K-major layout: theta_dev, grad_dev, m_dev, v_dev
+ * [K][stride] (stride >= P = usim_ppo_params(A) and a multiple of 4; the first P words of row k are member k's flat block, words behind P are never touched),
+ * step_dev [K], stats_dev [K][USIM_PPO_STATS], gate_dev [K][USIM_PPO_GATE_WORDS] or NULL.  Both calls are launches on `stream` and nothing else (no allocation, no
+ * synchronisation, no host read of device memory): a pair is capturable as one chain.
+ *
+ * THE CONTRACT: member k's words of grad_dev, stats_dev, theta_dev, m_dev, v_dev, step_dev and gate_dev after the calls are, bit for bit, what usim_ppo_grad /
+ * usim_ppo_adam_gated write for that member alone -- its row of theta, its rows of the data, its index list, its hyper-parameters, its gate.  A member reads and
+ * writes its own rows only: a NaN in one member's weights or data does not reach another's; a member whose stop flag is set is skipped (its workgroups return on
+ * entry) while the others go on.
+ *
+ * usim_ppo_batch_multi: the data pointers of usim_ppo_batch over members x rows rows, member k owning rows [k rows, (k + 1) rows); index_dev [K][index_stride]
+ * int32, each relative to the member's own rows and clamped to them as usim_ppo_grad clamps (NULL: rows 0 .. batch - 1 of every member); rows, batch, act_dim and
+ * normalize_advantage are one value for all members.  hyper_dev [K][USIM_PPO_HYPER_WORDS] float32 -- lr, clip_range, ent_coef, vf_coef, max_grad_norm,
+ * clip_range_vf, target_kl, 0 -- is written by the host once per update, not per minibatch: a sweep over any of them is one launch.  The table lives on the
+ * device and is not checked: a non-finite or negative entry is the caller's error, and what it does stays inside its member.  Value clipping is an instance of
+ * the gradient kernel, so it is on for all members or for none: value_clip != 0 reads clip_range_vf (> 0) per member from the table and needs old_value_dev;
+ * value_clip == 0 ignores that column.  target_kl (<= 0: off) takes effect only with a gate_dev.
+ *
+ * usim_ppo_grad_multi: prep, grid (65, K); grad, grid (nb, 2, K) with nb = min(USIM_PPO_WORKGROUPS, ceil(batch / 32)) -- the lone decomposition without the
+ * workgroups that have no tile, which a lone call has write zeros; reduce and finish add blocks / rows 0 .. nb - 1 in order (adding the lone call's further +0
+ * blocks to a sum that started from +0 changes no bit).  usim_ppo_adam_multi: count (one thread per member), adam, grid (ceil(params / 1024), K); lr and
+ * max_grad_norm (<= 0: no clipping) come from the table; stats_dev may be NULL, otherwise slot 6 of each row receives the norm used.
+ * work_dev: usim_ppo_work_floats_multi(A, K, batch) floats on the 16-byte grid, K regions of equal size (a multiple of 4 floats, so every region starts on the
+ * 16-byte grid), each: nb partial blocks | the four packed layer-2 matrices | nb rows of 8 float64 loss sums | the two advantage words.  The regions' size
+ * follows the call's own nb and the call rewrites every word it reads: a workspace sized for the largest batch serves every smaller one (an epoch's trailing
+ * partial minibatch), and no clearing between calls is needed.
+ * USIM_ERR_INVALID before anything is enqueued: what usim_ppo_grad / usim_ppo_adam refuse (NULL required pointers, act_dim outside 1 .. 8, batch < 1, rows < 1,
+ * rows < batch without an index list, eps negative or non-finite, a beta outside [0, 1), params < 1), members outside 1 .. USIM_POLICY_MAX_MEMBERS, stride < P
+ * (usim_ppo_adam_multi: < params) or not a multiple of 4, members x rows beyond INT_MAX, index_stride < batch with an index list, a NULL hyper_dev, value_clip
+ * with a NULL old_value_dev, work_dev off the 16-byte grid. ---- */
+#define USIM_PPO_HYPER_WORDS 8
+typedef struct usim_ppo_batch_multi {
+    const float *obs_dev, *act_dev, *old_logp_dev, *adv_dev, *ret_dev;  /* [K rows][19], [K rows][A], [K rows] x 3 */
+    const float*   old_value_dev;              /* [K rows]; required iff value_clip */
+    const int32_t* index_dev;                  /* [K][index_stride], or NULL */
+    const float*   hyper_dev;                  /* [K][USIM_PPO_HYPER_WORDS] */
+    int32_t*       gate_dev;                   /* [K][USIM_PPO_GATE_WORDS], or NULL: no gate */
+    int32_t index_stride, rows, batch, act_dim, normalize_advantage, value_clip;
+} usim_ppo_batch_multi;
+int64_t usim_ppo_work_floats_multi(int act_dim, int members, int batch);      /* < 0: error code */
+int usim_ppo_grad_multi(const float* theta_dev, int stride, int members, const usim_ppo_batch_multi* b,
+                        float* work_dev, float* grad_dev, float* stats_dev, void* stream);
+int usim_ppo_adam_multi(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev,
+                        int stride, int members, int params, const float* hyper_dev, float beta1, float beta2, float eps,
+                        float* stats_dev, int32_t* gate_dev, void* stream);
+
 /* ---- behaviour cloning (imitation.py NativeBC, DAggerTrainer): the supervised minibatch loss of the `imitation` package's BC on the same
  * networks, as further instances of usim_ppo_grad's gradient kernel -- the same parameter order, the same workspace (usim_ppo_work_floats; one buffer may serve both
  * calls in turn), the same four launches on `stream` and nothing else, the same fixed order of every sum, the same clamping of an index outside [0, rows).  The

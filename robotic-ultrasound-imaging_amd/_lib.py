@@ -20,7 +20,8 @@ POLICY_FUSED_ROW = 48             # doubles per row of usim_policy_fused.work_de
 PPO_STATS = 8                      # USIM_PPO_STATS
 PPO_WORKGROUPS = 128               # USIM_PPO_WORKGROUPS: gradient workgroups per network (tiles of 32 minibatch rows at this stride)
 PPO_GATE_WORDS = 4                 # USIM_PPO_GATE_WORDS: stop flag, gradient calls evaluated, optimizer steps applied, 0
-BC_NLL, BC_MSE = 0, 1              # USIM_BC_NLL, USIM_BC_MSE: the policy term of usim_bc_grad
+PPO_HYPER_WORDS = 8                # USIM_PPO_HYPER_WORDS: a member's row of usim_ppo_batch_multi.hyper_dev (lr, clip_range, ent_coef, vf_coef, max_grad_norm, clip_range_vf, target_kl, 0)
+BC_NLL, BC_MSE = 0, 1             # USIM_BC_NLL, USIM_BC_MSE: the policy term of usim_bc_grad
 RESET_PARAMS = 13
 LOG_WIDTH = 53
 WARM_WORDS = 8 + 16 * 4            # USIM_WARM_WORDS
@@ -153,6 +154,13 @@ class UsimPpoBatch(C.Structure):
                [(n, C.c_void_p) for n in ("old_value_dev", "gate_dev")] + [(n, C.c_float) for n in ("clip_range_vf", "target_kl")]
 
 
+class UsimPpoBatchMulti(C.Structure):
+    """struct usim_ppo_batch_multi (include/usim.h): usim_ppo_batch for K members -- the data over K x rows rows, the index lists [K][index_stride], the
+    hyper-parameter table [K][PPO_HYPER_WORDS] and the gates [K][PPO_GATE_WORDS]"""
+    _fields_ = [(n, C.c_void_p) for n in ("obs_dev", "act_dev", "old_logp_dev", "adv_dev", "ret_dev", "old_value_dev", "index_dev", "hyper_dev", "gate_dev")] + \
+               [(n, C.c_int32) for n in ("index_stride", "rows", "batch", "act_dim", "normalize_advantage", "value_clip")]
+
+
 class UsimBcBatch(C.Structure):
     """struct usim_bc_batch (include/usim.h): device pointers to normalised observations, expert actions and optional value targets + the minibatch's index list"""
     _fields_ = [(n, C.c_void_p) for n in ("obs_dev", "act_dev", "value_dev", "index_dev")] + \
@@ -204,7 +212,11 @@ SYMBOLS = {
                                 C.c_void_p, C.c_void_p]),
     "usim_ppo_adam_gated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
-    "usim_default_config": (C.c_int, [C.POINTER(UsimConfig)]),
+    "usim_ppo_work_floats_multi": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "usim_ppo_grad_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(UsimPpoBatchMulti), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_ppo_adam_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "usim_default_config":(C.c_int, [C.POINTER(UsimConfig)]),
     "usim_create": (C.c_int, [C.POINTER(UsimConfig), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "usim_destroy": (None, [C.c_void_p]),
     "usim_set_mapping": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -24,6 +24,10 @@
 // same for every thread, in front of every barrier -- and returns when it is set.  Thread 0 of finish counts the call and, last thing, sets the flag from the
 // float32 approx_kl it has just written; the one-thread count kernel counts the step.  Plain stores by single threads of single-workgroup kernels; no atomics.
 //
+// Populations (usim_ppo_grad_multi / usim_ppo_adam_multi; population.py PopulationPPO(concurrent=True)): the same six launches for K members at once, the member
+// being the last grid axis of every kernel and its hyper-parameters a row of a table on the device.  Each population kernel states its member's pointers and runs
+// the body of its lone counterpart, so a member's words are the bits of a lone call; the kernels and the workspace layout stand at the end of the namespace.
+//
 // THE ORDER OF EVERY SUM IS FIXED: a thread adds its rows in ascending order inside a tile and its tiles in ascending order; blocks are added in block order; sums
 // over a workgroup are a butterfly inside the wave and the waves in order (as usim_plan.hip).  No floating-point atomics, nothing ordered by arrival, no dependence
 // on the device's CU count: the same inputs give the same bits on every call.
@@ -95,8 +99,8 @@ DI double wg_sum(double x, double* lds) {
     return s;
 }
 
-__global__ __launch_bounds__(PP_RED) void usim_ppo_prep_kernel(const float* __restrict__ pi_w2, const float* __restrict__ vf_w2, PpoBatch b, float* __restrict__ pack,
-                                                               double* __restrict__ adv_out) {
+// prep's body, shared by the lone kernel and the population's (usim_ppo_prep_multi_kernel), which hands it one member's matrices, batch and workspace
+DI void ppo_prep(const float* __restrict__ pi_w2, const float* __restrict__ vf_w2, const PpoBatch& b, float* __restrict__ pack, double* __restrict__ adv_out) {
     __shared__ double red[PP_RED / 64];
     const int tid = threadIdx.x;
     if (pp_stopped(b.gate)) return;
@@ -132,6 +136,11 @@ __global__ __launch_bounds__(PP_RED) void usim_ppo_prep_kernel(const float* __re
     if (tid == 0) { adv_out[0] = mean; adv_out[1] = inv; }
 }
 
+__global__ __launch_bounds__(PP_RED) void usim_ppo_prep_kernel(const float* __restrict__ pi_w2, const float* __restrict__ vf_w2, PpoBatch b, float* __restrict__ pack,
+                                                               double* __restrict__ adv_out) {
+    ppo_prep(pi_w2, vf_w2, b, pack, adv_out);
+}
+
 // VF: clip_range_vf > 0.  The value clip is compiled into an instance of its own, so that the kernel of a call without it is the one it was before the clip existed
 // (the branch in the shared body changed the register allocation of the whole kernel: profiles/ppo/resource_usage_gate.txt)
 //
@@ -140,301 +149,38 @@ __global__ __launch_bounds__(PP_RED) void usim_ppo_prep_kernel(const float* __re
 // (stage 0) and the heads' loss (stage 3) differ, each behind `if constexpr`, so the PPO instances are compiled from the statements they were compiled from.  A
 // behaviour-cloning call without value targets gives the value network's workgroups no tile: they write zeros.  b.ret carries the value targets (NULL: none), the
 // float64 sums of approx_kl and clip_fraction carry the rows' squared action error and log-prob.
+//
+// The body's statements stand in usim_ppo_grad_body.h, which this kernel and the population's (usim_ppo_grad_multi_kernel, the member being blockIdx.z) include:
+// `N` gives each field's pointer per network (N.w1[net]: PpoNet, or the population's PpoNetRow), `work` is the workspace of the call or of the member, `lay` says
+// where it holds what (PpoLay: the fixed layout of W blocks; PpoMultiLay: nb blocks).  The lone instances are compiled from the statements they were compiled from.
+struct PpoLay {                                                   // the workspace of a lone call
+    DI int64_t pack(int A) const { return ppo_off_pack(A); }
+    DI int64_t sums(int A) const { return ppo_off_sums(A); }
+    DI int64_t adv(int A) const { return ppo_off_adv(A); }
+    DI int blocks() const { return PP_W; }
+};
 template <bool VF, int LOSS = PP_PPO>
 __global__ __launch_bounds__(PP_WG) void usim_ppo_grad_kernel(PpoNet N, PpoBatch b, float* __restrict__ work) {
-    __shared__ __attribute__((aligned(16))) float xs[PP_TM][PP_XS];          // the tile's observations, column 19 zero
-    __shared__ __attribute__((aligned(16))) float h1[PP_TM][PP_H1S];         // layer-1 activations; from the end of stage 6 the layer-1 deltas
-    __shared__ __attribute__((aligned(16))) float h2[PP_TM][PP_H2S];         // layer-2 activations; from stage 5 the layer-2 deltas
-    __shared__ __attribute__((aligned(16))) float whs[PP_MAXA][PP_H2];       // head weights, rows >= O zero
-    __shared__ __attribute__((aligned(16))) float dout[PP_TM][PP_MAXA];      // d loss / d head output, columns >= O zero
-    __shared__ float dls[PP_TM][PP_MAXA], acts[PP_TM][PP_MAXA];             // per-row d loss / d log_std; the tile's actions
-    __shared__ float r_old[PP_TM], r_adv[PP_TM], r_ret[PP_TM], r_oldv[VF ? PP_TM : 1];      // r_oldv: the tile's old values (VF only)
-    __shared__ double red[PP_WG / 64];
-    if (pp_stopped(b.gate)) return;
-    const int tid = threadIdx.x, net = blockIdx.y, A = b.adim, O = net ? 1 : A, B = b.batch;
-    const PpoLayout L = ppo_layout(net, A);
-    const int P = ppo_params(A);
-    const float* __restrict__ W2R = work + ppo_off_pack(A) + net * PP_W2;                 // [128][256]
-    const float* __restrict__ W2T = work + ppo_off_pack(A) + 2 * PP_W2 + net * PP_W2;     // [256][128]
-    const double* adv_stat = reinterpret_cast<const double*>(work + ppo_off_adv(A));
-    const double adv_mean = adv_stat[0], adv_inv = adv_stat[1];
-    const float* __restrict__ W1 = N.w1[net];
-    const float* __restrict__ B1 = N.b1[net];
-    const float* __restrict__ B2 = N.b2[net];
-    for (int t = tid; t < PP_MAXA * PP_H2; t += PP_WG) whs[t / PP_H2][t % PP_H2] = (t / PP_H2 < O) ? N.wh[net][t] : 0.f;
-
-    // this thread's places in the five products
-    const int j1 = tid & 255, half = tid >> 8;                   // layer 1 and dW1: feature j1; rows 16 half .. (forward), inputs 10 half .. (dW1)
-    const int cq = tid & 31, rg2 = tid >> 5;                     // layer 2: outputs 4 cq .. + 3 of rows 2 rg2, 2 rg2 + 1
-    const int hk = tid & 127, hq = tid >> 7;                     // head gradient: input hk, outputs hq and hq + 4; layer-2 delta: column hk, rows 8 hq .. + 7
-    const int cg = tid & 15, kg = tid >> 4;                      // dW2: outputs 8 cg .. + 7 x inputs 8 kg .. + 7
-    const int kq = tid & 63, rg4 = tid >> 6;                     // d h1: inputs 4 kq .. + 3 of rows 4 rg4 .. + 3
-    float aw2[8][8], aw1[10], awh0 = 0.f, awh1 = 0.f, ab1 = 0.f, ab2 = 0.f, asmall = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) aw2[i][j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) aw1[i] = 0.f;
-    double s_pl = 0.0, s_kl = 0.0, s_cf = 0.0, s_vl = 0.0;        // loss sums of the rows this thread speaks for (tid < 256, tid % 8 == 0)
-
-    const int ntiles = (LOSS != PP_PPO && net == 1 && !b.ret) ? 0 : (B + PP_TM - 1) / PP_TM;
-    for (int tile = blockIdx.x; tile < ntiles; tile += PP_W) {
-        const int row0 = tile * PP_TM;
-        // ---- stage 0: the tile's samples (rows past the batch: zeros, and no gradient below) ----
-        for (int t = tid; t < PP_TM * PP_XS; t += PP_WG) {
-            const int r = t / PP_XS, i = t - r * PP_XS;
-            xs[r][i] = (i < PP_OBS && row0 + r < B) ? b.obs[pp_row(b, row0 + r) * PP_OBS + i] : 0.f;
-        }
-        if (tid < 256) {
-            const int r = tid >> 3, a = tid & 7;
-            acts[r][a] = (a < A && row0 + r < B) ? b.act[pp_row(b, row0 + r) * A + a] : 0.f;
-        } else if (tid < 256 + PP_TM) {
-            const int r = tid - 256;
-            const bool valid = row0 + r < B;
-            const size_t src = valid ? pp_row(b, row0 + r) : 0;
-            if constexpr (LOSS == PP_PPO) {
-                r_old[r] = valid ? b.old_logp[src] : 0.f;
-                r_adv[r] = valid ? (float)(((double)b.adv[src] - adv_mean) * adv_inv) : 0.f;
-                r_ret[r] = valid ? b.ret[src] : 0.f;
-                if constexpr (VF) r_oldv[r] = valid ? b.oldv[src] : 0.f;
-            } else {
-                r_ret[r] = (valid && b.ret) ? b.ret[src] : 0.f;   // the value target (read by the value network's workgroups only)
-            }
-        }
-        __syncthreads();
-        // ---- stage 1: layer 1 (19 -> 256, tanh) ----
-        {
-            float wv[PP_OBS];
-#pragma unroll
-            for (int i = 0; i < PP_OBS; ++i) wv[i] = W1[j1 * PP_OBS + i];
-            const float bj = B1[j1];
-#pragma unroll 4
-            for (int rr = 0; rr < 16; ++rr) {
-                const int r = 16 * half + rr;
-                float acc = bj;
-#pragma unroll
-                for (int i = 0; i < PP_OBS; ++i) acc = fmaf(xs[r][i], wv[i], acc);
-                h1[r][j1] = pp_tanh(acc);
-            }
-        }
-        __syncthreads();
-        // ---- stage 2: layer 2 (256 -> 128, tanh): 2 rows x 4 outputs per thread, the transposed copy read along its rows ----
-        {
-            const int r0 = 2 * rg2, c0 = 4 * cq;
-            float a0[4], a1[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a0[j] = a1[j] = B2[c0 + j];
-#pragma unroll 2
-            for (int k = 0; k < PP_H1; k += 4) {
-                const float4 ha = *reinterpret_cast<const float4*>(&h1[r0][k]), hb = *reinterpret_cast<const float4*>(&h1[r0 + 1][k]);
-                const float xa[4] = {ha.x, ha.y, ha.z, ha.w}, xb[4] = {hb.x, hb.y, hb.z, hb.w};
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const float4 w = *reinterpret_cast<const float4*>(&W2T[(k + s) * PP_H2 + c0]);
-                    a0[0] = fmaf(xa[s], w.x, a0[0]); a0[1] = fmaf(xa[s], w.y, a0[1]); a0[2] = fmaf(xa[s], w.z, a0[2]); a0[3] = fmaf(xa[s], w.w, a0[3]);
-                    a1[0] = fmaf(xb[s], w.x, a1[0]); a1[1] = fmaf(xb[s], w.y, a1[1]); a1[2] = fmaf(xb[s], w.z, a1[2]); a1[3] = fmaf(xb[s], w.w, a1[3]);
-                }
-            }
-            *reinterpret_cast<float4*>(&h2[r0][c0]) = make_float4(pp_tanh(a0[0]), pp_tanh(a0[1]), pp_tanh(a0[2]), pp_tanh(a0[3]));
-            *reinterpret_cast<float4*>(&h2[r0 + 1][c0]) = make_float4(pp_tanh(a1[0]), pp_tanh(a1[1]), pp_tanh(a1[2]), pp_tanh(a1[3]));
-        }
-        __syncthreads();
-        // ---- stage 3: heads and the loss: eight lanes per row, lane a < O forms output a (waves 0 .. 3, whole) ----
-        if (tid < 256) {
-            const int r = tid >> 3, a = tid & 7;
-            const bool valid = row0 + r < B;
-            float out = 0.f;
-            if (a < O) {
-                out = N.bh[net][a];
-#pragma unroll 8
-                for (int k = 0; k < PP_H2; k += 4) {
-                    const float4 h = *reinterpret_cast<const float4*>(&h2[r][k]);
-                    const float4 w = *reinterpret_cast<const float4*>(&whs[a][k]);
-                    out = fmaf(h.x, w.x, out); out = fmaf(h.y, w.y, out); out = fmaf(h.z, w.z, out); out = fmaf(h.w, w.w, out);
-                }
-            }
-            if constexpr (LOSS != PP_PPO) {
-                if (net == 0) {
-                    // behaviour cloning: d = act - mean; log-prob as below; the row's squared action error sum_a d^2.  d loss / d log-prob = -1 / batch
-                    // (PP_BC_NLL: the gradient reaches the mean, y / sigma, and log_std, y^2 - 1); d loss / d mean = -2 d / batch (PP_BC_MSE: the mean only)
-                    const bool is_act = a < A;
-                    const float ls = is_act ? N.log_std[a] : 0.f, inv_s = expf(-ls);
-                    const float d = acts[r][a] - out, y = d * inv_s;
-                    float lp = is_act ? fmaf(-0.5f * y, y, -ls - LOG_SQRT_2PI_F) : 0.f;
-                    float sq = is_act ? d * d : 0.f;
-                    lp += __shfl_xor(lp, 1); lp += __shfl_xor(lp, 2); lp += __shfl_xor(lp, 4);
-                    sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4);
-                    if constexpr (LOSS == PP_BC_NLL) {
-                        const float g = valid ? -b.inv_b : 0.f;
-                        dout[r][a] = is_act ? (g * y) * inv_s : 0.f;
-                        dls[r][a] = is_act ? g * fmaf(y, y, -1.f) : 0.f;
-                    } else {
-                        dout[r][a] = (is_act && valid) ? (-2.f * b.inv_b) * d : 0.f;
-                        dls[r][a] = 0.f;
-                    }
-                    if (a == 0 && valid) {
-                        s_pl += LOSS == PP_BC_NLL ? -(double)lp : (double)sq;
-                        s_kl += (double)sq;
-                        s_cf += (double)lp;
-                    }
-                } else {
-                    const float d = out - r_ret[r];
-                    dout[r][a] = (a == 0 && valid) ? b.vf2 * d : 0.f;
-                    dls[r][a] = 0.f;
-                    if (a == 0 && valid) s_vl += (double)(d * d);
-                }
-            } else if (net == 0) {
-                const bool is_act = a < A;
-                const float ls = is_act ? N.log_std[a] : 0.f, inv_s = expf(-ls);
-                const float y = (acts[r][a] - out) * inv_s;
-                float lp = is_act ? fmaf(-0.5f * y, y, -ls - LOG_SQRT_2PI_F) : 0.f;      // DiagGaussianDistribution.log_prob, summed over the row's eight lanes
-                lp += __shfl_xor(lp, 1); lp += __shfl_xor(lp, 2); lp += __shfl_xor(lp, 4);
-                const float lr = lp - r_old[r], ratio = expf(lr), ad = r_adv[r];
-                const float lo = 1.f - b.clip, hi = 1.f + b.clip;
-                const bool pass = !((ad > 0.f && ratio > hi) || (ad < 0.f && ratio < lo));  // min(A r, A clip(r)) has a gradient where the unclipped term is the smaller
-                const float g = (valid && pass) ? -(ad * ratio) * b.inv_b : 0.f;          // d loss / d log-prob of the row
-                dout[r][a] = is_act ? (g * y) * inv_s : 0.f;                              // d log-prob / d mean = y / sigma
-                dls[r][a] = is_act ? g * fmaf(y, y, -1.f) : 0.f;                          // d log-prob / d log_std = y^2 - 1
-                if (a == 0 && valid) {
-                    const float rc = fminf(fmaxf(ratio, lo), hi);
-                    s_pl -= (double)fminf(ad * ratio, ad * rc);
-                    s_kl += (double)((ratio - 1.f) - lr);
-                    s_cf += fabsf(ratio - 1.f) > b.clip ? 1.0 : 0.0;
-                }
-            } else if constexpr (VF) {
-                // clip_range_vf: Vp = old + clamp(V - old, -c, c).  Inside the closed band Vp is V itself (not re-rounded through old) and the row is the
-                // unclipped one; outside it the loss row takes old +- c formed in float32 and the gradient is exactly zero
-                const float d = out - r_ret[r], old = r_oldv[r], dv = out - old;
-                const bool inside = fabsf(dv) <= b.cvf;
-                const float dc = inside ? d : (dv > 0.f ? old + b.cvf : old - b.cvf) - r_ret[r];
-                dout[r][a] = (a == 0 && valid && inside) ? b.vf2 * d : 0.f;
-                dls[r][a] = 0.f;
-                if (a == 0 && valid) s_vl += (double)(dc * dc);
-            } else {
-                const float d = out - r_ret[r];
-                dout[r][a] = (a == 0 && valid) ? b.vf2 * d : 0.f;
-                dls[r][a] = 0.f;
-                if (a == 0 && valid) s_vl += (double)(d * d);
-            }
-        }
-        __syncthreads();
-        // ---- stage 4: head gradients dWh += dout' h2, d bias, d log_std ----
-        {
-#pragma unroll 8
-            for (int r = 0; r < PP_TM; ++r) {
-                const float hv = h2[r][hk];
-                awh0 = fmaf(dout[r][hq], hv, awh0); awh1 = fmaf(dout[r][hq + 4], hv, awh1);
-            }
-            if (tid < PP_MAXA) { for (int r = 0; r < PP_TM; ++r) asmall += dout[r][tid]; }
-            else if (tid >= 64 && tid < 64 + PP_MAXA) { for (int r = 0; r < PP_TM; ++r) asmall += dls[r][tid - 64]; }
-        }
-        __syncthreads();
-        // ---- stage 5: layer-2 deltas in place of h2: (dout Wh) (1 - h2^2); every word has one owner ----
-        {
-            float wc[PP_MAXA];
-#pragma unroll
-            for (int a = 0; a < PP_MAXA; ++a) wc[a] = whs[a][hk];
-#pragma unroll
-            for (int rr = 0; rr < 8; ++rr) {
-                const int r = 8 * hq + rr;
-                float s = 0.f;
-#pragma unroll
-                for (int a = 0; a < PP_MAXA; ++a) s = fmaf(dout[r][a], wc[a], s);        // (outputs >= O: zero times zero)
-                const float hv = h2[r][hk];
-                h2[r][hk] = s * fmaf(-hv, hv, 1.f);
-            }
-        }
-        __syncthreads();
-        // ---- stage 6: dW2 += delta2' h1 (8 x 8 per thread), d b2, and d h1 = delta2 W2 into registers ----
-        float dh[4][4];
-        {
-#pragma unroll 2
-            for (int r = 0; r < PP_TM; ++r) {
-                const float4 d0 = *reinterpret_cast<const float4*>(&h2[r][8 * cg]), d1 = *reinterpret_cast<const float4*>(&h2[r][8 * cg + 4]);
-                const float4 e0 = *reinterpret_cast<const float4*>(&h1[r][8 * kg]), e1 = *reinterpret_cast<const float4*>(&h1[r][8 * kg + 4]);
-                const float dv[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w}, ev[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) aw2[i][j] = fmaf(dv[i], ev[j], aw2[i][j]);
-            }
-            if (tid < PP_H2) { for (int r = 0; r < PP_TM; ++r) ab2 += h2[r][tid]; }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dh[i][j] = 0.f;
-#pragma unroll 2
-            for (int c = 0; c < PP_H2; c += 4) {
-                float dv[4][4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float4 d = *reinterpret_cast<const float4*>(&h2[4 * rg4 + i][c]);
-                    dv[i][0] = d.x; dv[i][1] = d.y; dv[i][2] = d.z; dv[i][3] = d.w;
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const float4 w = *reinterpret_cast<const float4*>(&W2R[(c + s) * PP_H1 + 4 * kq]);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        dh[i][0] = fmaf(dv[i][s], w.x, dh[i][0]); dh[i][1] = fmaf(dv[i][s], w.y, dh[i][1]);
-                        dh[i][2] = fmaf(dv[i][s], w.z, dh[i][2]); dh[i][3] = fmaf(dv[i][s], w.w, dh[i][3]);
-                    }
-                }
-            }
-        }
-        __syncthreads();                                         // the last read of h1 as activations by another thread is behind
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float4* p = reinterpret_cast<float4*>(&h1[4 * rg4 + i][4 * kq]);
-            const float4 hv = *p;
-            *p = make_float4(dh[i][0] * fmaf(-hv.x, hv.x, 1.f), dh[i][1] * fmaf(-hv.y, hv.y, 1.f), dh[i][2] * fmaf(-hv.z, hv.z, 1.f), dh[i][3] * fmaf(-hv.w, hv.w, 1.f));
-        }
-        __syncthreads();
-        // ---- stage 7: dW1 += delta1' x, d b1 ----
-#pragma unroll 4
-        for (int r = 0; r < PP_TM; ++r) {
-            const float dv = h1[r][j1];
-#pragma unroll
-            for (int i = 0; i < 10; ++i) aw1[i] = fmaf(dv, xs[r][10 * half + i], aw1[i]);
-            if (half == 0) ab1 += dv;
-        }
-        __syncthreads();
-    }
-
-    // ---- this workgroup's block: every word of its network's share is written, zeros included ----
-    float* __restrict__ part = work + (size_t)blockIdx.x * P;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) part[L.w2 + (8 * cg + i) * PP_H1 + 8 * kg + j] = aw2[i][j];
-#pragma unroll
-    for (int i = 0; i < 10; ++i)
-        if (10 * half + i < PP_OBS) part[L.w1 + j1 * PP_OBS + 10 * half + i] = aw1[i];
-    if (half == 0) part[L.b1 + j1] = ab1;
-    if (tid < PP_H2) part[L.b2 + tid] = ab2;
-    if (hq < O) part[L.wh + hq * PP_H2 + hk] = awh0;
-    if (hq + 4 < O) part[L.wh + (hq + 4) * PP_H2 + hk] = awh1;
-    if (tid < O) part[L.bh + tid] = asmall;
-    if (net == 0 && tid >= 64 && tid < 64 + A) part[P - A + (tid - 64)] = asmall;
-    double* sums = reinterpret_cast<double*>(work + ppo_off_sums(A)) + (size_t)blockIdx.x * 8;
-    const double t_pl = wg_sum(s_pl, red), t_kl = wg_sum(s_kl, red), t_cf = wg_sum(s_cf, red), t_vl = wg_sum(s_vl, red);
-    if (tid == 0) {
-        if (net == 0) { sums[0] = t_pl; sums[3] = t_kl; sums[4] = t_cf; }
-        else sums[1] = t_vl;
-    }
+    const PpoLay lay;
+#include "usim_ppo_grad_body.h"
 }
 
-__global__ __launch_bounds__(256) void usim_ppo_reduce_kernel(const float* __restrict__ work, int P, int A, float ent_coef, float* __restrict__ grad,
-                                                               const int32_t* gate) {
+// one parameter per thread: the `blocks` partial blocks in block order
+template <class Lay>
+DI void ppo_reduce(const float* __restrict__ work, const Lay lay, int P, int A, float ent_coef, float* __restrict__ grad, const int32_t* gate) {
     if (pp_stopped(gate)) return;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     float s = 0.f;
 #pragma unroll 8
-    for (int w = 0; w < PP_W; ++w) s += work[(size_t)w * P + p];
+    for (int w = 0; w < lay.blocks(); ++w) s += work[(size_t)w * P + p];
     if (p >= P - A) s -= ent_coef;
     grad[p] = s;
+}
+
+__global__ __launch_bounds__(256) void usim_ppo_reduce_kernel(const float* __restrict__ work, int P, int A, float ent_coef, float* __restrict__ grad,
+                                                               const int32_t* gate) {
+    ppo_reduce(work, PpoLay{}, P, A, ent_coef, grad, gate);
 }
 
 DI double sum_of_squares(const float* __restrict__ g, int P, double* lds) {
@@ -449,16 +195,17 @@ DI double sum_of_squares(const float* __restrict__ g, int P, double* lds) {
     return wg_sum(q, lds);
 }
 
-__global__ __launch_bounds__(PP_RED) void usim_ppo_finish_kernel(const float* __restrict__ work, const float* __restrict__ grad, const float* __restrict__ log_std, int P,
-                                                                 int A, int batch, float vf_coef, float ent_coef, float* __restrict__ stats, int32_t* gate,
-                                                                 float target_kl) {
+// one workgroup: the `rows` rows of loss sums in row order, the gradient's norm, the statistics, the gate
+template <class Lay>
+DI void ppo_finish(const float* __restrict__ work, const Lay lay, const float* __restrict__ grad, const float* __restrict__ log_std, int P, int A, int batch, float vf_coef,
+                   float ent_coef, float* __restrict__ stats, int32_t* gate, float target_kl) {
     __shared__ double red[PP_RED / 64];
     if (pp_stopped(gate)) return;                                 // (every thread has read the flag before the barriers below; thread 0 writes it behind them)
     const double norm = sqrt(sum_of_squares(grad, P, red));
     if (threadIdx.x != 0) return;
-    const double* sums = reinterpret_cast<const double*>(work + ppo_off_sums(A));
+    const double* sums = reinterpret_cast<const double*>(work + lay.sums(A));
     double pl = 0.0, vl = 0.0, kl = 0.0, cf = 0.0, ent = 0.0;
-    for (int w = 0; w < PP_W; ++w) { pl += sums[8 * w]; vl += sums[8 * w + 1]; kl += sums[8 * w + 3]; cf += sums[8 * w + 4]; }
+    for (int w = 0; w < lay.blocks(); ++w) { pl += sums[8 * w]; vl += sums[8 * w + 1]; kl += sums[8 * w + 3]; cf += sums[8 * w + 4]; }
     for (int a = 0; a < A; ++a) ent += (double)log_std[a];
     ent += A * (0.5 + 0.9189385332046727);                       // A / 2 (1 + log 2 pi)
     pl /= batch; vl /= batch; kl /= batch; cf /= batch;
@@ -471,8 +218,14 @@ __global__ __launch_bounds__(PP_RED) void usim_ppo_finish_kernel(const float* __
     }
 }
 
-// one thread: Adam's step count and, with a gate that is open, the gate's count of optimizer steps
-__global__ void usim_ppo_count_kernel(int32_t* __restrict__ step, int32_t* gate) {
+__global__ __launch_bounds__(PP_RED) void usim_ppo_finish_kernel(const float* __restrict__ work, const float* __restrict__ grad, const float* __restrict__ log_std, int P,
+                                                                 int A, int batch, float vf_coef, float ent_coef, float* __restrict__ stats, int32_t* gate,
+                                                                 float target_kl) {
+    ppo_finish(work, PpoLay{}, grad, log_std, P, A, batch, vf_coef, ent_coef, stats, gate, target_kl);
+}
+
+// Adam's step count and, with a gate that is open, the gate's count of optimizer steps
+DI void ppo_count(int32_t* __restrict__ step, int32_t* gate) {
     if (gate) {
         if (gate[0] != 0) return;
         gate[2] += 1;
@@ -480,9 +233,11 @@ __global__ void usim_ppo_count_kernel(int32_t* __restrict__ step, int32_t* gate)
     *step += 1;
 }
 
-__global__ __launch_bounds__(PP_RED) void usim_ppo_adam_kernel(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v,
-                                                               const int32_t* __restrict__ step, int P, float lr, float beta1, float beta2, float eps, float max_norm,
-                                                               float* __restrict__ stats, const int32_t* gate) {
+// one thread
+__global__ void usim_ppo_count_kernel(int32_t* __restrict__ step, int32_t* gate) { ppo_count(step, gate); }
+
+DI void ppo_adam(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v, const int32_t* __restrict__ step, int P, float lr,
+                 float beta1, float beta2, float eps, float max_norm, float* __restrict__ stats, const int32_t* gate) {
     __shared__ double red[PP_RED / 64];
     __shared__ double corr[2];
     if (pp_stopped(gate)) return;
@@ -502,6 +257,123 @@ __global__ __launch_bounds__(PP_RED) void usim_ppo_adam_kernel(float* __restrict
     m[i] = (float)mi; v[i] = (float)vi;
     theta[i] = (float)((double)theta[i] - ((double)lr / corr[0]) * (mi / denom));
 }
+
+__global__ __launch_bounds__(PP_RED) void usim_ppo_adam_kernel(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v,
+                                                               const int32_t* __restrict__ step, int P, float lr, float beta1, float beta2, float eps, float max_norm,
+                                                               float* __restrict__ stats, const int32_t* gate) {
+    ppo_adam(theta, grad, m, v, step, P, lr, beta1, beta2, eps, max_norm, stats, gate);
+}
+
+// ---- the population's forms (usim_ppo_grad_multi / usim_ppo_adam_multi): the member is one more grid axis (the last).  Every kernel states its member's pointers --
+// row k of the K-major tensors, rows [k rows, (k + 1) rows) of the data, region k of the workspace, row k of the hyper-parameter table -- and runs the body above,
+// so member k's words are the bits of a lone call.  The gradient launch has nb = min(W, tiles) workgroups per network and member instead of W: a lone workgroup
+// without a tile writes +0.0f into every word of its block and +0.0 into its loss sums, both reductions start from +0 and adding +0 to a sum that started from +0
+// never changes a bit (such a sum is never -0), so blocks nb .. W - 1 are left out of the launch, the workspace and both reductions.
+// A member's workspace region, in floats: nb partial blocks | the four packed matrices (16-byte aligned) | nb rows of 8 float64 sums | the two advantage words
+__host__ __device__ constexpr int ppo_multi_blocks(int batch) { return batch > (PP_W - 1) * PP_TM ? PP_W : (batch + PP_TM - 1) / PP_TM; }
+__host__ __device__ constexpr int64_t ppo_multi_off_pack(int A, int nb) { return ((int64_t)nb * ppo_params(A) + 3) / 4 * 4; }
+__host__ __device__ constexpr int64_t ppo_multi_off_sums(int A, int nb) { return ppo_multi_off_pack(A, nb) + 4 * PP_W2; }
+__host__ __device__ constexpr int64_t ppo_multi_off_adv(int A, int nb) { return ppo_multi_off_sums(A, nb) + 16 * nb; }
+__host__ __device__ constexpr int64_t ppo_multi_member_floats(int A, int nb) { return ppo_multi_off_adv(A, nb) + 4; }      // a multiple of 4
+
+// the table's row of a member (include/usim.h USIM_PPO_HYPER_WORDS)
+enum { HY_LR = 0, HY_CLIP = 1, HY_ENT = 2, HY_VF = 3, HY_MAXNORM = 4, HY_CVF = 5, HY_KL = 6 };
+
+struct PpoMulti {
+    const float* theta;                                           // [K][stride]
+    const float *obs, *act, *old_logp, *adv, *ret, *oldv;        // [K rows]...
+    const int32_t* index;                                         // [K][index_stride] or NULL
+    const float* hyper;                                           // [K][USIM_PPO_HYPER_WORDS]
+    int32_t* gate;                                                // [K][USIM_PPO_GATE_WORDS] or NULL
+    float *work, *grad, *stats;                                   // K regions; [K][stride]; [K][USIM_PPO_STATS]
+    int64_t region;                                               // floats of a member's workspace region
+    int stride, index_stride, rows, batch, adim, normalize, nb;
+    float inv_b;
+};
+
+// a member's workspace region and its row of theta as the gradient body reads them
+struct PpoMultiLay {
+    int nb;
+    DI int64_t pack(int A) const { return ppo_multi_off_pack(A, nb); }
+    DI int64_t sums(int A) const { return ppo_multi_off_sums(A, nb); }
+    DI int64_t adv(int A) const { return ppo_multi_off_adv(A, nb); }
+    DI int blocks() const { return nb; }
+};
+struct PpoField {                                                 // N.w1[net] of a flat row: the field's place in either network
+    const float* row; int at[2];
+    DI const float* operator[](int net) const { return row + (net ? at[1] : at[0]); }
+};
+struct PpoNetRow { PpoField w1, b1, b2, wh, bh; const float* log_std; };
+DI PpoNetRow pm_net(const float* th, int A) {
+    const PpoLayout p = ppo_layout(0, A), v = ppo_layout(1, A);
+    return {{th, {p.w1, v.w1}}, {th, {p.b1, v.b1}}, {th, {p.b2, v.b2}}, {th, {p.wh, v.wh}}, {th, {p.bh, v.bh}}, th + ppo_params(A) - A};
+}
+DI const float* pm_hyper(const PpoMulti& M, int k) { return M.hyper + (size_t)k * USIM_PPO_HYPER_WORDS; }
+DI int32_t* pm_gate(const PpoMulti& M, int k) { return M.gate ? M.gate + (size_t)k * USIM_PPO_GATE_WORDS : nullptr; }
+DI float* pm_work(const PpoMulti& M, int k) { return M.work + (size_t)k * M.region; }
+// member k's batch as a lone call states it (vf2 formed as the host forms it: float64, rounded once)
+template <bool VF>
+DI PpoBatch pm_batch(const PpoMulti& M, int k) {
+    const size_t r0 = (size_t)k * M.rows;
+    const float* h = pm_hyper(M, k);
+    return PpoBatch{M.obs + r0 * PP_OBS, M.act + r0 * M.adim, M.old_logp + r0, M.adv + r0, M.ret + r0, M.index ? M.index + (size_t)k * M.index_stride : nullptr,
+                    M.rows, M.batch, M.adim, M.normalize, h[HY_CLIP], M.inv_b, (float)(2.0 * (double)h[HY_VF] / M.batch), VF ? M.oldv + r0 : nullptr,
+                    VF ? h[HY_CVF] : 0.f, pm_gate(M, k)};
+}
+
+// grid (65, K)
+__global__ __launch_bounds__(PP_RED) void usim_ppo_prep_multi_kernel(PpoMulti M) {
+    const int k = blockIdx.y, A = M.adim;
+    const float* th = M.theta + (size_t)k * M.stride;
+    const PpoBatch b = pm_batch<false>(M, k);                     // (prep reads neither the old values nor clip_range_vf)
+    float* work = pm_work(M, k);
+    ppo_prep(th + ppo_layout(0, A).w2, th + ppo_layout(1, A).w2, b, work + ppo_multi_off_pack(A, M.nb), reinterpret_cast<double*>(work + ppo_multi_off_adv(A, M.nb)));
+}
+
+// grid (nb, 2, K)
+template <bool VF>
+__global__ __launch_bounds__(PP_WG) void usim_ppo_grad_multi_kernel(PpoMulti M) {
+    const int k = blockIdx.z;
+    constexpr int LOSS = PP_PPO;
+    const PpoNetRow N = pm_net(M.theta + (size_t)k * M.stride, M.adim);
+    const PpoBatch b = pm_batch<VF>(M, k);
+    float* __restrict__ work = pm_work(M, k);
+    const PpoMultiLay lay{M.nb};
+#include "usim_ppo_grad_body.h"
+}
+
+// grid (ceil(P / 256), K)
+__global__ __launch_bounds__(256) void usim_ppo_reduce_multi_kernel(PpoMulti M) {
+    const int k = blockIdx.y, A = M.adim;
+    ppo_reduce(pm_work(M, k), PpoMultiLay{M.nb}, ppo_params(A), A, pm_hyper(M, k)[HY_ENT], M.grad + (size_t)k * M.stride, pm_gate(M, k));
+}
+
+// grid (1, K)
+__global__ __launch_bounds__(PP_RED) void usim_ppo_finish_multi_kernel(PpoMulti M) {
+    const int k = blockIdx.y, A = M.adim;
+    const float* h = pm_hyper(M, k);
+    ppo_finish(pm_work(M, k), PpoMultiLay{M.nb}, M.grad + (size_t)k * M.stride,
+               M.theta + (size_t)k * M.stride + ppo_params(A) - A, ppo_params(A), A, M.batch, h[HY_VF], h[HY_ENT], M.stats + (size_t)k * USIM_PPO_STATS, pm_gate(M, k),
+               h[HY_KL]);
+}
+
+// one thread per member
+__global__ __launch_bounds__(256) void usim_ppo_count_multi_kernel(int32_t* __restrict__ step, int32_t* gate, int members) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < members) ppo_count(step + k, gate ? gate + (size_t)k * USIM_PPO_GATE_WORDS : nullptr);
+}
+
+// grid (ceil(P / 1024), K)
+__global__ __launch_bounds__(PP_RED) void usim_ppo_adam_multi_kernel(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m, float* __restrict__ v,
+                                                                     const int32_t* __restrict__ step, int stride, int P, const float* __restrict__ hyper, float beta1,
+                                                                     float beta2, float eps, float* __restrict__ stats, const int32_t* gate) {
+    const int k = blockIdx.y;
+    const size_t o = (size_t)k * stride;
+    const float* h = hyper + (size_t)k * USIM_PPO_HYPER_WORDS;
+    ppo_adam(theta + o, grad + o, m + o, v + o, step + k, P, h[HY_LR], beta1, beta2, eps, h[HY_MAXNORM], stats ? stats + (size_t)k * USIM_PPO_STATS : nullptr,
+             gate ? gate + (size_t)k * USIM_PPO_GATE_WORDS : nullptr);
+}
+
 
 }  // namespace usim
 
@@ -583,4 +455,52 @@ extern "C" int usim_ppo_adam_gated(float* theta_dev, const float* grad_dev, floa
 extern "C" int usim_ppo_adam(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int params, float lr, float beta1, float beta2,
                              float eps, float max_grad_norm, float* stats_dev, void* stream) {
     return usim_ppo_adam_gated(theta_dev, grad_dev, m_dev, v_dev, step_dev, params, lr, beta1, beta2, eps, max_grad_norm, stats_dev, nullptr, stream);
+}
+
+// ---- the population's calls ----
+static bool multi_sizes_ok(int stride, int members, int params) {
+    return members >= 1 && members <= USIM_POLICY_MAX_MEMBERS && params >= 1 && stride >= params && stride % 4 == 0;
+}
+
+extern "C" int64_t usim_ppo_work_floats_multi(int act_dim, int members, int batch) {
+    using namespace usim;
+    if (act_dim < 1 || act_dim > PP_MAXA || members < 1 || members > USIM_POLICY_MAX_MEMBERS || batch < 1) return (int64_t)USIM_ERR_INVALID;
+    return (int64_t)members * ppo_multi_member_floats(act_dim, ppo_multi_blocks(batch));
+}
+
+extern "C" int usim_ppo_grad_multi(const float* theta_dev, int stride, int members, const usim_ppo_batch_multi* b, float* work_dev, float* grad_dev, float* stats_dev,
+                                   void* stream) {
+    using namespace usim;
+    if (!theta_dev || !b || !work_dev || !grad_dev || !stats_dev || (reinterpret_cast<uintptr_t>(work_dev) & 15)) return USIM_ERR_INVALID;
+    if (!b->obs_dev || !b->act_dev || !b->old_logp_dev || !b->adv_dev || !b->ret_dev || !b->hyper_dev) return USIM_ERR_INVALID;
+    if (b->act_dim < 1 || b->act_dim > PP_MAXA || b->batch < 1 || b->rows < 1 || (!b->index_dev && b->rows < b->batch)) return USIM_ERR_INVALID;
+    if (b->batch > INT32_MAX - PP_LOADS * PP_RED) return USIM_ERR_INVALID;                  // (as usim_ppo_grad)
+    const int A = b->act_dim, P = ppo_params(A);
+    if (!multi_sizes_ok(stride, members, P) || (int64_t)members * b->rows > INT32_MAX) return USIM_ERR_INVALID;
+    if (b->index_dev && b->index_stride < b->batch) return USIM_ERR_INVALID;
+    if (b->value_clip && !b->old_value_dev) return USIM_ERR_INVALID;
+    const int nb = ppo_multi_blocks(b->batch);
+    const PpoMulti M{theta_dev, b->obs_dev, b->act_dev, b->old_logp_dev, b->adv_dev, b->ret_dev, b->old_value_dev, b->index_dev, b->hyper_dev, b->gate_dev,
+                     work_dev, grad_dev, stats_dev, ppo_multi_member_floats(A, nb), stride, b->index_stride, b->rows, b->batch, A, b->normalize_advantage, nb,
+                     (float)(1.0 / b->batch)};
+    const hipStream_t s = (hipStream_t)stream;
+    const unsigned K = (unsigned)members;
+    hipLaunchKernelGGL(usim_ppo_prep_multi_kernel, dim3(1 + 2 * PP_W2 / PP_RED, K), dim3(PP_RED), 0, s, M);
+    if (b->value_clip) hipLaunchKernelGGL(usim_ppo_grad_multi_kernel<true>, dim3(nb, 2, K), dim3(PP_WG), 0, s, M);
+    else hipLaunchKernelGGL(usim_ppo_grad_multi_kernel<false>, dim3(nb, 2, K), dim3(PP_WG), 0, s, M);
+    hipLaunchKernelGGL(usim_ppo_reduce_multi_kernel, dim3((P + 255) / 256, K), dim3(256), 0, s, M);
+    hipLaunchKernelGGL(usim_ppo_finish_multi_kernel, dim3(1, K), dim3(PP_RED), 0, s, M);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
+}
+
+extern "C" int usim_ppo_adam_multi(float* theta_dev, const float* grad_dev, float* m_dev, float* v_dev, int32_t* step_dev, int stride, int members, int params,
+                                   const float* hyper_dev, float beta1, float beta2, float eps, float* stats_dev, int32_t* gate_dev, void* stream) {
+    using namespace usim;
+    if (!theta_dev || !grad_dev || !m_dev || !v_dev || !step_dev || !hyper_dev || !multi_sizes_ok(stride, members, params)) return USIM_ERR_INVALID;
+    if (!nonneg_finite(eps) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return USIM_ERR_INVALID;
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(usim_ppo_count_multi_kernel, dim3((members + 255) / 256), dim3(256), 0, s, step_dev, gate_dev, members);
+    hipLaunchKernelGGL(usim_ppo_adam_multi_kernel, dim3((params + PP_RED - 1) / PP_RED, (unsigned)members), dim3(PP_RED), 0, s, theta_dev, grad_dev, m_dev, v_dev, step_dev,
+                       stride, params, hyper_dev, beta1, beta2, eps, stats_dev, gate_dev);
+    return hipGetLastError() == hipSuccess ? USIM_OK : USIM_ERR_HIP;
 }

@@ -14,8 +14,12 @@ seed) compute -- tests/test_gpu_population_rollout.py, tests/test_gpu_population
     collector = PopulationRollout(env, pop, vn, buffer, seed=0)
     ppo = PopulationPPO(env, pop, vn, buffer, collector, seeds=[0, 1, 2, 3], learning_rate=[3e-4, 3e-4, 1e-4, 1e-4]); ppo.learn(40)
 
-Still out: a multi form of usim_policy_step_fused (its cross-workgroup wait would have to become per member), the time-limit bootstrap (refused), learners running
-concurrently (PopulationPPO runs its K updates one after the other on the env's stream)."""
+    ppo = PopulationPPO(env, pop, vn, buffer, collector, seeds=range(32), learning_rate=list(sweep), concurrent=True)     # one gradient launch for all K members
+
+PopulationPPO(concurrent=True) is the learner's side of the same idea (include/usim.h usim_ppo_grad_multi / usim_ppo_adam_multi): the member is a grid axis of the
+learner's kernels, a minibatch step of K members is the launches of one, and every member's words are the bits of its lone update.
+
+Still out: a multi form of usim_policy_step_fused (its cross-workgroup wait would have to become per member) and the time-limit bootstrap (refused)."""
 import ctypes as C
 import math
 import time
@@ -333,29 +337,142 @@ def _per_member(name, value, K):
     return [value] * K
 
 
+_SHARED = ("n_epochs", "batch_size", "normalize_advantage", "adam_eps")      # one value for all members of a concurrent population: they shape the launches
+
+
+def _check_concurrent(per):
+    """the refusals of PopulationPPO(concurrent=True) (ValueError, before the library is loaded); `per`: keyword -> its K values"""
+    for name in _SHARED:
+        v = per.get(name)
+        for k in range(1, len(v) if v else 0):
+            if v[k] != v[0]:
+                raise ValueError(f"concurrent=True: {name} must be the same for all members, member 0 has {v[0]!r} and member {k} has {v[k]!r}; the members of "
+                                 f"one launch share it (learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, target_kl and the value of clip_range_vf may differ)")
+    v = per.get("clip_range_vf")
+    if v:
+        for k in range(1, len(v)):
+            if (v[k] is None) != (v[0] is None):
+                raise ValueError(f"concurrent=True: clip_range_vf must be set for all members or for none (value clipping is an instance of the gradient kernel), "
+                                 f"member 0 has {v[0]!r} and member {k} has {v[k]!r}")
+
+
 class PopulationPPO:
     """K ppo.NativePPO learners over one PopulationRollout: member k's learner sees population.member(k), vecnorm.member(k) and its columns of the shared buffer
     (n_envs = G), and computes what a lone NativePPO computes on a shard.  `seeds` (K minibatch-shuffle seeds) and every keyword of NativePPO, each one value for
     all members or a sequence of K: several seeds of one configuration, or a sweep.  update() runs the K updates one after the other, then collector.pack() once.
     history[k]: member k's rows as NativePPO.learn() writes them (time/*, train/*); with a monitor attached to the env (before the collector was built) also
     rollout/ep_rew_mean and rollout/ep_len_mean over member k's rows of the monitor's ring.  The ring is SHARED: its `window` last episodes of ALL members, so a
-    member's mean runs over roughly window / K episodes -- size the window K times SB3's 100 for the same smoothing."""
+    member's mean runs over roughly window / K episodes -- size the window K times SB3's 100 for the same smoothing.
 
-    def __init__(self, env, population, vecnorm, buffer, collector, *, seeds, **hyper):
+    concurrent=True runs the K updates as ONE chain of launches (usim_ppo_grad_multi / usim_ppo_adam_multi: the member is a grid axis), bit for bit the updates of
+    the sequential path.  n_epochs, batch_size, normalize_advantage and adam_eps must then be one value for all members, and clip_range_vf set for all or for none
+    (ValueError before the library is loaded); learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, target_kl, the value of clip_range_vf (callables
+    included) and the seeds stay per member.  The population then owns grad, exp_avg, exp_avg_sq [K, stride], step_count [K], stats / first_stats [K, 8], gate
+    [K, 4], index [K, rollout], the hyper-parameter table and the workspace; every learner's attributes of those names are views of its row, so adam_state_dict,
+    save_checkpoint, load_checkpoint, history and a member's lone update() keep working on the same memory.  It is meant for many small members, where a lone
+    update is launch-bound and leaves most of its 256 gradient workgroups without a tile; with few large members (each minibatch already of 4096 rows or more) a
+    lone gradient launch fills the device and the gain is smaller (1.15 times at 4 x 4096 environments); with ONE member leave it off: the concurrent update is 1.9 %
+    slower than the lone one there (27.2 against 26.7 ms) -- profiles/population_learner/cost.txt has the measured points."""
+
+    def __init__(self, env, population, vecnorm, buffer, collector, *, seeds, concurrent=False, **hyper):
         from .ppo import NativePPO
         K, G = _check_population(env, population, vecnorm, buffer)
         seeds = _per_member("seeds", seeds, K)
         per = {name: _per_member(name, v, K) for name, v in hyper.items()}
+        if concurrent:
+            _check_concurrent(per)
         self.env, self.population, self.vecnorm, self.buffer, self.collector = env, population, vecnorm, buffer, collector
-        self.members, self.envs_per_member = K, G
-        self.learners = [NativePPO(env, population.member(k), vecnorm.member(k), _BufferSlice(buffer, k, G), None, seed=seeds[k],
-                                   **{name: v[k] for name, v in per.items()}) for k in range(K)]
+        self.members, self.envs_per_member, self.concurrent = K, G, bool(concurrent)
+        self.learners = []
+        for k in range(K):
+            self.learners.append(NativePPO(env, population.member(k), vecnorm.member(k), _BufferSlice(buffer, k, G), None, seed=seeds[k],
+                                           **{name: v[k] for name, v in per.items()}))
+            if concurrent:
+                self._seat_learner(k)
         self.history = [[] for _ in range(K)]
 
+    def _seat_learner(self, k):
+        """concurrent=True: learner k's gradient, moments, step count, statistics, gate and index list become views of row k of the population's tensors (built with
+        learner 0), and all learners share learner 0's lone workspace -- a member's lone update() stays valid on the same memory, K workspaces are not kept"""
+        l, pop, K = self.learners[k], self.population, self.members
+        if k == 0:
+            dev, P = l.device, pop.params
+            z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
+            self.lib, self.device = l.lib, dev
+            self.grad, self.exp_avg, self.exp_avg_sq = z(K, pop.stride), z(K, pop.stride), z(K, pop.stride)
+            self.step_count, self.gate = z(K, dtype=torch.int32), z(K, _lib.PPO_GATE_WORDS, dtype=torch.int32)
+            self.stats, self.first_stats = z(K, _lib.PPO_STATS), z(K, _lib.PPO_STATS)
+            self.index, self.hyper = z(K, l.rollout, dtype=torch.int32), z(K, _lib.PPO_HYPER_WORDS)
+            self._hyper_host = torch.zeros(K, _lib.PPO_HYPER_WORDS, dtype=torch.float32).pin_memory()
+            self._ev, self._std = z(K), z(K)                                 # train/explained_variance and train/std of the last update(), per member
+            floats = int(self.lib.usim_ppo_work_floats_multi(pop.act_dim, K, l.batch_size))
+            if floats < 0:
+                _lib.check(self.lib, floats, None)
+            self._work = z(floats)
+        P = pop.params
+        l.grad, l.exp_avg, l.exp_avg_sq = self.grad[k, :P], self.exp_avg[k, :P], self.exp_avg_sq[k, :P]
+        l.step_count, l.stats, l.first_stats, l.gate, l._index = self.step_count[k:k + 1], self.stats[k], self.first_stats[k], self.gate[k], self.index[k]
+        l._work = self.learners[0]._work
+
     def update(self):
-        """the K updates (NativePPO.update), then the collector's pack(); -> the K statistics dictionaries"""
+        """the K updates, then the collector's pack(); -> the K statistics dictionaries.  concurrent=False: NativePPO.update of every member, one after the other.
+        concurrent=True: the same updates with the member as a grid axis -- the shared buffer is flattened once (environment-major: member k's rows are
+        contiguous and are the rows of its lone flatten), the hyper-parameter table is written and the gates are cleared once, every epoch draws the K
+        torch.randperm from the members' own generators (the draws of the sequential path, so the two paths and a member's lone update() are interchangeable
+        mid-run), every minibatch is ONE usim_ppo_grad_multi and ONE usim_ppo_adam_multi, and one host read at the end brings all members' statistics, gates,
+        explained variances and train/std.  Return value, every learner's last_update and every word of the members' state are those of the sequential path."""
+        if self.concurrent:
+            return self._update_concurrent()
         out = [l.update() for l in self.learners]
         self.collector.pack()
+        return out
+
+    def _update_concurrent(self):
+        from .ppo import STAT_NAMES
+        b, ls, K, G, lib, pop = self.buffer, self.learners, self.members, self.envs_per_member, self.lib, self.population
+        if not b.full:
+            raise RuntimeError("rollout buffer is not full")
+        check = lambda rc: _lib.check(lib, rc, None)
+        T, l0 = int(b.buffer_size), ls[0]
+        N, batch, A, P = l0.rollout, l0.batch_size, pop.act_dim, pop.params
+        # usim_explained_variance per member on its [T, G] block in the order of its lone update (K launches into K words)
+        values, returns = (x.reshape(T, K, G).transpose(0, 1).contiguous() for x in (b.values, b.returns))
+        for k in range(K):
+            check(lib.usim_explained_variance(values[k].data_ptr(), returns[k].data_ptr(), T * G, self._ev.data_ptr() + 4 * k, _stream(self.device)))
+        cvf = [l.current_clip_range_vf() for l in ls]
+        value_clip = cvf[0] is not None
+        obs, act, lp, adv, ret = (l0._flat(x) for x in (b.observations, b.actions, b.log_probs, b.advantages, b.returns))
+        old = l0._flat(b.values) if value_clip else None
+        self._hyper_host.copy_(torch.tensor([[l.current_lr(), l.current_clip_range(), l.ent_coef, l.vf_coef, l.max_grad_norm, cvf[k] or 0.0, l.target_kl or 0.0, 0.0]
+                                             for k, l in enumerate(ls)], dtype=torch.float32))
+        self.hyper.copy_(self._hyper_host, non_blocking=True)                # from pinned memory, in stream order: the host does not wait (update() ends with a read)
+        self.gate.zero_()
+        ptr = lambda t: t.data_ptr()
+        steps = 0
+        for _ in range(l0.n_epochs):
+            for k, l in enumerate(ls):
+                self.index[k].copy_(torch.randperm(N, device=self.device, generator=l.generator))
+            for i in range(0, N, batch):
+                n = min(batch, N - i)
+                mb = _lib.UsimPpoBatchMulti(ptr(obs), ptr(act), ptr(lp), ptr(adv), ptr(ret), None if old is None else ptr(old), ptr(self.index) + 4 * i, ptr(self.hyper),
+                                            ptr(self.gate), N, N, n, A, int(l0.normalize_advantage), int(value_clip))
+                check(lib.usim_ppo_grad_multi(ptr(pop.theta), pop.stride, K, C.byref(mb), ptr(self._work), ptr(self.grad), ptr(self.stats), _stream(self.device)))
+                check(lib.usim_ppo_adam_multi(ptr(pop.theta), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self.step_count), pop.stride, K, P,
+                                              ptr(self.hyper), 0.9, 0.999, l0.adam_eps, ptr(self.stats), ptr(self.gate), _stream(self.device)))
+                if steps == 0:
+                    self.first_stats.copy_(self.stats)
+                steps += 1
+        self.collector.pack()
+        std = torch.exp(pop.theta[:, P - A:P])
+        for k in range(K):                                                   # the lone update's reduction, member by member: the same bits
+            torch.mean(std[k], dim=0, keepdim=True, out=self._std[k:k + 1])
+        s = torch.cat((self.stats.reshape(-1), self._ev, self._std, self.gate.to(torch.float32).reshape(-1))).tolist()      # one read for all members
+        n, out = _lib.PPO_STATS, []
+        for k, l in enumerate(ls):
+            stop, evaluated, done = (int(x) for x in s[(n + 2) * K + 4 * k:(n + 2) * K + 4 * k + 3])
+            l.last_update = {"train/clip_range": l.current_clip_range(), **({} if cvf[k] is None else {"train/clip_range_vf": cvf[k]}), "train/std": s[(n + 1) * K + k],
+                             "train/optimizer_steps": done, "train/minibatches_evaluated": evaluated, "train/early_stop": stop}
+            out.append(dict(zip(STAT_NAMES, s[n * k:n * k + 6] + [s[n * K + k]])))
         return out
 
     def learn(self, iterations):

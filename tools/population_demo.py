@@ -5,10 +5,11 @@
       every NAME.zip in FOLDER that has its vec_normalize_NAME.pkl beside it -- the checkpoints a training run leaves behind (src/rl.py:133, forty per run) -- becomes
       one member; evaluate_population plays `--episodes` deterministic episodes per member in ONE run and the ranking by mean return is printed
 
-  python tools/population_demo.py train [--members 4] [--envs-per-member 4096] [--steps 128] [--iterations 10] [--sequential] [--save FOLDER]
+  python tools/population_demo.py train [--members 4] [--envs-per-member 4096] [--steps 128] [--iterations 10] [--concurrent] [--sequential] [--save FOLDER]
       K seeds of `tracking` trained side by side (PopulationRollout + PopulationPPO, SB3's initialisation per member); every iteration prints each member's raw reward
       per step and rollout/ep_rew_mean.  --sequential: the same K runs one after the other (policy.FusedRollout(fused_stats=False) + ppo.NativePPO on shard
-      environments: the runs the population equals bit for bit) -- the wall time to compare with"""
+      environments: the runs the population equals bit for bit) -- the wall time to compare with.  --concurrent: PopulationPPO(concurrent=True), the K updates
+      as one chain of launches (usim_ppo_grad_multi / usim_ppo_adam_multi) instead of one after the other; the same bits"""
 import argparse
 import importlib
 import sys
@@ -65,14 +66,14 @@ def train(a):
         buf = P.DeviceRolloutBuffer(T, K * G, 19, env.action_dim, device=DEV)
         env.attach_monitor(usim.DeviceMonitor(env, window=100 * K))           # before the collector is built; the ring is shared by the members
         coll = M.PopulationRollout(env, pop, vn, buf, seed=0)
-        ppo = M.PopulationPPO(env, pop, vn, buf, coll, seeds=list(range(K)), n_epochs=4)
+        ppo = M.PopulationPPO(env, pop, vn, buf, coll, seeds=list(range(K)), n_epochs=4, concurrent=a.concurrent)
         torch.cuda.synchronize(); t0 = time.time()
         for it in range(a.iterations):
             ppo.learn(1)
             raw = (coll.raw_reward_sum / (T * G)).tolist()
             print(f"iter {it:3d}  " + "  ".join(f"[{k}] r/step {raw[k]:6.3f} ep_rew {ppo.history[k][-1]['rollout/ep_rew_mean']:8.2f}" for k in range(K)), flush=True)
         torch.cuda.synchronize()
-        print(f"population: {K} members x {G} environments x {T} steps x {a.iterations} iterations in {time.time() - t0:.2f} s (wall, set-up and capture excluded)")
+        print(f"population{' (concurrent learners)' if a.concurrent else ''}: {K} members x {G} environments x {T} steps x {a.iterations} iterations in {time.time() - t0:.2f} s (wall, set-up and capture excluded)")
         if a.save:
             for z, p in ppo.save_checkpoint(a.save, [f"seed_{k}" for k in range(K)]):
                 print("wrote", z, p)
@@ -107,6 +108,7 @@ def main():
     t = sub.add_parser("train")
     t.add_argument("--members", type=int, default=4); t.add_argument("--envs-per-member", type=int, default=4096); t.add_argument("--steps", type=int, default=128)
     t.add_argument("--iterations", type=int, default=10); t.add_argument("--sequential", action="store_true"); t.add_argument("--save", default=None)
+    t.add_argument("--concurrent", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("population_demo.py needs a GPU; the simulator has no CPU fallback")
